@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: EM iterations/sec of the vLGP variational-EM loop.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2], "C3"): 200 trials x 1000 bins x 100 Poisson
@@ -13,10 +13,12 @@ norms) over all 4000 fifty-bin segments -- the body of core.vem
 With N > 1 the 200 trials are block-partitioned over the ranks (strong
 scaling: total work fixed) and the M/H-step statistics are all-reduced by RCCL.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement); the
-extra objects are ``roofline`` (dominant kernel, HIP-event timed on the
-engine's stream inside the timed region) and ``cpu_baseline`` (the NumPy/SciPy
-oracle timed on a bounded sample of the same workload on this host).
+Prints ONE JSON line on rank 0: the headline (``value``, ``ms_per_step``) and
+what the timed session's own timers say.  ``--full`` adds what takes runs of
+its own: ``kernels`` / ``roofline`` / ``h_step`` (per-kernel HIP-event timings
+from a second session) and ``cpu_baseline`` (the NumPy/SciPy oracle timed on a
+bounded sample of the same workload on this host).  ``--dump-outputs DIR``
+writes what the last timed EM iteration computed as ``DIR/<name>.npy``.
 """
 import argparse
 import json
@@ -162,6 +164,14 @@ def host_info():
     return model, os.cpu_count() or 1
 
 
+def blas_threads():
+    """Threads the BLAS pool was started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else every core).  Never ask
+    for more: an OpenBLAS has buffers for the threads it started with and crashes when raised above them."""
+    from threadpoolctl import threadpool_info
+
+    return max([m.get("num_threads", 1) for m in threadpool_info() if m.get("user_api") == "blas"] or [1])
+
+
 def _oracle_em_iteration(name, budget_trials, threads):
     """One timed EM iteration (the 2nd of two) of the oracle on the first ``budget_trials`` trials."""
     from oracle import vlgp_oracle as O
@@ -197,8 +207,9 @@ def _oracle_em_iteration(name, budget_trials, threads):
 def cpu_baseline(name, budget_trials):
     """The oracle's EM iteration on a bounded sample of the same workload, on this host, scaled to the full
     trial count: with one BLAS thread (the reference is effectively single-core) and
-    with OPENBLAS threads = nproc (50x50 matrices do not thread -- reported, not the baseline)."""
+    with every thread of the BLAS pool (50x50 matrices do not thread -- reported, not the baseline)."""
     model, nproc = host_info()
+    nthreads = blas_threads()
     per1, (e1, m1, h1), wall1, nseg, n_trials = _oracle_em_iteration(name, budget_trials, 1)
     scale = n_trials / float(budget_trials)
     out = {
@@ -209,12 +220,40 @@ def cpu_baseline(name, budget_trials):
                   % (budget_trials, n_trials, nseg, e1, m1, h1, scale, wall1),
         "e_step_ms_full": 1e3 * e1 * scale,
     }
-    if nproc > 1:
+    if nthreads > 1:
         half = max(min(budget_trials // 2, 6), 1)   # a side note (50 x 50 matrices do not thread): kept short
-        pern, _, walln, _, _ = _oracle_em_iteration(name, half, nproc)
-        out["all_threads"] = {"value": 1.0 / (pern * n_trials / float(half)), "unit": "EM it/s", "cores": nproc,
-                              "sample": "same on the first %d trials with %d BLAS threads; %.0fs wall" % (half, nproc, walln)}
+        pern, _, walln, _, _ = _oracle_em_iteration(name, half, nthreads)
+        out["all_threads"] = {"value": 1.0 / (pern * n_trials / float(half)), "unit": "EM it/s", "cores": nthreads,
+                              "sample": "same on the first %d trials with %d BLAS threads; %.0fs wall" % (half, nthreads, walln)}
     return out
+
+
+DUMP_BYTES = 60 * 10 ** 6   # under 64 MB with the .npy headers
+
+
+def dump_outputs(sess, out_dir):
+    """What a caller of the timed EM iteration holds after it, as ``out_dir/<name>.npy`` (float64): the parameters
+    (a, b, noise, omega, sigma) and the segments' posterior (mu, v, w, dmu as (rows, latents), rows in the order of the
+    segment list).  When the posterior would take the dump past DUMP_BYTES, a fixed sample of its rows (seed 0, sorted)
+    is written instead, with their indices as ``posterior_rows``.  With several ranks: this rank's shard."""
+    p, eng, segs = sess.params, sess.eng, sess.segs
+    arrays = {k: np.asarray(p[k], dtype=np.float64) for k in ("a", "b", "noise", "omega", "sigma")}
+    keys = ("mu", "v", "w", "dmu")
+    got = eng.download(segs.set_id, keys)
+    _, _, off = eng.sets[segs.set_id]
+    units = np.arange(len(segs)) if segs.unit_of is None else np.asarray(segs.unit_of)
+    rows = np.concatenate([np.arange(off[u], off[u + 1]) for u in units])
+    per_row = 8 * (len(keys) * eng.L + 1)
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // per_row
+    if len(rows) > room:
+        pick = np.sort(np.random.default_rng(0).choice(len(rows), room, replace=False))
+        rows = rows[pick]
+        arrays["posterior_rows"] = pick.astype(np.float64)
+    for k in keys:
+        arrays[k] = got[k][rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def self_launch(n):
@@ -263,6 +302,12 @@ def main():
                     help="untimed EM iterations first (the first four run the rank 17-32 classes of the E-step: "
                          "omega starts at its upper bound)")
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (parameters, segments' posterior) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: per-kernel timings and roofline from a second "
+                         "session (--kernel-steps) and the CPU baseline (unless --no-cpu-baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--allow-shm", action="store_true",
                     help="tests only: accept the host shared-memory transport (several ranks on ONE GPU); a multi-GPU "
@@ -273,7 +318,7 @@ def main():
                     help="CPU baseline on the WHOLE workload (one full-size oracle EM iteration, about four minutes "
                          "for C3 on one core) instead of the bounded sample; quoted once in DESIGN.md")
     ap.add_argument("--kernel-steps", type=int, default=6,
-                    help="extra EM iterations after the timed region, M-step serialised, for the per-kernel timings")
+                    help="with --full: EM iterations of a second session, M-step serialised, for the per-kernel timings")
     args = ap.parse_args()
 
     import vlgp_amd
@@ -306,6 +351,8 @@ def main():
 
     for _ in range(args.warmup):
         sess.em_iteration()
+    # the timed region has always run with the per-launch events on (they also keep the M-step off its graph path):
+    # kept in every run, so that `value` is the same measurement with and without --full
     eng.profile(True)
     eng.profile_reset()
     eng.barrier()
@@ -348,7 +395,9 @@ def main():
     transport = eng.transport
     rccl_ranks = eng.rccl_ranks  # from ncclCommCount, not from WORLD_SIZE: what RCCL saw
     hstat = [float(v) for v in eng.hstep_stats()]
-    if world == 1 and args.kernel_steps > 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sess, args.dump_outputs)
+    if args.full and world == 1 and args.kernel_steps > 0:
         # (round 6) a SECOND session, warmed up like the first: its kernel_steps iterations are EM iterations
         # warmup + 1 ... warmup + kernel_steps of the same fit, i.e. the first iterations of the timed region -- same
         # ranks, same rank classes of every kernel (until round 5 they were the iterations AFTER the timed region,
@@ -395,6 +444,34 @@ def main():
     sess.close()
 
     if rank != 0:
+        return
+
+    out = {
+        "metric": "EM iterations/sec", "value": args.steps / elapsed, "unit": "EM it/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": ("%s: %d trials x %d bins x %d Poisson channels, %d latents, window %d -> %d segments; "
+                                "Eniter=Mniter=25, rank 50, VB, Hstep on" % (args.workload, n_trials, n_bins, N, L,
+                                                                              cfg["window"], n_seg)) if lik is None else
+                               ("%s: %d ragged trials of 500 ... %d bins (%d bins in all) x %d channels (%d Poisson + %d "
+                                "Gaussian), %d latents, window %d -> %d segments; Eniter=Mniter=25, rank 50, VB, Hstep on"
+                                % (args.workload, n_trials, n_bins, sum(int(tr["y"].shape[0]) for tr in trials), N,
+                                   N - C5_GAUSS, C5_GAUSS, L, cfg["window"], n_seg)),
+                   "parallelism": "trials sharded over %d rank(s)%s" % (
+                       world, "" if world == 1 else "; all-reduce of the M-step statistics and norms over " + transport +
+                       ", H-step round sums added on the host (shared memory)"),
+                   "transport": transport, "rccl_ranks": int(rccl_ranks[0]), "rccl_ranks_m_lane": int(rccl_ranks[1]),
+                   "rccl_ranks_source": "ncclCommCount of the handle's communicators"},
+        "ms_per_e_step": phase_ms["e"], "ms_per_m_step": phase_ms["m"], "ms_per_h_step": phase_ms["h"],
+        "ms_per_step_per_rank": per_rank_ms,
+        # every timed EM iteration's own timers (runtime lists of vlgp/core.py:307-331), rank 0
+        "phase_ms_per_step": {k: [round(1e3 * float(t), 3) for t in rt[k + "_elapsed"][timed]] for k in ("e", "m", "h", "em")},
+        "value_survey_protocol": survey["value"] if survey else None, "survey_protocol": survey,
+        "effective_rank": ranks_used, "effective_rank_per_step": ranks_per_step, "omega_final": omega,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
         return
 
     T = cfg["window"]
@@ -566,28 +643,7 @@ def main():
                                       "(profiles/r*/pmc_summary.json: FETCH_SIZE x 2 + WRITE_SIZE, separate passes); "
                                       "not collected in this run"}
 
-    out = {
-        "metric": "EM iterations/sec", "value": args.steps / elapsed, "unit": "EM it/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": ("%s: %d trials x %d bins x %d Poisson channels, %d latents, window %d -> %d segments; "
-                                "Eniter=Mniter=25, rank 50, VB, Hstep on" % (args.workload, n_trials, n_bins, N, L,
-                                                                              cfg["window"], n_seg)) if lik is None else
-                               ("%s: %d ragged trials of 500 ... %d bins (%d bins in all) x %d channels (%d Poisson + %d "
-                                "Gaussian), %d latents, window %d -> %d segments; Eniter=Mniter=25, rank 50, VB, Hstep on"
-                                % (args.workload, n_trials, n_bins, sum(int(tr["y"].shape[0]) for tr in trials), N,
-                                   N - C5_GAUSS, C5_GAUSS, L, cfg["window"], n_seg)),
-                   "parallelism": "trials sharded over %d rank(s)%s" % (
-                       world, "" if world == 1 else "; all-reduce of the M-step statistics and norms over " + transport +
-                       ", H-step round sums added on the host (shared memory)"),
-                   "transport": transport, "rccl_ranks": int(rccl_ranks[0]), "rccl_ranks_m_lane": int(rccl_ranks[1]),
-                   "rccl_ranks_source": "ncclCommCount of the handle's communicators"},
-        "ms_per_e_step": phase_ms["e"], "ms_per_m_step": phase_ms["m"], "ms_per_h_step": phase_ms["h"],
-        "ms_per_step_per_rank": per_rank_ms,
-        # every timed EM iteration's own timers (runtime lists of vlgp/core.py:307-331), rank 0
-        "phase_ms_per_step": {k: [round(1e3 * float(t), 3) for t in rt[k + "_elapsed"][timed]] for k in ("e", "m", "h", "em")},
-        "value_survey_protocol": survey["value"] if survey else None, "survey_protocol": survey,
+    out.update({
         "roofline": roofline, "kernels": kernels,
         # the H-step beyond its kernel: dependent L-BFGS-B rounds of the timed region, their kernel time at the stand-alone
         # launch average, and what is left (launch + mailbox + host optimiser step per round, prior rebuild, M-step lane)
@@ -602,9 +658,8 @@ def main():
            prof_live["hstep"][1] + prof_live["hstep_lr"][1] + prof_live["hstep_tab"][1],
            ((prof["hstep"][1] + prof["hstep_lr"][1] + prof["hstep_tab"][1]) / (prof["hstep"][0] + prof["hstep_lr"][0]))
            if prof["hstep"][0] + prof["hstep_lr"][0] else 0.0),
-        "effective_rank": ranks_used, "effective_rank_per_step": ranks_per_step, "omega_final": omega,
         "kernel_pass_rank_per_step": k_ranks,  # the ranks the `kernels` / `roofline` timings were taken at
-    }
+    })
     if not args.no_cpu_baseline and world == 1:
         cb = cpu_baseline(args.workload, n_trials if args.cpu_full else min(args.cpu_trials, n_trials))
         out["cpu_baseline"] = cb

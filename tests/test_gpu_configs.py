@@ -392,3 +392,41 @@ def test_c5_full_size_500_ragged_trials(V):
         Tn = tr["y"].shape[0]
         for l in range(L):
             assert np.array_equal(res["params"]["cholesky"][Tn][l], p2["cholesky"][Tn][l]), (Tn, l)
+
+
+# ------------------------------------------------------------------ bench.py: plain line, --dump-outputs, --full
+def test_bench_plain_line_dump_and_full(tmp_path):
+    """A plain bench run prints the headline without the figures that take runs of their own; --dump-outputs writes the
+    last timed step's parameters and posterior (float64, the same from run to run); --full adds the per-kernel pass,
+    the roofline and the CPU baseline."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--workload", "C1"] + list(extra)
+        done = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert done.returncode == 0, done.stderr[-2000:]
+        lines = [ln for ln in done.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    plain = run("--dump-outputs", str(tmp_path / "a"))
+    assert plain["metric"] == "EM iterations/sec" and plain["unit"] == "EM it/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "f64" and plain["steps"] == 2 and len(plain["phase_ms_per_step"]["em"]) == 2
+    assert abs(plain["ms_per_step"] * plain["value"] - 1e3) < 1e-6
+    assert not {"kernels", "roofline", "h_step", "cpu_baseline"} & set(plain)
+    run("--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".npy" for k in ("a", "b", "noise", "omega", "sigma", "mu", "v", "w", "dmu"))
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and x.shape == y.shape and relerr(x, y) < 1e-12, f
+    assert np.load(tmp_path / "a" / "mu.npy").shape == (10 * 200, 3)   # C1: 10 trials x 200 bins, 3 latents
+    assert np.load(tmp_path / "a" / "a.npy").shape == (3, 20)
+    full = run("--full", "--cpu-trials", "2")
+    assert {"kernels", "roofline", "h_step", "cpu_baseline"} <= set(full) and full["steps"] == 2

@@ -301,6 +301,44 @@ def test_bench_refuses_a_world_that_is_not_the_gpus_asked_for():
     assert not [ln for ln in done.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_dump_keeps_segment_order_and_samples_under_64_mb(tmp_path):
+    """bench.py --dump-outputs on a stand-in session: rows follow the segment list (overlapping segments are stored
+    stage-major on the device), and a posterior too large for the budget (C5: 12 860 segments x 10 latents) is written
+    as a fixed sample of its rows, named in posterior_rows; every array float64, under 64 MB in all."""
+    import types
+
+    import bench
+
+    def session(n_seg, T, L, unit_of=None):
+        rng = np.random.default_rng(1)
+        dev = {k: rng.standard_normal((n_seg * T, L)) for k in ("mu", "v", "w", "dmu")}
+        eng = types.SimpleNamespace(L=L, sets={1: (n_seg, n_seg * T, np.arange(n_seg + 1) * T)},
+                                    download=lambda sid, keys: {k: dev[k].copy() for k in keys})
+        segs = type("Segs", (list,), {})(range(n_seg))
+        segs.set_id, segs.unit_of = 1, unit_of
+        params = {"a": np.ones((L, 200)), "b": np.zeros((1, 200)), "noise": np.ones(200), "omega": np.ones(L),
+                  "sigma": np.ones(L)}
+        return types.SimpleNamespace(params=params, eng=eng, segs=segs), dev
+
+    sess, dev = session(6, 50, 3, unit_of=np.array([0, 3, 1, 4, 2, 5]))
+    bench.dump_outputs(sess, str(tmp_path / "small"))
+    mu = np.load(tmp_path / "small" / "mu.npy")
+    assert mu.shape == (300, 3) and np.array_equal(mu[50:100], dev["mu"][150:200])
+    assert not (tmp_path / "small" / "posterior_rows.npy").exists()
+
+    sess, dev = session(12860, 50, 10)
+    bench.dump_outputs(sess, str(tmp_path / "big"))
+    files = sorted((tmp_path / "big").iterdir())
+    assert sum(f.stat().st_size for f in files) < 64e6
+    assert all(np.load(f).dtype == np.float64 for f in files)
+    rows = np.load(tmp_path / "big" / "posterior_rows.npy").astype(np.int64)
+    assert len(rows) > 100000 and np.all(np.diff(rows) > 0)
+    for k in ("mu", "v", "w", "dmu"):
+        assert np.array_equal(np.load(tmp_path / "big" / (k + ".npy")), dev[k][rows])
+    bench.dump_outputs(sess, str(tmp_path / "again"))
+    assert np.array_equal(np.load(tmp_path / "again" / "posterior_rows.npy"), rows.astype(np.float64))
+
+
 def test_initial_prior_behaves_like_the_dict_it_stands_for():
     """engine._InitialPrior (params["initial"]["cholesky"] of a fit without a window): get() answers for a length
     `in` reports, a deep copy stays lazy, and a pickle is a plain {T: ndarray} dict with no vlgp_amd class in it."""

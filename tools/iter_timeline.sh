@@ -3,7 +3,7 @@
 # (rocprofv3 --kernel-trace; the tracer stretches concurrent launches, the serial seams are what to read here)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/iter_tl; rm -rf $O; mkdir -p $O; cd $R
-rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python bench.py --steps 8 --warmup 6 --no-cpu-baseline > $O/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python bench.py --full --steps 8 --warmup 6 --no-cpu-baseline > $O/log.txt 2>&1
 T=$(find $O/tr -name "*kernel_trace.csv" | head -1)
 python - "$T" <<'PY'
 import csv, sys

@@ -67,7 +67,7 @@ if __name__=="__main__":
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     g=np.load(os.path.join(ROOT, 'tests/golden/hstep.npz'))
     mu=g['mu']; w=g['w']; print(mu.shape, w.shape, g['logp'])
-    c3=np.load('/root/repo/tests/golden/vem_c3.npz')
+    c3=np.load(os.path.join(ROOT, 'tests/golden/vem_c3.npz'))
     W=c3['seg_w']; print('c3 seg_w', W.shape, W.min(), W.max(), np.median(W))
     T=50; t=np.arange(T,dtype=float); eps=1e-4
     rng=np.random.default_rng(0)
