@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define VLGP_ABI_VERSION 1
+#define VLGP_ABI_VERSION 2
 #define VLGP_MAX_SETS 4
 #define VLGP_MAX_L 64             /* latents per handle.  The reference has no bound (vlgp/core.py:76,106; gp.py:82);
                                      up to 10 the specialised kernels run, up to 16 the register-resident generic
@@ -111,6 +111,27 @@ int vlgp_stash_mu(vlgp_ctx* ctx, int set, int restore);
 int vlgp_download_units(vlgp_ctx* ctx, int set, double* mu, double* v, double* w,
                         double* dmu);
 int vlgp_free_units(vlgp_ctx* ctx, int set);
+
+/* ---- held-out evaluation ---------------------------------------------- */
+/* Leave-one-neuron-out replicas (no counterpart in the reference, whose evaluation.loglik is broken).  Set `dst` becomes
+ * n_rep replicas of set `src`, replica-major (unit k M_src + m is unit m of replica k), replica k leaving channel
+ * channel[k] out of its E-step: vlgp_estep on `dst` runs what it would run with a[:, channel[k]] = 0 for replica k,
+ * bit for bit.  y and x (and x.b) are ALIASED to `src`; mu, v, w, dmu start as copies of src's.  `src` must be a plain
+ * uploaded set (not a cut, no overlap stages).  While a replica set exists, vlgp_upload_units and vlgp_free_units on
+ * `src` return VLGP_ERR_STATE.  A replicated set takes vlgp_estep (split E-step only: a configuration that kernel
+ * family cannot run -- L > 10, N > 1024, long units at R above its limit, short units at effective rank > 32 -- is
+ * VLGP_ERR_STATE, never another kernel), vlgp_download_units, vlgp_free_units and vlgp_loglik; every other entry point
+ * refuses it with VLGP_ERR_STATE. */
+int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel);
+/* Plug-in rate and log-likelihood of the observations under the set's current posterior (mu, v):
+ *   Poisson   rate = trunc_exp(a_n.mu_t + (b x)_tn + 1/2 (a_n^2).v_t)  (the E-step's rate; vb == 0 drops the v term)
+ *             ll = y log rate - rate - lgamma(y + 1);   sums[n] = {sum ll, sum y, sum rate, sum lgamma(y + 1)}
+ *   Gaussian  rate = eta = a_n.mu_t + (b x)_tn
+ *             ll = -log(2 pi noise_n) / 2 - (y - eta)^2 / (2 noise_n);   sums[n] = {sum ll, sum y, sum eta, sum y^2}
+ * Plain set: rate (rows, N) row-major or NULL, sums (N, 4), channels in plain order.  Replicated set: only replica k's
+ * own held-out channel, on the source rows: rate (rows_src, n_rep) or NULL, sums (n_rep, 4).  Sums cover this handle's
+ * units only (no reduction over ranks) and are bitwise reproducible (fixed-order two-stage reduction, no atomics). */
+int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

@@ -1,0 +1,239 @@
+"""Held-out evaluation on the device (vlgp_loglik, vlgp_replicate_units, vlgp_amd.evaluation) against a NumPy
+restatement: the oracle's E-step with a[:, n] = 0 from a zero start, then channel n's plug-in rate with its own
+loading, scored with the definitions of vlgp_amd/evaluation.py."""
+import math
+
+import numpy as np
+import pytest
+from scipy.special import gammaln
+
+from conftest import relerr
+from oracle import vlgp_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+STAGE = 1e-9
+
+
+@pytest.fixture(scope="module")
+def V():
+    import vlgp_amd
+
+    return vlgp_amd
+
+
+def _lagged(y, history):
+    """x (T, 1 + history, N): a column of ones, then each channel's own counts 1 ... history bins back."""
+    T, N = y.shape
+    x = np.ones((T, 1 + history, N))
+    for h in range(1, history + 1):
+        x[h:, h, :] = y[:-h]
+        x[:h, h, :] = 0.0
+    return x
+
+
+def _problem(seed=3, M=6, T=150, N=14, L=3, n_gauss=0, lengths=None, history=0, method="VB", max_iter=4):
+    from vlgp_amd import synth
+
+    trials = synth.make_trials(M, T, N, min(L, 3), seed=seed, n_gauss=n_gauss, lengths=lengths)
+    rng = np.random.default_rng(seed)
+    for tr in trials:
+        tr["x"] = _lagged(tr["y"], history)
+    P = 1 + history
+    y = np.concatenate([tr["y"] for tr in trials])
+    b = np.zeros((P, N))
+    b[0] = np.log(np.maximum(y.mean(0), 1e-3))
+    b[0, N - n_gauss:] = y[:, N - n_gauss:].mean(0) if n_gauss else b[0, N - n_gauss:]
+    if history:
+        b[1:] = -0.05 * rng.random((history, N))
+    a = 0.3 * rng.standard_normal((L, N))
+    if L > 10:  # (as test_gpu_parity's problems: eta = mu a in the range of the few-latent cases -- the E-step's Newton
+        a *= 5.0 / L  # sweeps amplify rounding once rates grow, and the stage tolerance is about arithmetic, not conditioning)
+    lik = np.array(["poisson"] * (N - n_gauss) + ["gaussian"] * n_gauss)
+    noise = np.ones(N)
+    noise[N - n_gauss:] = 0.5 + rng.random(n_gauss)
+    omega = np.linspace(2e-2, 1e-3, L)
+    params = {"ydim": N, "zdim": L, "xdim": P, "a": a, "b": b, "noise": noise, "omega": omega,
+              "sigma": np.ones(L), "rank": 50, "likelihood": lik}
+    from vlgp_amd import get_config
+
+    config = get_config(max_iter=max_iter, method=method)
+    return trials, params, config
+
+
+def _rate_ll(y, x, mu, v, a, b, noise, gauss, vb):
+    """Plug-in rate (Gaussian: eta) and log-likelihood, (T, N) each."""
+    eta = O.linear_predictor(x, mu, a, b)
+    lam = np.exp(np.minimum(eta + (0.5 * (v @ a ** 2) if vb else 0.0), 10.0))
+    rate = np.where(gauss, eta, lam)
+    llp = y * np.log(lam) - lam - gammaln(y + 1.0)
+    llg = -0.5 * np.log(2 * np.pi * noise) - (y - eta) ** 2 / (2 * noise)
+    return rate, np.where(gauss, llg, llp)
+
+
+def _restated_loo(trials, params, config, channels, n_iter=None):
+    a, b, noise = params["a"], params["b"], params["noise"]
+    L = params["zdim"]
+    gauss = np.asarray(params["likelihood"]) == "gaussian"
+    vb = config["method"] == "VB"
+    n_iter = config["max_iter"] if n_iter is None else n_iter
+    rates, lls = [], np.zeros(len(channels))
+    for tr in trials:
+        T = tr["y"].shape[0]
+        G = O.build_prior([T], params["omega"], params["sigma"], 50)[T]
+        cols = []
+        for i, n in enumerate(channels):
+            a0 = a.copy()
+            a0[:, n] = 0.0
+            z = np.zeros((T, L))
+            mu, v, _, _, _ = O.estep_unit(tr["y"], tr["x"], z, z, z, a0, b, noise, gauss, G, n_iter,
+                                          config["dmu_bound"], vb)
+            r, ll = _rate_ll(tr["y"], tr["x"], mu, v, a, b, noise, gauss, vb)
+            cols.append(r[:, n])
+            lls[i] += ll[:, n].sum()
+        rates.append(np.stack(cols, axis=1))
+    return rates, lls
+
+
+@pytest.mark.parametrize("case", ["poisson", "mixed", "history"])
+def test_loglik_matches_restatement(V, case):
+    kw = {"poisson": {}, "mixed": {"n_gauss": 3}, "history": {"history": 2}}[case]
+    trials, params, config = _problem(seed=5, **kw)
+    rng = np.random.default_rng(1)
+    L, N = params["zdim"], params["ydim"]
+    for tr in trials:
+        T = tr["y"].shape[0]
+        tr["mu"] = 0.3 * rng.standard_normal((T, L))
+        tr["v"] = 0.1 * rng.random((T, L))
+    gauss = np.asarray(params["likelihood"]) == "gaussian"
+    per = V.evaluation.loglik({"trials": trials, "params": params, "config": config}, per_channel=True)
+    want = np.zeros(N)
+    rates = []
+    for tr in trials:
+        r, ll = _rate_ll(tr["y"], tr["x"], tr["mu"], tr["v"], params["a"], params["b"], params["noise"], gauss, True)
+        want += ll.sum(0)
+        rates.append(r)
+    assert relerr(per, want) < 1e-12
+    total = V.evaluation.loglik({"trials": trials, "params": params, "config": config})
+    assert total == pytest.approx(want.sum(), rel=1e-12)
+    # the rates themselves, through the engine
+    from vlgp_amd.engine import Engine
+
+    with Engine(N, L, params["xdim"], 50, gauss) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(0, [{"y": t["y"], "x": t["x"], "mu": t["mu"], "v": t["v"], "w": None} for t in trials])
+        sums, rate = eng.loglik(0, vb=True, want_rate=True)
+    assert relerr(rate, np.concatenate(rates)) < 1e-12
+    assert np.array_equal(sums[:, 0], per)
+
+
+@pytest.mark.parametrize("case", ["mixed", "ragged", "short", "map", "subset"])
+def test_leave_one_out_matches_restatement(V, case):
+    kw, channels = {}, None
+    if case == "mixed":
+        kw = {"n_gauss": 3}
+    elif case == "ragged":
+        kw = {"lengths": [150, 120, 150, 120, 150, 120]}
+    elif case == "short":
+        kw = {"T": 50}
+    elif case == "map":
+        kw = {"method": "MAP"}
+    elif case == "subset":
+        channels = [9, 2, 13]
+    trials, params, config = _problem(seed=11, **kw)
+    got = V.evaluation.leave_one_out(trials, params, config, channels=channels)
+    chans = list(range(params["ydim"])) if channels is None else channels
+    assert got["channels"] == chans and got["path"] == "batched" and got["n_failed"] == 0
+    want_rate, want_ll = _restated_loo(trials, params, config, chans)
+    for g, w in zip(got["rate"], want_rate):
+        assert g.shape == w.shape
+        assert relerr(g, w) < STAGE
+    assert relerr(got["ll"], want_ll) < STAGE
+    gauss = (np.asarray(params["likelihood"]) == "gaussian")[chans]
+    assert np.all(np.isnan(got["bits_per_spike"][gauss]))
+    assert np.all(np.isfinite(got["bits_per_spike"][~gauss]))
+
+
+@pytest.mark.parametrize("shape", ["long", "short"])
+def test_batched_equals_sequential_bit_for_bit(V, monkeypatch, shape):
+    if shape == "long":
+        monkeypatch.setenv("VLGP_ESTEP_LSPLIT", "1")
+        trials, params, config = _problem(seed=13, n_gauss=2)
+    else:
+        monkeypatch.setenv("VLGP_ESTEP_SPLIT", "1")
+        trials, params, config = _problem(seed=13, T=50, n_gauss=2)
+    ev = V.evaluation
+    base = ev.leave_one_out(trials, params, config, path="batched")
+    seq = ev.leave_one_out(trials, params, config, path="sequential")
+    assert base["path"] == "batched" and seq["path"] == "sequential"
+    for key in ("ll", "n_spikes"):
+        assert np.array_equal(base[key], seq[key]), key
+    assert all(np.array_equal(g, w) for g, w in zip(base["rate"], seq["rate"]))
+    for cap in (1, 3):
+        other = ev.leave_one_out(trials, params, config, path="batched", max_replicas=cap)
+        assert np.array_equal(other["ll"], base["ll"])
+        assert all(np.array_equal(g, w) for g, w in zip(other["rate"], base["rate"]))
+    again = ev.leave_one_out(trials, params, config, path="batched")
+    assert np.array_equal(again["ll"], base["ll"])
+    assert all(np.array_equal(g, w) for g, w in zip(again["rate"], base["rate"]))
+
+
+def test_zero_loading_channel_reproduces_transform_from_zero(V):
+    trials, params, config = _problem(seed=17)
+    n = 4
+    params["a"][:, n] = 0.0
+    got = V.evaluation.leave_one_out(trials, params, config, channels=[n, 7])
+    gauss = np.asarray(params["likelihood"]) == "gaussian"
+    for tr, g in zip(trials, got["rate"]):
+        T = tr["y"].shape[0]
+        G = O.build_prior([T], params["omega"], params["sigma"], 50)[T]
+        z = np.zeros((T, params["zdim"]))
+        mu, v, _, _, _ = O.estep_unit(tr["y"], tr["x"], z, z, z, params["a"], params["b"], params["noise"], gauss, G,
+                                      config["max_iter"], config["dmu_bound"], True)
+        r, _ = _rate_ll(tr["y"], tr["x"], mu, v, params["a"], params["b"], params["noise"], gauss, True)
+        assert relerr(g[:, 0], r[:, n]) < STAGE
+
+
+def test_many_latents_take_the_sequential_path(V):
+    trials, params, config = _problem(seed=19, M=3, T=80, N=8, L=12, max_iter=3)
+    got = V.evaluation.leave_one_out(trials, params, config, channels=[0, 5])
+    assert got["path"] == "sequential"
+    want_rate, want_ll = _restated_loo(trials, params, config, [0, 5])
+    for g, w in zip(got["rate"], want_rate):
+        assert relerr(g, w) < STAGE
+    assert relerr(got["ll"], want_ll) < STAGE
+    with pytest.raises(V.VlgpError):
+        V.evaluation.leave_one_out(trials, params, config, channels=[0], path="batched")
+
+
+def test_replicated_set_refuses_other_entry_points(V):
+    from vlgp_amd.api import bind_priors
+    from vlgp_amd.engine import Engine
+
+    trials, params, config = _problem(seed=23, M=4, T=100, N=10)
+    L, N = params["zdim"], params["ydim"]
+    units = [{"y": t["y"], "x": None, "mu": np.zeros((t["y"].shape[0], L)), "v": None, "w": None} for t in trials]
+    with Engine(N, L, 1, 50) as eng:
+        eng.set_params(params["a"], params["b"][:1], params["noise"])
+        eng.upload(0, units)
+        bind_priors(eng, trials, dict(params))
+        eng.replicate(0, 2, [1, 3, 5])
+        with pytest.raises(V.VlgpError, match="replicated"):
+            eng.mstep(2, 2)
+        with pytest.raises(V.VlgpError, match="replicated"):
+            eng.update_w(2)
+        with pytest.raises(V.VlgpError, match="replicated"):
+            eng.hstep_objective(2, 100, 1.0, [0], np.log(np.array([[1.0, 1e-2, 1e-4]])))
+        with pytest.raises(V.VlgpError, match="replicated"):
+            eng.norms(2)
+        with pytest.raises(V.VlgpError, match="source of a replicated set"):
+            eng.free_units(0)
+        with pytest.raises(V.VlgpError, match="source of a replicated set"):
+            eng.upload(0, units)
+        eng.estep(2, 2)
+        got = eng.download(2, ("mu",))["mu"]
+        assert got.shape == (3 * sum(t["y"].shape[0] for t in trials), L)
+        sums, rate = eng.loglik(2, want_rate=True)
+        assert sums.shape == (3, 4) and rate.shape == (got.shape[0] // 3, 3)
+        eng.free_units(2)
+        eng.free_units(0)

@@ -6,5 +6,6 @@ from .util import load, save  # noqa: F401
 from .engine import (DeviceTrials, Engine, VlgpError, constrain_latent, constrain_loading,  # noqa: F401
                      estep, hstep, infer, make_cholesky, mstep, update_v, update_w, vem)
 from .preprocess import get_config, get_params  # noqa: F401
+from . import evaluation  # noqa: F401,E402
 
-__all__ = ["fit", "transform", "Engine", "DeviceTrials", "VlgpError"]
+__all__ = ["fit", "transform", "Engine", "DeviceTrials", "VlgpError", "evaluation"]

@@ -15,7 +15,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlgp_hip.so")
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 MAX_SETS = 4
 UNIQUE_ID_BYTES = 128
 PROF_ESTEP, PROF_MSTEP, PROF_HSTEP, PROF_PRIOR = 0, 1, 2, 3
@@ -52,6 +52,8 @@ _SIGNATURES = {
     "vlgp_download_units": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp]),
     "vlgp_stash_mu": (C.c_int, [_h, C.c_int, C.c_int]),
     "vlgp_free_units": (C.c_int, [_h, C.c_int]),
+    "vlgp_replicate_units": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip]),
+    "vlgp_loglik": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
     "vlgp_set_params": (C.c_int, [_h, _dp, _dp, _dp]),
     "vlgp_get_params": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp]),
     "vlgp_build_prior": (C.c_int, [_h, C.c_int, _ip, _dp, _dp]),

@@ -14,7 +14,7 @@ from . import engine as E
 from .preprocess import fill_params, fill_trials, get_config, get_params, initialize
 from .util import segment_starts
 
-__all__ = ["fit", "transform", "FitSession"]
+__all__ = ["fit", "transform", "FitSession", "bind_priors"]
 
 logger = logging.getLogger(__name__)
 
@@ -227,6 +227,22 @@ def fit(trials, n_factors, device=0, comm=None, verbose=True, **kwargs):
     return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, **kwargs).run().finish()
 
 
+def bind_priors(eng, trials, params):
+    """Give the engine a prior factor for every trial length: ``params["cholesky"]``'s where it has one, the
+    rest built on the device (and added to ``params["cholesky"]``, a new dict)."""
+    chol = dict(params.get("cholesky") or {})
+    lengths = sorted({int(tr["y"].shape[0]) for tr in trials})
+    missing = [T for T in lengths if T not in chol]
+    have = [T for T in lengths if T in chol]
+    if missing:
+        eng.build_prior(missing, params["omega"], params["sigma"])
+        for T in missing:
+            chol[T] = eng.get_prior(T)
+    for T in have:
+        eng.set_prior(T, chol[T])
+    params["cholesky"] = chol
+
+
 def transform(trials, params, config, device=0):
     """Infer latents of new trials with fitted parameters (vlgp/api.py:171-184).
 
@@ -239,17 +255,7 @@ def transform(trials, params, config, device=0):
         eng.set_params(params["a"], params["b"], params["noise"])
         eng.upload(SET_TRIALS, trials)
         dev = E.DeviceTrials(trials, eng, SET_TRIALS)
-        chol = dict(params.get("cholesky") or {})
-        lengths = sorted({int(tr["y"].shape[0]) for tr in trials})
-        missing = [T for T in lengths if T not in chol]
-        have = [T for T in lengths if T in chol]
-        if missing:
-            eng.build_prior(missing, params["omega"], params["sigma"])
-            for T in missing:
-                chol[T] = eng.get_prior(T)
-        for T in have:
-            eng.set_prior(T, chol[T])
-        params["cholesky"] = chol
+        bind_priors(eng, trials, params)
         E.infer(dev, params, config)
         dev.pull()
     return trials

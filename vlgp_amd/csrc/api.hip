@@ -116,6 +116,15 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     return us;
 }
 
+// a replicated set (vlgp_replicate_units) takes the E-step, downloads, vlgp_loglik and vlgp_free_units; everything else
+// would read its aliased y / x with the replicas' row count, or mix the replicas' excluded channels back in
+#define NOT_REPLICATED(ctx, us, what)                                                                                \
+    do {                                                                                                             \
+        if ((us)->rep_src >= 0)                                                                                      \
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "%s refuses a replicated set (leave-one-out replicas of set %d: "    \
+                             "E-step, download, loglik and free only)", what, (us)->rep_src);                        \
+    } while (0)
+
 // ---- profiling -----------------------------------------------------------
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st) {
     if (!ctx->prof_on) return;
@@ -481,7 +490,13 @@ static void free_set(vlgp_ctx* ctx, UnitSet& us) {
     if (!us.valid) return;
     (void)hipStreamSynchronize(ctx->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
-    if (!us.alias) { fr(us.y); fr(us.x); fr(us.mu); fr(us.v); fr(us.w); }
+    if (us.rep_src >= 0) {  // replicas: y, x, xb are the source's
+        fr(us.mu); fr(us.v); fr(us.w); fr(us.d_rep_ch); fr(us.d_rep_wconst); fr(us.d_rep_xa);
+        ctx->sets[us.rep_src].rep_users--;
+        us.d_xb = nullptr;
+    } else if (!us.alias) {
+        fr(us.y); fr(us.x); fr(us.mu); fr(us.v); fr(us.w);
+    }
     fr(us.dmu); fr(us.d_off); fr(us.d_src_start); fr(us.d_unit_prior); fr(us.d_xb); fr(us.d_scratch); fr(us.d_mu_stash);
     fr(us.d_links);
     us = UnitSet();
@@ -665,6 +680,8 @@ extern "C" int vlgp_upload_units(vlgp_ctx* ctx, int set, int M, const int64_t* o
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, false);
     if (!us) return VLGP_ERR_ARG;
+    if (us->rep_users > 0)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", set);
     if (M < 1 || !offsets || !y) return vlgp_fail(ctx, VLGP_ERR_ARG, "upload needs M >= 1, offsets and y");
     if (offsets[0] != 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "offsets[0] must be 0");
     if (!x && ctx->P != 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "x == NULL (all ones) requires xdim == 1");
@@ -695,6 +712,9 @@ extern "C" int vlgp_cut_units(vlgp_ctx* ctx, int src, int dst, int M_dst, const 
     if (!s || !d) return VLGP_ERR_ARG;
     if (src == dst || M_dst < 1 || window < 1 || !start) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad cut arguments");
     if (s->alias) return vlgp_fail(ctx, VLGP_ERR_STATE, "cannot cut a set that is itself a cut");
+    NOT_REPLICATED(ctx, s, "vlgp_cut_units");
+    if (d->rep_users > 0)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", dst);
     bool exact = (int64_t)M_dst * window == s->rows;
     for (int k = 0; k < M_dst; ++k) {
         if (start[k] < 0 || start[k] + window > s->rows)
@@ -735,6 +755,7 @@ extern "C" int vlgp_merge_units(vlgp_ctx* ctx, int cut_set) {
     CHK(vlgp_join_m(ctx));
     UnitSet* c = vlgp_get_set(ctx, cut_set, true);
     if (!c) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, c, "vlgp_merge_units");
     if (c->parent < 0) return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is not a cut", cut_set);
     if (c->alias) return VLGP_OK;
     UnitSet* p = vlgp_get_set(ctx, c->parent, true);
@@ -747,6 +768,7 @@ extern "C" int vlgp_stash_mu(vlgp_ctx* ctx, int set, int restore) {
     CHK(vlgp_join_m(ctx));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_stash_mu");
     const size_t nb = (size_t)us->rows * ctx->L * sizeof(double);
     if (!restore) {
         if (!us->d_mu_stash) HIPCHK(ctx, hipMalloc(&us->d_mu_stash, nb));
@@ -779,10 +801,103 @@ extern "C" int vlgp_free_units(vlgp_ctx* ctx, int set) {
     CHK(vlgp_join_m(ctx));
     UnitSet* us = vlgp_get_set(ctx, set, false);
     if (!us) return VLGP_ERR_ARG;
+    if (us->rep_users > 0)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", set);
     for (auto& other : ctx->sets)
         if (other.valid && other.alias && other.parent == set) free_set(ctx, other);
     free_set(ctx, *us);
     return VLGP_OK;
+}
+
+// ---- leave-one-out replicas and held-out likelihood ---------------------------
+extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel) {
+    NEED_CTX(ctx);
+    ctx->hmom_us = nullptr;
+    CHK(vlgp_join_m(ctx));
+    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    UnitSet* s = vlgp_get_set(ctx, src, true);
+    UnitSet* d = vlgp_get_set(ctx, dst, false);
+    if (!s || !d) return VLGP_ERR_ARG;
+    if (src == dst || n_rep < 1 || !channel) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad replicate arguments");
+    for (int k = 0; k < n_rep; ++k)
+        if (channel[k] < 0 || channel[k] >= ctx->N)
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "replica %d leaves out channel %d, outside [0, %d)", k, channel[k], ctx->N);
+    if (s->rep_src >= 0 || s->parent >= 0 || s->alias || !s->stage_start.empty())
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)", src);
+    if (d->rep_users > 0)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", dst);
+    if ((int64_t)n_rep * s->M > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "too many replicated units");
+    for (auto& other : ctx->sets)
+        if (other.valid && other.alias && other.parent == dst) free_set(ctx, other);
+    free_set(ctx, *d);
+    const int Ms = s->M, L = ctx->L;
+    const int64_t rs = s->rows;
+    std::vector<int64_t> off((size_t)n_rep * Ms + 1);
+    for (int k = 0; k < n_rep; ++k)
+        for (int m = 0; m < Ms; ++m) off[(size_t)k * Ms + m] = k * rs + s->off[m];
+    off[(size_t)n_rep * Ms] = n_rep * rs;
+    CHK(set_offsets(ctx, *d, n_rep * Ms, off.data()));
+    d->rep_src = src;
+    d->n_rep = n_rep;
+    d->rows_src = rs;
+    d->rep_ch.assign(channel, channel + n_rep);
+    d->x_ones = s->x_ones;
+    d->y = s->y;  // aliased: a copy per replica would be rows x N doubles each
+    d->x = s->x;
+    s->rep_users++;
+    d->valid = true;  // (from here on free_set releases whatever was allocated, should a step below fail)
+    const size_t nb = (size_t)rs * L * sizeof(double);
+    CHK(dev_alloc(ctx, &d->mu, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, &d->v, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, &d->w, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, &d->dmu, n_rep * rs * L, false));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_ch, sizeof(int) * n_rep));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * 16 * n_rep));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_xa, sizeof(d->rep_xh)));
+    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_ch, channel, sizeof(int) * n_rep, hipMemcpyHostToDevice, ctx->stream));
+    for (int k = 0; k < n_rep; ++k) {
+        const int64_t o = k * rs * L;
+        HIPCHK(ctx, hipMemcpyAsync(d->mu + o, s->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->v + o, s->v, nb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->w + o, s->w, nb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->dmu + o, s->dmu, nb, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the channel list is the caller's again)
+    d->valid = true;
+    return VLGP_OK;
+}
+
+extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums) {
+    NEED_CTX(ctx);
+    CHK(vlgp_join_m(ctx));
+    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
+    UnitSet* us = vlgp_get_set(ctx, set, true);
+    if (!us) return VLGP_ERR_ARG;
+    if (!sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik needs sums");
+    if (us->parent >= 0 && !us->alias)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on a copied cut: merge it and score the source set");
+    const bool rep = us->rep_src >= 0;
+    UnitSet& rows_of = rep ? ctx->sets[us->rep_src] : *us;  // the y / x rows
+    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
+    const int slots = rep ? us->n_rep : ctx->N;
+    const int64_t n_rate = rep ? us->rows_src * us->n_rep : us->rows * ctx->N;
+    const int64_t o_sums = rate ? n_rate : 0;
+    double* d_rate = nullptr;
+    double* d_out = nullptr;
+    HIPCHK(ctx, hipMalloc(&d_out, sizeof(double) * (size_t)(o_sums + 4 * (int64_t)slots)));
+    if (rate) d_rate = d_out;
+    int rc = launch_loglik(ctx, *us, vb, d_rate, d_out + o_sums);
+    if (rc == VLGP_OK) {
+        hipError_t e = hipMemcpyAsync(sums, d_out + o_sums, sizeof(double) * 4 * slots, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && rate)
+            e = hipMemcpyAsync(rate, d_rate, sizeof(double) * (size_t)n_rate, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_loglik copy-out failed: %s", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_out);
+    return rc;
 }
 
 // ---- parameters ------------------------------------------------------------
@@ -1034,6 +1149,7 @@ extern "C" int vlgp_update_w(vlgp_ctx* ctx, int set) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_update_w");
     return launch_estep(ctx, *us, EM_W, 0, 0.0, 0);
 }
 
@@ -1045,6 +1161,7 @@ extern "C" int vlgp_update_v(vlgp_ctx* ctx, int set, int vb, int* n_failed) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_update_v");
     if (n_failed) *n_failed = 0;
     if (!vb) return VLGP_OK;
     CHK(begin_count(ctx));
@@ -1115,6 +1232,7 @@ extern "C" int vlgp_set_overlaps(vlgp_ctx* ctx, int set, int n_stages, const int
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_set_overlaps");
     if (us->alias || us->Tmin != us->Tmax)
         return vlgp_fail(ctx, VLGP_ERR_STATE, "overlaps belong to a copied cut of equal-length units");
     if (n_stages < 1 || !stage_start || stage_start[0] != 0 || stage_start[n_stages] != us->M || n_links < 0 ||
@@ -1158,6 +1276,7 @@ extern "C" int vlgp_unshare_mu(vlgp_ctx* ctx, int set) {
     NEED_CTX(ctx);
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_unshare_mu");
     us->share_mu = false;
     return VLGP_OK;
 }
@@ -1170,6 +1289,7 @@ extern "C" int vlgp_mstep_begin(vlgp_ctx* ctx, int set, int n_iter, int use_hess
     if (ctx->m_pending) return vlgp_fail(ctx, VLGP_ERR_STATE, "an M-step is already in flight (call vlgp_mstep_end)");
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_mstep_begin");
     if (!(da_bound > 0) || !(db_bound > 0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "da_bound/db_bound must be positive");
     // fork: the M-step lane starts after everything already queued on the main stream
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -1233,6 +1353,7 @@ extern "C" int vlgp_hstep_objective(vlgp_ctx* ctx, int set, int window, double d
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_hstep_objective");
     if (n_eval < 1 || !latent || !logp || !ll || !dll) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad hstep arguments");
     return launch_hstep(ctx, *us, window, dt, n_eval, latent, logp, ll, dll);
 }
@@ -1242,6 +1363,7 @@ extern "C" int vlgp_hstep_prepare(vlgp_ctx* ctx, int set, int window) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_hstep_prepare");
     ctx->hprep = false;
     if (ctx->hmom_bracket || window < 1) return VLGP_OK;
     // On the MAIN stream, behind everything queued so far -- the call may come while the E-step still runs (the host
@@ -1258,6 +1380,7 @@ extern "C" int vlgp_hstep_begin(vlgp_ctx* ctx, int set, int window) {
     NEED_CTX(ctx);
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_hstep_begin");
     ctx->hmom_bracket = true;
     // the first objective call inside the bracket builds the moments and the w copy -- unless vlgp_hstep_prepare did,
     // for this set and window, and no entry point that may change the units ran since
@@ -1290,6 +1413,7 @@ extern "C" int vlgp_apply_latent_map(vlgp_ctx* ctx, int set, const double* map, 
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us || !map) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad latent map arguments");
+    NOT_REPLICATED(ctx, us, "vlgp_apply_latent_map");
     const int L = ctx->L;
     // staged through a pinned and a device buffer of its own, reused after the event behind the last kernel that read
     // them: nothing waits here (this is the first call of every EM iteration, constrain_loading)
@@ -1331,6 +1455,7 @@ extern "C" int vlgp_norms(vlgp_ctx* ctx, int set, double out[2]) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_norms");
     if (ctx->world == 1) {  // one rank: the kernel of the two-halves form (the same sums, bit for bit)
         CHK(vlgp_norms_begin(ctx, set));
         return vlgp_norms_end(ctx, out);
@@ -1350,6 +1475,7 @@ extern "C" int vlgp_norms_begin(vlgp_ctx* ctx, int set) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_norms_begin");
     CHK(wait_norms(ctx));  // (a pass never collected: dropped)
     ctx->x_pending = 0;
     ctx->x_set = set;
@@ -1389,6 +1515,7 @@ extern "C" int vlgp_latent_moments(vlgp_ctx* ctx, int set, double* sum1, double*
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_latent_moments");
     std::vector<double> m;
     CHK(moments_host(ctx, *us, m));
     const int L = ctx->L, t = L * (L + 1) / 2;
@@ -1417,6 +1544,7 @@ extern "C" int vlgp_project_units(vlgp_ctx* ctx, int set, const double* proj, co
     CHK(vlgp_join_m(ctx));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_project_units");
     if (!proj || !shift) return vlgp_fail(ctx, VLGP_ERR_ARG, "null projection");
     if (us->alias) return vlgp_fail(ctx, VLGP_ERR_STATE, "project the owning set, not an aliased cut");
     const int N = ctx->N, L = ctx->L;

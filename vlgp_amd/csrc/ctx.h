@@ -54,6 +54,18 @@ struct UnitSet {
     int* d_links = nullptr;         // (n_links, 3): first unit, second unit, shared rows
     int n_links = 0;
     bool share_mu = true;           // false once the segments' mu was rebound (constrain_loading "svd")
+    // Replicated set (vlgp_replicate_units): n_rep copies of set rep_src's units, replica-major (unit k M_src + m), replica
+    // k leaving channel rep_ch[k] out of its E-step.  y and xb are the source's (aliased, never freed here); mu, v, w, dmu
+    // are the replicas' own.  The source counts the replica sets that alias it (rep_users) and refuses re-upload / free.
+    int rep_src = -1;
+    int n_rep = 0;
+    int64_t rows_src = 0;
+    std::vector<int> rep_ch;
+    int* d_rep_ch = nullptr;          // (n_rep)
+    double* d_rep_wconst = nullptr;   // (n_rep, 16): Gaussian constant of w per replica (estep_split.hip)
+    void* d_rep_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
+    double rep_xh[8] = {};
+    int rep_users = 0;
 };
 
 // Debug / test switches of the H-step dispatch (environment VLGP_HSTEP_*, VLGP_DEBUG_OCC), read ONCE when the handle is
@@ -258,4 +270,7 @@ int launch_moments(vlgp_ctx* ctx, UnitSet& us);  // tri(L) gram | sum mu | sum v
 int launch_project(vlgp_ctx* ctx, UnitSet& us, const double* d_proj, const double* d_shift, double* d_part,
                    double* d_out);  // mu = y proj - shift; d_out = column sums of y
 int launch_gather(vlgp_ctx* ctx, UnitSet& src, UnitSet& dst, int window);
+// plug-in rates and per-channel log-likelihood sums of a set (evaluate.hip): d_rate (rows, N) for a plain set, (rows_src,
+// n_rep) for a replicated one, or null; d_sums (slots, 4) with slots = N or n_rep, written in a fixed order
+int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);

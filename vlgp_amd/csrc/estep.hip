@@ -427,7 +427,13 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     const int N = ctx->N, L = ctx->L;
     const bool need_prior = (mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
     if (need_prior) CHK(vlgp_bind_priors(ctx, us));
-    if (!us.x_ones) CHK(vlgp_refresh_xb(ctx, us));
+    if (us.rep_src >= 0) {  // replicated set: x.b of the source rows, the split E-step or an error (never another family)
+        UnitSet& src = ctx->sets[us.rep_src];
+        if (!src.x_ones) CHK(vlgp_refresh_xb(ctx, src));
+        us.d_xb = src.d_xb;
+    } else if (!us.x_ones) {
+        CHK(vlgp_refresh_xb(ctx, us));
+    }
 
     // LDS demand over the priors this set uses
     int64_t gsz = 0, lcsz = 0;
@@ -469,6 +475,8 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
         int handled = 0;
         CHK(launch_estep_split(ctx, us, A, &handled));
         if (handled) { ctx->last_estep_path = handled == 2 ? VLGP_PATH_ESTEP_LSPLIT : (handled == 3 ? VLGP_PATH_ESTEP_SPLIT_MIXED : VLGP_PATH_ESTEP_SPLIT); return VLGP_OK; }
+        if (us.rep_src >= 0)
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: only the split E-step leaves a channel out, and it declined");
     }
 
     // FAST: register-resident factorisations (estep_fast.hip); declines when it does not apply

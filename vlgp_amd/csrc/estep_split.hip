@@ -21,6 +21,7 @@
 //                       Each wave takes the code path of ITS latent's rank: one latent above 16 no longer moves
 //                       the whole launch to the slow instantiation.
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -35,6 +36,7 @@ namespace {
 enum { SP_YA = 0, SP_RES = 1, SP_W = 2 };
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
+struct ExclArgs;
 struct SplitArgs {
     int N, L, M;
     int64_t rows;
@@ -53,7 +55,10 @@ struct SplitArgs {
                          // launch's raw step target G (I + H)^-1 G's: the curvature pass that follows applies
                          // mu += clip(dl - mu) for the latents in `dmask` (estep_lane.h)
     unsigned dmask;
-    double* xg;        // (M L, pkg): packed X = chol(I + G'WG)^-1 per (unit, latent)
+    union {
+        double* xg;              // (M L, pkg): packed X = chol(I + G'WG)^-1 per (unit, latent)
+        const ExclArgs* excl;    // EXCL row passes (which never read xg): the replica table, in device memory
+    };
     unsigned long long* clk;  // debug: per-phase cycle counters of the first wave of the lane-per-task launches, or null
     int prio, clk_kind;    // lane-per-task launches: s_setprio level of their waves; warm the scalar cache with G first
     double* xl;        // lane-per-task launches (estep_lane.h): X entry-major, 64 LANE_EMAX doubles per (group of 64 units, latent)
@@ -73,6 +78,22 @@ struct SplitArgs {
     int shg_rk[16];            // shared-G launches: rank and compact factor of lat[i] (no table lookups per wave)
     const double* shg_gl[16];
     int lat[16];       // their indices
+};
+
+// A replicated set (vlgp_replicate_units): n_rep copies of a source set's units, replica-major, replica k with channel
+// ch[k] left out.  Only the row passes read channels: their EXCL instantiations map a row of replica k to its source
+// row (row - k rows_src) for y and xb, and zero channel ch[k]'s loadings in the record they read -- a compare and select
+// in place, same summation order, so a replica runs bit for bit what the same kernels run with a[:, ch[k]] = 0.
+// EXCL = false instantiations never read it.  (esplit_ya takes it by value; esplit_pass through SplitArgs::excl, so that
+// the kernel arguments of its existing instantiations -- and with them their code -- stay as they were.)
+struct ExclArgs {
+    const int* ch;         // (n_rep) excluded channel of each replica
+    const double* wconst;  // (n_rep, 16): the Gaussian constant of w (wconst) without that channel
+    const double* y;       // the source set's y and xb (row-major, rows_src rows)
+    const double* xb;
+    int64_t rows_src;
+    int64_t row_base;      // absolute row of the launch's first row (esplit_ya: by value, set per launch)
+    const double* mu_lm;   // the row passes: unshifted latent-major mu -- a lane's row base is A.mu - mu_lm
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -143,6 +164,23 @@ esplit_cols_kernel(int N, int L, int LT, int REC, const double* __restrict__ a, 
     }
 }
 
+// the Gaussian constant of w per replica of a replicated set: wconst of esplit_cols_kernel with channel ch[k] left out
+// (the same fma chain in channel order, the left-out term skipped: with a[:, n] = 0 it adds exactly 0)
+__global__ void __launch_bounds__(256)
+esplit_excl_wconst(int N, int L, int n_rep, const double* __restrict__ a, const double* __restrict__ noise,
+                   const int* __restrict__ gauss, const int* __restrict__ ch, double* __restrict__ wconst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rep * 16) return;
+    const int k = i >> 4, l = i & 15;
+    double s = 0.0;
+    if (l < L) {
+        const int ex = ch[k];
+        for (int n = 0; n < N; ++n)
+            if (gauss[n] && n != ex) s = fma(a[l * N + n] * a[l * N + n], 1.0 / noise[n], s);
+    }
+    wconst[i] = s;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // (rows, L) <-> (L, rows): the split kernels work on latent-major copies -- a wave whose lanes are rows (passes) or time
 // bins of one latent (latent kernels) then touches 8 contiguous bytes per lane instead of 8 of every 8 L (PMC: ~500
@@ -178,10 +216,10 @@ esplit_from_lm(int L, int64_t rows, const double* __restrict__ b0, const double*
 // time (128 contiguous bytes per row and load), four rows per wave and step; the per-channel coefficients of a lane's
 // channels stay in registers (N <= 16 NJ).  The lane-per-row form (esplit_pass<SP_YA>) reads 8 bytes of every 8 N:
 // 466 MB of HBM traffic for 160 MB of y at C3 (PMC), 108 us.
-template <int LT, int NJ>
+template <int LT, int NJ, bool EXCL = false>
 __global__ void __launch_bounds__(256)
 esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, const double* __restrict__ ycoef,
-          double* __restrict__ ya, int rows_per_wave) {
+          double* __restrict__ ya, int rows_per_wave, ExclArgs X) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int r4 = lane >> 4, c16 = lane & 15;
     double cf[NJ][LT];
@@ -196,6 +234,12 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
         const int64_t row = w0 + it + r4;
         const bool in = row < rows;
         const double* yr = y + (in ? row : 0) * N;
+        int ex = -1;  // EXCL: the channel this row's replica leaves out
+        if constexpr (EXCL) {
+            const int64_t ar = X.row_base + (in ? row : 0), k = ar / X.rows_src;
+            yr = X.y + (ar - k * X.rows_src) * N;
+            ex = X.ch[k];
+        }
         double acc[LT];
 #pragma unroll
         for (int l = 0; l < LT; ++l) acc[l] = 0.0;
@@ -204,7 +248,7 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
             const int n = c16 + 16 * j;
             const double yv = (in && n < N) ? yr[n] : 0.0;
 #pragma unroll
-            for (int l = 0; l < LT; ++l) acc[l] = fma(yv, cf[j][l], acc[l]);
+            for (int l = 0; l < LT; ++l) acc[l] = fma(yv, (EXCL && n == ex) ? 0.0 : cf[j][l], acc[l]);
         }
 #pragma unroll
         for (int o = 8; o >= 1; o >>= 1)
@@ -224,7 +268,7 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
 // latency, not throughput); the partial sums meet in LDS and are added in wave order (deterministic).
 // RPL: rows per lane (rows row0 + 64 q): one channel record serves RPL rows -- fewer scalar loads per (row, channel)
 // and RPL independent exp chains per record.
-template <int LT, int KIND, bool HASXB, int CS, int RPL>
+template <int LT, int KIND, bool HASXB, int CS, int RPL, bool EXCL = false>
 __global__ void __launch_bounds__(256)
 esplit_pass(SplitArgs A, const double* __restrict__ cols) {
     constexpr int REC = rec_len<LT>();
@@ -258,6 +302,25 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
         yrow[q] = A.y + rr[q] * N;
         xbrow[q] = HASXB ? A.xb + rr[q] * N : nullptr;
     }
+    int ex[RPL], rk[RPL];  // EXCL: replica of each row and the channel it leaves out
+    ExclArgs X;
+    if constexpr (EXCL) {
+        X = *A.excl;
+        X.row_base = A.mu - X.mu_lm;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int64_t ar = X.row_base + rr[q], k = ar / X.rows_src, sr = ar - k * X.rows_src;
+            rk[q] = (int)k;
+            ex[q] = X.ch[k];
+            yrow[q] = X.y + sr * N;
+            xbrow[q] = HASXB ? X.xb + sr * N : nullptr;
+        }
+    }
+    // entry i < 2 LT of a channel record as row q sees it: 0 for the channel its replica leaves out (EXCL)
+    auto rec = [&](const double (&rv)[REC], int q, int i) -> double {
+        if constexpr (EXCL) return (int)__double_as_longlong(rv[2 * LT + 2]) == ex[q] ? 0.0 : rv[i];
+        else return rv[i];
+    };
     // the residual pass subtracts from ya at the end: fetched here, by the wave that writes (a load after the channel
     // loop is one more trip to memory in the life of a short wave)
     double yav[RPL][LT], wv[RPL][LT];
@@ -306,7 +369,7 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
             const int n = (int)__double_as_longlong(rv[2 * LT + 2]);
             const double yc = yrow[0][n] * rv[2 * LT + 1];
 #pragma unroll
-            for (int l = 0; l < LT; ++l) acc[0][l] = fma(yc, rv[l], acc[0][l]);
+            for (int l = 0; l < LT; ++l) acc[0][l] = fma(yc, rec(rv, 0, l), acc[0][l]);
         };
         double ra_[REC], rb_[REC];
         load_rec(0, ra_);
@@ -325,12 +388,12 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
             for (int q = 0; q < RPL; ++q) {
                 double eta = HASXB ? xbrow[q][(int)__double_as_longlong(rv[2 * LT + 2])] : rv[2 * LT];
 #pragma unroll
-                for (int l = 0; l < LT; ++l) eta = fma(mr[q][l], rv[l], eta);
+                for (int l = 0; l < LT; ++l) eta = fma(mr[q][l], rec(rv, q, l), eta);
 #pragma unroll
-                for (int l = 0; l < LT; ++l) eta = fma(vr[q][l], rv[LT + l], eta);
+                for (int l = 0; l < LT; ++l) eta = fma(vr[q][l], rec(rv, q, LT + l), eta);
                 const double rate = trunc_exp_tab256(eta, etab);
 #pragma unroll
-                for (int l = 0; l < LT; ++l) acc[q][l] = fma(rate, rv[KIND == SP_RES ? l : LT + l], acc[q][l]);
+                for (int l = 0; l < LT; ++l) acc[q][l] = fma(rate, rec(rv, q, KIND == SP_RES ? l : LT + l), acc[q][l]);
             }
         };
         double ra_[REC], rb_[REC];
@@ -352,10 +415,10 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
                 for (int q = 0; q < RPL; ++q) {
                     double eta = HASXB ? xbrow[q][(int)__double_as_longlong(ra_[2 * LT + 2])] : ra_[2 * LT];
 #pragma unroll
-                    for (int l = 0; l < LT; ++l) eta = fma(mr[q][l], ra_[l], eta);
+                    for (int l = 0; l < LT; ++l) eta = fma(mr[q][l], rec(ra_, q, l), eta);
                     const double mval = eta * ra_[2 * LT + 1];
 #pragma unroll
-                    for (int l = 0; l < LT; ++l) acc[q][l] = fma(mval, ra_[l], acc[q][l]);
+                    for (int l = 0; l < LT; ++l) acc[q][l] = fma(mval, rec(ra_, q, l), acc[q][l]);
                 }
             }
         }
@@ -390,7 +453,10 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
                         if (A.ra) A.ra[(int64_t)l * A.ld + row] = rav;
                         if (A.sv) A.sv[(int64_t)l * A.ld + row] = fma(wv[q][l], mr[q][l], rav);
                     } else {
-                        A.w[(int64_t)l * A.ld + row] = fma(2.0, acc[q][l], A.wconst[l]);  // (the records hold a^2 / 2)
+                        double wc;
+                        if constexpr (EXCL) wc = X.wconst[rk[q] * 16 + l];
+                        else wc = A.wconst[l];
+                        A.w[(int64_t)l * A.ld + row] = fma(2.0, acc[q][l], wc);  // (the records hold a^2 / 2)
                         if ((A.dmask >> l) & 1u) A.mu[(int64_t)l * A.ld + row] = mr[q][l];
                     }
                 }
@@ -1591,22 +1657,37 @@ static thread_local hipStream_t t_lane = nullptr;
 // (a helper reached without a lane would launch on the legacy null stream without a word)
 #define NEED_LANE(ctx) \
     do { if (!t_lane) return vlgp_fail(ctx, VLGP_ERR_STATE, "split E-step launch helper called outside launch_estep_split"); } while (0)
+// the replica table of the set the row passes run on (its row_base that of the lane), or null: set beside t_lane
+static thread_local const ExclArgs* t_excl = nullptr;
+static thread_local const ExclArgs* t_excl_dev = nullptr;  // its device copy (the row passes read it through SplitArgs::excl)
 
-template <int LT, int CS, int RPL>
-int run_passes_cs(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) {
+template <int LT, int CS, int RPL, bool EXCL>
+int run_passes_x(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) {
     constexpr int RPB = (256 / CS) * RPL;
     const dim3 grid((unsigned)((A.rows + RPB - 1) / RPB)), blk(256);
     NEED_LANE(ctx);
     hipStream_t st = t_lane;
     if (A.xb) {
-        if (kind == SP_RES) hipLaunchKernelGGL((esplit_pass<LT, SP_RES, true, CS, RPL>), grid, blk, 0, st, A, cols);
-        else hipLaunchKernelGGL((esplit_pass<LT, SP_W, true, CS, RPL>), grid, blk, 0, st, A, cols);
+        if (kind == SP_RES) hipLaunchKernelGGL((esplit_pass<LT, SP_RES, true, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
+        else hipLaunchKernelGGL((esplit_pass<LT, SP_W, true, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
     } else {
-        if (kind == SP_RES) hipLaunchKernelGGL((esplit_pass<LT, SP_RES, false, CS, RPL>), grid, blk, 0, st, A, cols);
-        else hipLaunchKernelGGL((esplit_pass<LT, SP_W, false, CS, RPL>), grid, blk, 0, st, A, cols);
+        if (kind == SP_RES) hipLaunchKernelGGL((esplit_pass<LT, SP_RES, false, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
+        else hipLaunchKernelGGL((esplit_pass<LT, SP_W, false, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
     }
     HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
+}
+
+template <int LT, int CS, int RPL>
+int run_passes_cs(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) {
+    if constexpr (RPL == 1) {
+        if (t_excl) {
+            SplitArgs Ax = A;
+            Ax.excl = t_excl_dev;
+            return run_passes_x<LT, CS, RPL, true>(ctx, Ax, kind, cols);
+        }
+    }
+    return run_passes_x<LT, CS, RPL, false>(ctx, A, kind, cols);
 }
 
 template <int LT>
@@ -1614,8 +1695,15 @@ int run_passes(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) 
     NEED_LANE(ctx);
     if (kind == SP_YA) {
         const dim3 grid((unsigned)((A.rows + 255) / 256)), blk(256);
-        if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, SP_YA, true, 1, 1>), grid, blk, 0, t_lane, A, cols);
-        else hipLaunchKernelGGL((esplit_pass<LT, SP_YA, false, 1, 1>), grid, blk, 0, t_lane, A, cols);
+        if (t_excl) {
+            SplitArgs Ax = A;
+            Ax.excl = t_excl_dev;
+            if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, SP_YA, true, 1, 1, true>), grid, blk, 0, t_lane, Ax, cols);
+            else hipLaunchKernelGGL((esplit_pass<LT, SP_YA, false, 1, 1, true>), grid, blk, 0, t_lane, Ax, cols);
+        } else {
+            if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, SP_YA, true, 1, 1>), grid, blk, 0, t_lane, A, cols);
+            else hipLaunchKernelGGL((esplit_pass<LT, SP_YA, false, 1, 1>), grid, blk, 0, t_lane, A, cols);
+        }
         HIPCHK(ctx, hipGetLastError());
         return VLGP_OK;
     }
@@ -1625,7 +1713,7 @@ int run_passes(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) 
     static const int forced_rpl = getenv("VLGP_PASS_RPL") ? atoi(getenv("VLGP_PASS_RPL")) : 0;
     int cs = forced;
     if (cs != 1 && cs != 2 && cs != 4) cs = A.ntot >= 64 ? 4 : (A.ntot >= 32 ? 2 : 1);
-    const int rpl = forced_rpl == 2 && LT <= 5 ? 2 : 1;
+    const int rpl = forced_rpl == 2 && LT <= 5 && !t_excl ? 2 : 1;  // (replicated sets: one row per lane)
     if constexpr (LT <= 5) {
         if (rpl == 2) {
             if (cs == 4) return run_passes_cs<LT, 4, 2>(ctx, A, kind, cols);
@@ -1653,8 +1741,14 @@ int run_ya(vlgp_ctx* ctx, const SplitArgs& A, int LT, const double* cols, const 
     const dim3 grid((unsigned)((A.rows + 4 * rows_per_wave - 1) / (4 * rows_per_wave))), blk(256);
     NEED_LANE(ctx);
     hipStream_t st = t_lane;
-#define ESPLIT_YA(LTV, NJV) \
-    hipLaunchKernelGGL((esplit_ya<LTV, NJV>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, A.ya, rows_per_wave)
+    const ExclArgs X = t_excl ? *t_excl : ExclArgs{};
+#define ESPLIT_YA(LTV, NJV)                                                                                              \
+    do {                                                                                                                 \
+        if (t_excl) hipLaunchKernelGGL((esplit_ya<LTV, NJV, true>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, \
+                                       A.ya, rows_per_wave, X);                                                          \
+        else hipLaunchKernelGGL((esplit_ya<LTV, NJV>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, A.ya,       \
+                                rows_per_wave, X);                                                                       \
+    } while (0)
     const bool small = A.N <= 64;
     if (LT == 3) { if (small) ESPLIT_YA(3, 4); else ESPLIT_YA(3, 8); }
     else if (LT == 5) { if (small) ESPLIT_YA(5, 4); else ESPLIT_YA(5, 8); }
@@ -1852,23 +1946,34 @@ int run_latent(vlgp_ctx* ctx, SplitArgs A, const LatentClasses& C, bool mean) {
 int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
     *handled = 0;
     const int N = ctx->N, L = ctx->L;
+    // a replicated set (vlgp_replicate_units) runs here or nowhere: only these row passes leave a channel out, so neither
+    // the switches nor the size heuristics below may send it to another kernel family -- a limit it exceeds is an error
+    const bool rep = us.rep_src >= 0;
+#define SPLIT_DECLINE(cond, what)                                                                                   \
+    do {                                                                                                            \
+        if (cond) {                                                                                                 \
+            if (rep) return vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: the split E-step cannot run it (%s)", what); \
+            return VLGP_OK;                                                                                         \
+        }                                                                                                           \
+    } while (0)
     const char* sw = getenv("VLGP_ESTEP_SPLIT");
-    if (sw && sw[0] == '0') return VLGP_OK;
-    if (getenv("VLGP_ESTEP_GENERIC")) return VLGP_OK;
-    if (L > 10 || N > 1024) return VLGP_OK;
+    if (!rep && sw && sw[0] == '0') return VLGP_OK;
+    if (!rep && getenv("VLGP_ESTEP_GENERIC")) return VLGP_OK;
+    SPLIT_DECLINE(L > 10, "L > 10");
+    SPLIT_DECLINE(N > 1024, "N > 1024");
     // long units (full-length trials): the same launch sequence with one workgroup per (unit, latent) task, once there
     // are enough tasks to fill the chip (VLGP_ESTEP_LSPLIT=0/1 never / always)
     const bool lng = us.Tmax > 64;
     if (lng) {
         const char* lsw = getenv("VLGP_ESTEP_LSPLIT");
-        if (lsw && lsw[0] == '0') return VLGP_OK;
-        if (ctx->R > LRP) return VLGP_OK;
-        if (!(lsw && lsw[0] == '1') && (int64_t)us.M * L < 128) return VLGP_OK;
+        if (!rep && lsw && lsw[0] == '0') return VLGP_OK;
+        SPLIT_DECLINE(ctx->R > LRP, "long units with prior rank R above the long-unit split limit");
+        if (!rep && !(lsw && lsw[0] == '1') && (int64_t)us.M * L < 128) return VLGP_OK;
     }
     // the persistent kernel (one workgroup per unit, two or three per CU) wins while its workgroups are ONE generation
     // (measured at N = 100, L = 5: 500 units 0.89 ms persistent / 1.09 ms split; 1000 units 2.09 / 1.42 ms -- the second
     // generation costs as much as the first however few units it holds)
-    if (!lng && !(sw && sw[0] == '1') && (us.rows < 16LL * 1024 || us.M <= 2 * ctx->n_cu)) return VLGP_OK;
+    if (!rep && !lng && !(sw && sw[0] == '1') && (us.rows < 16LL * 1024 || us.M <= 2 * ctx->n_cu)) return VLGP_OK;
     const bool need_prior = (E.mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
     int rmax = 0;
     int rlat[16] = {0};  // largest rank of each latent over the priors this set uses
@@ -1892,7 +1997,7 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
             }
         }
     }
-    if (!lng && rmax > 32) return VLGP_OK;
+    SPLIT_DECLINE(!lng && rmax > 32, "short units at effective prior rank above 32");
     const int maxra = rmax <= 16 ? 16 : (rmax <= 20 ? 20 : (rmax <= 24 ? 24 : 32));
     const int LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
     const int REC = (2 * LT + 3 + 1) & ~1;
@@ -1915,13 +2020,28 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
         us.scratch_len = need;
     }
     if (!ctx->d_ecols) HIPCHK(ctx, hipMalloc(&ctx->d_ecols, sizeof(double) * ((size_t)N * 50 + 32)));
-    if (REC > 34) return VLGP_OK;
+    SPLIT_DECLINE(REC > 34, "channel records longer than 34 doubles");
+#undef SPLIT_DECLINE
     double* cols = ctx->d_ecols;
     double* wconst = ctx->d_ecols + (int64_t)N * 34;
     double* ycoef = wconst + 32;  // (N, LT), LT <= 10
     hipLaunchKernelGGL(esplit_cols_kernel, dim3(1), dim3(256), 0, ctx->stream, N, L, LT, REC, ctx->d_a, ctx->d_b,
                        ctx->d_noise, ctx->d_gauss, cols, wconst, ycoef);
     HIPCHK(ctx, hipGetLastError());
+    ExclArgs XA{};  // replicated set: its replica table, source rows, per-replica wconst
+    if (rep) {
+        const UnitSet& src = ctx->sets[us.rep_src];
+        XA.ch = us.d_rep_ch;
+        XA.wconst = us.d_rep_wconst;
+        XA.y = src.y;
+        XA.xb = E.xb;  // (launch_estep points the replicas' xb at the source's, refreshed)
+        XA.rows_src = us.rows_src;
+        XA.row_base = 0;
+        XA.mu_lm = nullptr;  // (set below, with the latent-major copies)
+        hipLaunchKernelGGL(esplit_excl_wconst, dim3((unsigned)((us.n_rep * 16 + 255) / 256)), dim3(256), 0, ctx->stream, N,
+                           L, us.n_rep, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_ch, us.d_rep_wconst);
+        HIPCHK(ctx, hipGetLastError());
+    }
 
     SplitArgs A;
     A.N = N; A.L = L; A.M = us.M; A.rows = us.rows;
@@ -1935,6 +2055,12 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
         const unsigned nb = (unsigned)((us.rows + 255) / 256);
         hipLaunchKernelGGL(esplit_to_lm, dim3(nb), dim3(256), 0, ctx->stream, L, us.rows, E.mu, E.v, E.w, A.mu, A.v, A.w);
         HIPCHK(ctx, hipGetLastError());
+    }
+    if (rep) {  // the replica table the row passes read (a host copy that outlives the asynchronous upload)
+        XA.mu_lm = A.mu;
+        static_assert(sizeof(ExclArgs) <= sizeof(us.rep_xh), "UnitSet::rep_xh too small for ExclArgs");
+        memcpy(us.rep_xh, &XA, sizeof(ExclArgs));
+        HIPCHK(ctx, hipMemcpyAsync(us.d_rep_xa, us.rep_xh, sizeof(ExclArgs), hipMemcpyHostToDevice, ctx->stream));
     }
     A.failg = reinterpret_cast<int*>(A.xg + (int64_t)us.M * L * pkg);
     A.xl = reinterpret_cast<double*>(A.failg) + ((int64_t)us.M * L + 1) / 2 + 1;
@@ -1995,6 +2121,8 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
                          : (maxra <= 16 ? VLGP_PROF_ESTEP_RA16 : (maxra <= 24 ? VLGP_PROF_ESTEP_RA24 : VLGP_PROF_ESTEP_RA32));
     vlgp_prof_begin(ctx, kind);
     t_lane = ctx->stream;
+    t_excl = rep ? &XA : nullptr;
+    t_excl_dev = rep ? reinterpret_cast<const ExclArgs*>(us.d_rep_xa) : nullptr;
     int rc = VLGP_OK;
     if (with_mean) rc = run_ya(ctx, A, LT, cols, ycoef);
 
@@ -2101,6 +2229,7 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
         }
     }
     t_lane = ctx->stream;
+    t_excl = nullptr;
     for (int h = 1; h < n_lanes; ++h) {  // join whatever happened above: the extra lanes must never outlive the call
         (void)hipEventRecord(ctx->ev_e_join[h - 1], ctx->elane[h - 1]);
         (void)hipStreamWaitEvent(ctx->stream, ctx->ev_e_join[h - 1], 0);

@@ -66,6 +66,7 @@ class Engine:
             check(rc, None)
         self.h = h
         self.sets = {}  # set id -> (M, rows, offsets)
+        self.replicas = {}  # replicated set id -> its held-out channels (Engine.replicate)
         self.state_epoch = 0  # bumped by every call that can change a set's mu (em_iteration's norm cache keys on it)
         self.rank, self.world = 0, 1
         self.host_exchange = False
@@ -145,6 +146,7 @@ class Engine:
         self._ck(self.lib.vlgp_upload_units(self.h, set_id, len(trials), i64ptr(off), dptr(y), dptr(x),
                                             dptr(mu), dptr(v), dptr(w)))
         self.sets[set_id] = (len(trials), int(off[-1]), off)
+        self.replicas.pop(set_id, None)
 
     def cut(self, src, dst, starts, window):
         self.state_epoch += 1
@@ -152,6 +154,7 @@ class Engine:
         self._ck(self.lib.vlgp_cut_units(self.h, src, dst, len(starts), i64ptr(starts), int(window)))
         off = np.arange(len(starts) + 1, dtype=np.int64) * int(window)
         self.sets[dst] = (len(starts), int(off[-1]), off)
+        self.replicas.pop(dst, None)
 
     def set_overlaps(self, set_id, stage_start, links, link_start):
         """Overlapping units of a copied cut: see vlgp_set_overlaps (include/vlgp_hip.h)."""
@@ -185,6 +188,31 @@ class Engine:
         self.state_epoch += 1
         self._ck(self.lib.vlgp_free_units(self.h, set_id))
         self.sets.pop(set_id, None)
+        self.replicas.pop(set_id, None)
+
+    def replicate(self, src, dst, channels):
+        """Set ``dst`` := one replica of set ``src`` per entry of ``channels``, replica k leaving channel
+        ``channels[k]`` out of its E-step (vlgp_replicate_units): replica-major units, y / x aliased to ``src``."""
+        self.state_epoch += 1
+        ch = np.ascontiguousarray(channels, dtype=np.int32)
+        self._ck(self.lib.vlgp_replicate_units(self.h, int(src), int(dst), len(ch), iptr(ch)))
+        m, rows, off = self.sets[src]
+        k = len(ch)
+        roff = np.concatenate([r * rows + off[:-1] for r in range(k)] + [np.array([k * rows], dtype=np.int64)])
+        self.sets[dst] = (k * m, k * rows, roff)
+        self.replicas[dst] = ch
+
+    def loglik(self, set_id, vb=True, want_rate=False):
+        """Plug-in rates and per-channel log-likelihood sums of a set (vlgp_loglik): ``(sums, rate)``, sums
+        (slots, 4) and rate (rows, slots) or None; slots = N for a plain set, the replicas for a replicated one."""
+        _, rows, _ = self.sets[set_id]
+        n_rep = self.replicas.get(set_id)
+        slots = self.N if n_rep is None else len(n_rep)
+        rows_out = rows if n_rep is None else rows // max(len(n_rep), 1)
+        sums = np.empty((slots, 4))
+        rate = np.empty((rows_out, slots)) if want_rate else None
+        self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
+        return sums, rate
 
     # -- parameters -------------------------------------------------------
     def set_params(self, a, b, noise):
