@@ -302,7 +302,10 @@ int vlgp_profile_get(vlgp_ctx* ctx, int kind, int64_t* launches, double* total_m
 int vlgp_debug_phase_clock(vlgp_ctx* ctx, int on, uint64_t out[8]);
 /* Element-wise probe of the device arithmetic the prior kernel relies on being bit-identical to the
  * reference's NumPy (vlgp/math.py:113-119): kind 0 out = exp(a) as np.exp computes it, 1 out = sqrt(a),
- * 2 out = a / b, 3 out = fma(a, b, out).  Host arrays of n doubles; b may be NULL for kinds 0, 1. */
+ * 2 out = a / b, 3 out = fma(a, b, out); and of the exponentials every Poisson rate goes through (csrc/fast_exp.h,
+ * tables in LDS as the kernels hold them): 4 out = fast_exp(clamp10(a)), 5 fast_exp_tab<false>(clamp10(a)),
+ * 6 trunc_exp_tab64(a), 7 fast_exp_tab256<false>(clamp10(a)), 8 trunc_exp_tab256(a).  Host arrays of n doubles; b is
+ * read by kinds 2, 3 only and may be NULL otherwise. */
 int vlgp_debug_npx(vlgp_ctx* ctx, int kind, int64_t n, const double* a, const double* b, double* out);
 /* Which implementation ran the most recent vlgp_estep / vlgp_update_w / vlgp_update_v of this handle (the
  * reference has one serial loop, vlgp/core.py:123-126; the library picks a kernel family by set shape, and the

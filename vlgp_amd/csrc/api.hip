@@ -1631,7 +1631,7 @@ extern "C" int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]) {
 extern "C" int vlgp_debug_npx(vlgp_ctx* ctx, int kind, int64_t n, const double* a, const double* b, double* out) {
     NEED_CTX(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->dev));
-    if (n < 1 || !a || !out || kind < 0 || kind > 3 || (kind >= 2 && !b)) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad probe arguments");
+    if (n < 1 || !a || !out || kind < 0 || kind > 8 || ((kind == 2 || kind == 3) && !b)) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad probe arguments");
     CHK(vlgp_ensure_work(ctx, 3 * n));
     double* W = ctx->d_work;
     HIPCHK(ctx, hipMemcpyAsync(W, a, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));

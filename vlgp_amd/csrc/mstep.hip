@@ -893,7 +893,10 @@ __global__ void noise_stats_kernel(int N, int L, int P, double count, const doub
     const double s1 = E[(int64_t)N + n] - s_eta;
     const double s2 = (E[n] - 2.0 * s_yeta) + s_eta2;
     const double mean = s1 / count;
-    noise[n] = s2 / count - mean * mean;
+    // a constant residual (silent channel, zero loading) cancels completely: rounding may leave -1e-15, a variance
+    // never below zero (the comparison keeps a NaN)
+    const double var = s2 / count - mean * mean;
+    noise[n] = var < 0.0 ? 0.0 : var;
 }
 __global__ void zero_kernel(int64_t n, double* p) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -14,6 +14,7 @@
 // (2) first arg-max of d[i:]; (3) every remaining row gets its new column entry and residual
 // (npx_ichol_row), one row per thread.
 #include "ctx.h"
+#include "fast_exp.h"
 #include "np_exact.h"
 
 struct IcholArgs {
@@ -515,7 +516,29 @@ __global__ void npx_probe_kernel(int kind, int64_t n, const double* a, const dou
     else if (kind == 2) out[i] = a[i] / b[i];
     else out[i] = fma(a[i], b[i], out[i]);
 }
+// ---- debug: the device build of fast_exp.h, element-wise (kinds 4 ... 8: the five exponentials the Poisson rates go
+// through).  The tables are filled in LDS by the product's own init functions, as the E- and M-step kernels fill them.
+__global__ void __launch_bounds__(256) rate_probe_kernel(int kind, int64_t n, const double* a, double* out) {
+    __shared__ double tab64[64], tab256[256];
+    fast_exp_tab_init(tab64, threadIdx.x);
+    fast_exp_tab256_init(tab256, threadIdx.x);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    if (kind == 4) out[i] = fast_exp(clamp10(x));
+    else if (kind == 5) out[i] = fast_exp_tab<false>(clamp10(x), tab64);
+    else if (kind == 6) out[i] = trunc_exp_tab64(x, tab64);
+    else if (kind == 7) out[i] = fast_exp_tab256<false>(clamp10(x), tab256);
+    else out[i] = trunc_exp_tab256(x, tab256);
+}
 int launch_npx_probe(vlgp_ctx* ctx, int kind, int64_t n, const double* d_a, const double* d_b, double* d_out) {
+    if (kind >= 4) {
+        hipLaunchKernelGGL(rate_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, kind, n, d_a,
+                           d_out);
+        HIPCHK(ctx, hipGetLastError());
+        return VLGP_OK;
+    }
     hipLaunchKernelGGL(npx_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, kind, n, d_a, d_b,
                        d_out);
     HIPCHK(ctx, hipGetLastError());
