@@ -132,6 +132,20 @@ int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* 
  * own held-out channel, on the source rows: rate (rows_src, n_rep) or NULL, sums (n_rep, 4).  Sums cover this handle's
  * units only (no reduction over ranks) and are bitwise reproducible (fixed-order two-stage reduction, no atomics). */
 int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums);
+/* Terms of the variational lower bound of a plain set (uploaded or cut; a replicated set is VLGP_ERR_STATE) under its
+ * current posterior (mu, v, w), the current parameters and the prior factors the set's lengths are bound to.
+ *   row_sums (N, 4): per channel, with eta = a_n.mu_t + (b x)_tn and s = 1/2 (a_n^2).v_t (s = 0 when vb == 0),
+ *     Poisson   {sum E_q log p, sum y, sum rate, sum y s},  E_q log p = y eta - trunc_exp(eta + s) - lgamma(y + 1)
+ *     Gaussian  {sum E_q log p, sum y, sum eta, sum s / noise_n},
+ *               E_q log p = -log(2 pi noise_n) / 2 - ((y - eta)^2 + 2 s) / (2 noise_n)
+ *   row_ell (rows) or NULL: per row the sum of E_q log p over the channels (the per-unit split is the caller's sum)
+ *   kl_terms (units, L, 4): with G the compact (T, r) prior factor of the unit's length and latent,
+ *     H = I_r + G' diag(w) G and beta = argmin |G beta - mu|:  {log det H, tr H^-1, beta'beta, |mu - G beta|^2};
+ *     KL[q || p] = (tr H^-1 + beta'beta - r + log det H) / 2.  A pivot of H or G'G that is not positive makes the four
+ *     terms of that (unit, latent) NaN; *n_failed (may be NULL) counts those pairs.
+ * Waits for a pending M-step and norms pass; changes no unit state, no parameter and nothing vlgp_hstep_prepare built.
+ * This handle's units only (no reduction over ranks); fixed-order reductions, no atomics: the same bits on every run. */
+int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms, int* n_failed);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

@@ -54,6 +54,7 @@ _SIGNATURES = {
     "vlgp_free_units": (C.c_int, [_h, C.c_int]),
     "vlgp_replicate_units": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip]),
     "vlgp_loglik": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
+    "vlgp_elbo": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "vlgp_set_params": (C.c_int, [_h, _dp, _dp, _dp]),
     "vlgp_get_params": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp]),
     "vlgp_build_prior": (C.c_int, [_h, C.c_int, _ip, _dp, _dp]),

@@ -87,8 +87,9 @@ class FitSession:
     ``fit`` is ``FitSession(...).run().finish()``.
     """
 
-    def __init__(self, trials, n_factors, device=0, comm=None, verbose=True, **kwargs):
+    def __init__(self, trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, **kwargs):
         self.echo = _echo if verbose else None
+        self.track_elbo = bool(track_elbo)
         echo = self.echo
         self.trials = trials
         self.config = config = get_config(**kwargs)
@@ -169,6 +170,8 @@ class FitSession:
 
     def em_iteration(self):
         """One EM iteration on the segments; True when the stopping rule fires."""
+        if self.track_elbo:
+            return E.em_iteration(self.segs, self.params, self.config, self.runtime, self.echo, track_elbo=True)
         return E.em_iteration(self.segs, self.params, self.config, self.runtime, self.echo)
 
     def run(self):
@@ -192,6 +195,12 @@ class FitSession:
             if echo:
                 echo("Inferring")
             E.infer(self.dev_trials, params, config, echo=echo)
+            if self.track_elbo:  # the bound of the full-length trials under the final posterior, summed over the ranks
+                final = E._elbo_totals(eng, SET_TRIALS, config["method"] == "VB")
+                if eng.world > 1:
+                    eng.allreduce_host(final)
+                self.runtime["elbo_final"] = float(final[0])
+                config["runtime"] = self.runtime
             self.dev_trials.pull()
             if self.materialize_x:
                 for tr in self.trials:
@@ -212,7 +221,7 @@ class FitSession:
             self.eng = None
 
 
-def fit(trials, n_factors, device=0, comm=None, verbose=True, **kwargs):
+def fit(trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, **kwargs):
     """Variational-EM fit of vLGP on one MI355X (or one rank of several).
 
     Same arguments as the reference: ``lik``, ``history``, ``a``, ``b``,
@@ -222,9 +231,15 @@ def fit(trials, n_factors, device=0, comm=None, verbose=True, **kwargs):
     factor -- the device kernel is bit-identical to the reference's on the NumPy 2.2 / AVX-512 / OpenBLAS
     stack the golden vectors were captured on, "host" uses this host's own NumPy: INTEGRATION.md),
     ``materialize_x`` (default True: trials that came
-    without regressors get a writable ``np.ones((T, xdim, N))`` back, as the reference leaves them).
+    without regressors get a writable ``np.ones((T, xdim, N))`` back, as the reference leaves them),
+    ``track_elbo`` (default False: nothing extra runs and no key is added.  True: ``config["runtime"]["elbo"]``
+    gets the variational lower bound after every E-step, ``"elbo_ell"`` / ``"elbo_kl"`` its two parts, and
+    ``"elbo_final"`` the bound of the full-length trials after the final inference; all summed over the ranks.  The
+    per-iteration trace is the objective of the SEGMENT set the EM loop works on -- segments of a trial whose length
+    is not a multiple of the window overlap -- not of the trials; see ``vlgp_amd.evaluation.elbo``).
     """
-    return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, **kwargs).run().finish()
+    return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, track_elbo=track_elbo,
+                      **kwargs).run().finish()
 
 
 def bind_priors(eng, trials, params):

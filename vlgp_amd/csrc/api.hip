@@ -598,7 +598,7 @@ extern "C" int vlgp_destroy(vlgp_ctx* ctx) {
     free_priors(ctx);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(ctx->d_gauss); fr(ctx->d_a); fr(ctx->d_b); fr(ctx->d_noise); fr(ctx->d_da); fr(ctx->d_db);
-    fr(ctx->d_hwlm); fr(ctx->d_ecols); fr(ctx->d_fail); fr(ctx->d_fail_m); fr(ctx->d_work_m); fr(ctx->d_clk); fr(ctx->d_work);
+    fr(ctx->d_hwlm); fr(ctx->d_ecols); fr(ctx->d_fail); fr(ctx->d_fail_m); fr(ctx->d_work_m); fr(ctx->d_clk); fr(ctx->d_work); fr(ctx->d_elbo);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_m_start) (void)hipEventDestroy(ctx->ev_m_start);
     if (ctx->ev_m_done) (void)hipEventDestroy(ctx->ev_m_done);
@@ -898,6 +898,66 @@ extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double*
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_out);
     return rc;
+}
+
+// ---- variational lower bound -----------------------------------------------------
+// the waits of vlgp_join_m without its epoch bump: vlgp_elbo only reads, so what vlgp_hstep_prepare built stays valid
+static int join_m_reader(vlgp_ctx* ctx) {
+    CHK(wait_norms(ctx));
+    if (ctx->m_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_m_done));
+    return VLGP_OK;
+}
+
+extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms,
+                         int* n_failed) {
+    NEED_CTX(ctx);
+    CHK(vlgp_prior_collect(ctx));
+    CHK(join_m_reader(ctx));
+    if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
+    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    UnitSet* us = vlgp_get_set(ctx, set, true);
+    if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_elbo");
+    if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
+    if (n_failed) *n_failed = 0;
+    if (!us->x_ones) CHK(vlgp_refresh_xb(ctx, *us));
+    CHK(vlgp_bind_priors(ctx, *us));
+    int rp = 1, T_seen = -1;
+    for (int m = 0; m < us->M; ++m) {  // the largest effective rank among the set's lengths sizes the KL kernel's LDS
+        const int T = (int)(us->off[m + 1] - us->off[m]);
+        if (T == T_seen) continue;
+        T_seen = T;
+        const Prior& pr = ctx->priors.find(T)->second;  // (vlgp_bind_priors found every length)
+        for (int l = 0; l < ctx->L; ++l) rp = std::max(rp, pr.rl[l]);
+    }
+    const int N = ctx->N, L = ctx->L;
+    const int64_t tasks = (int64_t)us->M * L;
+    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo: too many (unit, latent) pairs");
+    const int64_t n_blk = (us->rows + 255) / 256;
+    const int64_t o_sums = (int64_t)N * n_blk * 4, o_terms = o_sums + 4 * (int64_t)N, o_rows = o_terms + 4 * tasks;
+    const int64_t o_flag = o_rows + (row_ell ? us->rows : 0), need = o_flag + (tasks + 1) / 2;
+    if (need > ctx->elbo_len) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->d_elbo) HIPCHK(ctx, hipFree(ctx->d_elbo));
+        ctx->d_elbo = nullptr;
+        ctx->elbo_len = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->d_elbo, sizeof(double) * (size_t)(need + need / 4)));
+        ctx->elbo_len = need + need / 4;
+    }
+    double* d = ctx->d_elbo;
+    int* d_flag = reinterpret_cast<int*>(d + o_flag);
+    CHK(launch_elbo(ctx, *us, vb, rp, d, d + o_sums, row_ell ? d + o_rows : nullptr, d + o_terms, d_flag));
+    std::vector<int> flag((size_t)tasks);
+    HIPCHK(ctx, hipMemcpyAsync(row_sums, d + o_sums, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(kl_terms, d + o_terms, sizeof(double) * 4 * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream));
+    if (row_ell)
+        HIPCHK(ctx, hipMemcpyAsync(row_ell, d + o_rows, sizeof(double) * (size_t)us->rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    int bad = 0;
+    for (int64_t i = 0; i < tasks; ++i) bad += flag[(size_t)i] != 0;
+    if (n_failed) *n_failed = bad;
+    return VLGP_OK;
 }
 
 // ---- parameters ------------------------------------------------------------

@@ -204,6 +204,10 @@ struct vlgp_ctx {
     hipEvent_t ev_stage_par = nullptr, ev_stage_map = nullptr;
     bool stage_par_busy = false, stage_map_busy = false;
 
+    // vlgp_elbo's own device buffer (partials, sums, terms, flags): it never borrows d_work, which a prepared H-step owns
+    double* d_elbo = nullptr;
+    int64_t elbo_len = 0;
+
     std::string err;
 };
 
@@ -274,3 +278,7 @@ int launch_gather(vlgp_ctx* ctx, UnitSet& src, UnitSet& dst, int window);
 // n_rep) for a replicated one, or null; d_sums (slots, 4) with slots = N or n_rep, written in a fixed order
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
+// expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
+// effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace
+int launch_elbo(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_part, double* d_sums, double* d_row_ell,
+                double* d_terms, int* d_flag);

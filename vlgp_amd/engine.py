@@ -214,6 +214,27 @@ class Engine:
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
         return sums, rate
 
+    def elbo(self, set_id, vb=True, want_rows=False):
+        """Terms of the variational lower bound of a plain set (vlgp_elbo): ``(row_sums, kl_terms, n_failed, row_ell)``
+        -- row_sums (N, 4) per channel, kl_terms (units, L, 4) = log det H, tr H^-1, beta'beta, |mu - G beta|^2 per
+        (unit, latent), the number of pairs whose factorisation failed (their terms are NaN), and with ``want_rows``
+        the expected log-likelihood of every row summed over the channels (else None).  Changes no state."""
+        units, rows, _ = self.sets[set_id]
+        sums = np.empty((self.N, 4))
+        terms = np.empty((units, self.L, 4))
+        row_ell = np.empty(rows) if want_rows else None
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_elbo(self.h, int(set_id), int(bool(vb)), dptr(sums), dptr(row_ell), dptr(terms),
+                                    C.byref(n)))
+        return sums, terms, n.value, row_ell
+
+    def unit_ranks(self, set_id):
+        """(units, L) effective rank of the prior factor each (unit, latent) of the set is bound to."""
+        _, _, off = self.sets[set_id]
+        lengths = np.diff(np.asarray(off))
+        by_len = {int(T): self.prior_ranks(int(T)) for T in np.unique(lengths)}
+        return np.stack([by_len[int(T)] for T in lengths]).astype(np.int64)
+
     # -- parameters -------------------------------------------------------
     def set_params(self, a, b, noise):
         a, b, noise = _f64(a), _f64(b), _f64(noise)
@@ -825,9 +846,25 @@ def new_runtime():
     return {"it": 0, "e_elapsed": [], "m_elapsed": [], "h_elapsed": [], "em_elapsed": []}
 
 
-def em_iteration(trials, params, config, runtime, echo=None):
+def _elbo_totals(eng, sid, vb):
+    """[elbo, ell, kl] of this rank's units of set ``sid`` (evaluation.elbo_from_terms; NaN elbo / kl under MAP)."""
+    from .evaluation import elbo_from_terms
+
+    sums, terms, bad, _ = eng.elbo(sid, vb)
+    out = elbo_from_terms(sums, terms, eng.unit_ranks(sid), vb=vb, n_failed=bad)
+    return np.array([out["elbo"], out["ell"], float(np.sum(out["kl"]))])
+
+
+def em_iteration(trials, params, config, runtime, echo=None, track_elbo=False):
     """One pass of the body of core.vem (vlgp/core.py:298-357): E, M, H, timers,
-    callbacks, convergence test.  Returns True when the stopping rule fires."""
+    callbacks, convergence test.  Returns True when the stopping rule fires.
+
+    ``track_elbo``: after the E-step -- the posterior fresh, the parameters and the prior those the E-step used -- the
+    variational lower bound of the unit set is appended to ``runtime["elbo"]`` (its expected log-likelihood and KL
+    totals to ``runtime["elbo_ell"]``, ``runtime["elbo_kl"]``), summed over the ranks.  The units are the segments of
+    the cut, and segments of one trial may overlap: the trace is the objective of the SEGMENT SET, not of the trials.
+    The M-step is then enqueued after the E-step instead of under it (it would change a, b under the evaluation);
+    the iteration computes the same bits either way."""
     eng, sid = trials.engine, trials.set_id
     tol = config["tol"]
     runtime["it"] += 1
@@ -862,7 +899,7 @@ def em_iteration(trials, params, config, runtime, echo=None):
 
     # the M-step lane waits for the E-step on the device (an event): its ~50 launches are enqueued (one graph launch,
     # ~80 us of host time) while the E-step still runs, unless constrain_latent has to touch mu, a, b in between
-    early_m = m_async and not latent_constraint
+    early_m = m_async and not latent_constraint and not track_elbo
     if early_m:
         begin_m()
     m_first = m_async and ((eng.world > 1 and not eng.host_exchange) or bool(os.environ.get("VLGP_M_SEQUENTIAL")))
@@ -881,6 +918,7 @@ def em_iteration(trials, params, config, runtime, echo=None):
         after_estep()
     eng.estep_wait()   # the E-step alone: neither the M-step lane nor what is queued behind it
     t1 = time.perf_counter()
+    elbo_now = _elbo_totals(eng, sid, config["method"] == "VB") if track_elbo else None
     constrain_latent(trials, params, config)
     if latent_constraint:
         after_estep()
@@ -919,6 +957,11 @@ def em_iteration(trials, params, config, runtime, echo=None):
             runtime["it"], runtime["e_elapsed"][-1], runtime["m_elapsed"][-1]))
 
     norm_mu_now, norm_dmu = eng.norms_end()
+    if track_elbo:
+        if eng.world > 1:  # (here, with no lane in flight: every rank reports the sum over the ranks)
+            eng.allreduce_host(elbo_now)
+        for key, val in zip(("elbo", "elbo_ell", "elbo_kl"), elbo_now):
+            runtime.setdefault(key, []).append(float(val))
     if config["callbacks"]:
         trials.pull()
         for cb in config["callbacks"]:

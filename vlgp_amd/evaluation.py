@@ -16,7 +16,21 @@ Definitions (the tests hold the code to them).  For channel ``n`` at row ``t`` o
   constant rate at the channel's mean count over the evaluated rows (the ``lgamma`` terms cancel).  Gaussian channels,
   and channels without a spike, get NaN.
 
-Every sum is a fixed-order device reduction (``vlgp_loglik``): the results are the same bits on every run.
+Variational lower bound (``elbo``).  For one trial of length ``T``, latent ``l``, ``G = params["cholesky"][T][l]`` with
+its all-zero columns dropped (``T x r``), ``w = w[:, l]``, ``mu = mu[:, l]``:
+
+- ``H = I_r + G' diag(w) G``, ``S = H^-1``; the posterior the E-step works with is ``q(x_l) = N(mu, G S G')``, whose
+  diagonal is the stored ``v[:, l]``.
+- ``beta = argmin |G beta - mu|``; ``off_prior = |mu - G beta|^2 / max(|mu|^2, tiny)`` is reported: the KL against a
+  rank-``r`` prior exists only for ``mu`` in the range of ``G``.
+- ``KL[trial, l] = 1/2 (tr S + beta'beta - r + log det H)``.
+- expected log-likelihood of ``y[t, n]``, ``eta = a[:, n] . mu[t] + b[:, n] . x[t, :, n]``,
+  ``s = 1/2 (a[:, n] ** 2) . v[t]``: Poisson ``y eta - trunc_exp(eta + s) - lgamma(y + 1)``; Gaussian
+  ``-1/2 log(2 pi noise[n]) - ((y - eta) ** 2 + 2 s) / (2 noise[n])``.
+- ``ELBO = sum E_q log p(y | x) - sum KL``.  Under MAP (``method != "VB"``: a point estimate, no entropy) ``elbo`` and
+  ``kl`` are NaN and ``log_joint = sum log p(y | mu) - 1/2 sum beta'beta`` is reported instead.
+
+Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``): the results are the same bits on every run.
 """
 import math
 
@@ -26,7 +40,8 @@ from . import engine as E
 from ._lib import VlgpError
 from .api import bind_priors
 
-__all__ = ["loglik", "leave_one_out", "plan_chunks", "bits_per_spike", "REPLICA_BUDGET_BYTES"]
+__all__ = ["loglik", "leave_one_out", "plan_chunks", "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo",
+           "elbo_from_terms"]
 
 SET_TEST, SET_REPLICAS = 0, 2
 
@@ -90,6 +105,83 @@ def loglik(fit, per_channel=False, device=0):
         sums, _ = eng.loglik(SET_TEST, vb=vb)
     per = sums[:, 0].copy()
     return per if per_channel else float(np.sum(per))
+
+
+def elbo_from_terms(row_sums, kl_terms, ranks, vb=True, n_failed=0, mu_sq=None, row_ell=None, offsets=None):
+    """Assemble ``vlgp_elbo``'s two device arrays into the result dict (pure host code).
+
+    ``row_sums`` (N, 4): column 0 is the expected log-likelihood per channel.  ``kl_terms`` (units, L, 4):
+    ``log det H, tr S, beta'beta, |mu - G beta|^2`` per (unit, latent); NaN where the factorisation failed.  ``ranks``
+    (units, L): the effective rank ``r`` of each pair's prior factor.  ``mu_sq`` (units, L): ``|mu|^2``, for
+    ``off_prior`` (NaN without it).  ``row_ell`` (rows) with ``offsets`` (units + 1): per-row expected log-likelihood
+    and the units' row ranges, for ``elbo_per_trial``.
+
+    Returns ``elbo``, ``ell``, ``kl`` (units, L), ``ell_per_channel``, ``off_prior`` (units, L), ``n_failed``; under MAP
+    (``vb`` false) ``elbo`` and ``kl`` are NaN and ``log_joint = ell - 1/2 sum beta'beta`` is added; with ``row_ell``
+    also ``elbo_per_trial`` (``log_joint_per_trial`` under MAP).  A failed pair's NaN reaches every total it enters."""
+    row_sums = np.asarray(row_sums, dtype=float)
+    terms = np.asarray(kl_terms, dtype=float)
+    ranks = np.asarray(ranks, dtype=float)
+    if terms.ndim != 3 or terms.shape[2] != 4 or ranks.shape != terms.shape[:2]:
+        raise ValueError("kl_terms must be (units, L, 4) with ranks (units, L)")
+    logdet, tr_s, bb, resid = (terms[:, :, k] for k in range(4))
+    ell_ch = row_sums[:, 0].copy()
+    ell = float(np.sum(ell_ch))
+    if vb:
+        kl = 0.5 * (tr_s + bb - ranks + logdet)
+    else:
+        kl = np.full(ranks.shape, np.nan)
+    if mu_sq is None:
+        off = np.full(ranks.shape, np.nan)
+    else:
+        off = resid / np.maximum(np.asarray(mu_sq, dtype=float), np.finfo(float).tiny)
+    out = {"elbo": ell - float(np.sum(kl)), "ell": ell, "kl": kl, "ell_per_channel": ell_ch, "off_prior": off,
+           "n_failed": int(n_failed)}
+    if not vb:
+        out["log_joint"] = ell - 0.5 * float(np.sum(bb))
+    if row_ell is not None:
+        offsets = np.asarray(offsets, dtype=np.int64)
+        if offsets.shape != (terms.shape[0] + 1,):
+            raise ValueError("offsets must hold units + 1 row bounds")
+        ell_unit = np.array([np.sum(row_ell[offsets[i]:offsets[i + 1]]) for i in range(terms.shape[0])])
+        if vb:
+            out["elbo_per_trial"] = ell_unit - np.sum(kl, axis=1)
+        else:
+            out["log_joint_per_trial"] = ell_unit - 0.5 * np.sum(bb, axis=1)
+    return out
+
+
+def elbo(fit, per_trial=False, device=0):
+    """Variational lower bound of a fit's own trials under their own posterior ``mu, v, w``, the fit's parameters and
+    ``params["cholesky"]`` (module docstring for the definitions); lengths without a factor there are built from
+    ``omega, sigma`` as ``transform`` does.  Same calling shape as ``loglik``.
+
+    Returns a dict: ``elbo``, ``ell``, ``kl`` (trials, L), ``ell_per_channel``, ``off_prior`` (trials, L), ``n_failed``
+    (pairs whose ``H`` or ``G'G`` was not positive definite: their terms, and the totals, are NaN); under MAP ``elbo``
+    and ``kl`` are NaN and ``log_joint`` holds the penalised log joint.  ``per_trial=True`` adds ``elbo_per_trial``:
+    the device leaves the expected log-likelihood of every row (channels summed in order) in the same launch and the
+    rows of a trial are added on the host -- no second reduction kernel, no call per trial."""
+    trials, params, config = fit["trials"], fit["params"], fit.get("config") or {}
+    vb = config.get("method", "VB") == "VB"
+    L = params["zdim"]
+
+    def zeros(tr):
+        return np.zeros((tr["y"].shape[0], L))
+
+    units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
+              "v": tr["v"] if tr.get("v") is not None else zeros(tr),
+              "w": tr["w"] if tr.get("w") is not None else zeros(tr)} for tr in trials]
+    eng, _ = _engine(params, device)
+    with eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(SET_TEST, units)
+        bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
+        sums, terms, bad, row_ell = eng.elbo(SET_TEST, vb=vb, want_rows=per_trial)
+        ranks = eng.unit_ranks(SET_TEST)
+        offsets = eng.sets[SET_TEST][2]
+    mu_sq = np.array([np.sum(np.asarray(tr["mu"], dtype=float) ** 2, axis=0) for tr in trials])
+    return elbo_from_terms(sums, terms, ranks, vb=vb, n_failed=bad, mu_sq=mu_sq, row_ell=row_ell,
+                           offsets=offsets if per_trial else None)
 
 
 def _is_refusal(err):
