@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define VLGP_ABI_VERSION 2
+#define VLGP_ABI_VERSION 3
 #define VLGP_MAX_SETS 4
 #define VLGP_MAX_L 64             /* latents per handle.  The reference has no bound (vlgp/core.py:76,106; gp.py:82);
                                      up to 10 the specialised kernels run, up to 16 the register-resident generic
@@ -341,10 +341,14 @@ int vlgp_debug_last_estep_path(vlgp_ctx* ctx, int* path);
 #define VLGP_PATH_HSTEP_OLD 5      /* round-1 kernels behind their debug switches */
 #define VLGP_PATH_HSTEP_MIXED 6    /* one round, two launches: low-rank kernel up to rank 32, dense kernel for the rougher evaluations */
 int vlgp_debug_last_hstep_path(vlgp_ctx* ctx, int* path);
-/* The H-step's debug switches (environment VLGP_HSTEP_DENSE / _GENERIC / _LOWRANK / _GENERIC_SEG / _LR_TOL,
- * VLGP_DEBUG_OCC) are read when the handle is created; this reads them again (tests that switch kernels on a live
- * handle).  Nothing in production needs it. */
+/* The library's debug / test switches (environment VLGP_*; DESIGN.md section 7 lists them, csrc/ctx.h holds the table)
+ * have ONE lifetime: all of them are read when the handle is created and again by this call, and by nothing else -- no
+ * launch reads the environment.  A test that sets or unsets one on a live handle calls this afterwards.  A malformed or
+ * out-of-range value is reported on stderr and the switch keeps its default.  Nothing in production needs it. */
 int vlgp_debug_reload_switches(vlgp_ctx* ctx);
+/* The value the handle currently holds for the switch `name` ("VLGP_..."): a flag 0 / 1, a tri-state -1 (unset) / 0 / 1,
+ * an integer or a real.  VLGP_ERR_ARG for a name the table does not hold. */
+int vlgp_debug_switch(vlgp_ctx* ctx, const char* name, double* value);
 /* Counters of the H-step objective calls since the handle was created: out[0] evaluations that took the low-rank round,
  * out[1] the sum of their predicted ranks (even + odd block), out[2] evaluations that took the dense round,
  * out[3] low-rank rounds re-run densely because a rank exceeded the prediction. */

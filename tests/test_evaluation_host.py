@@ -17,8 +17,8 @@ def test_header_declares_and_binding_binds_the_evaluation_entry_points():
     text = open(os.path.join(ROOT, "include", "vlgp_hip.h")).read()
     assert re.search(r"int vlgp_replicate_units\(vlgp_ctx\* ctx, int src, int dst, int n_rep, const int\* channel\);", text)
     assert re.search(r"int vlgp_loglik\(vlgp_ctx\* ctx, int set, int vb, double\* rate, double\* sums\);", text)
-    assert int(re.search(r"#define VLGP_ABI_VERSION (\d+)", text).group(1)) == 2
-    assert _lib.ABI_VERSION == 2
+    assert int(re.search(r"#define VLGP_ABI_VERSION (\d+)", text).group(1)) == 3
+    assert _lib.ABI_VERSION == 3
     assert "vlgp_replicate_units" in _lib.EXPORTS and "vlgp_loglik" in _lib.EXPORTS
 
 

@@ -33,7 +33,7 @@ def estep_path(request, monkeypatch):
     """Both dispatch paths of the short-unit E-step, every run: the size-based default (persistent kernels on
     fixture-sized sets) and the split E-step (estep_split.hip: the chip-wide launch sequence that takes over at
     more than 512 units -- the kernels the headline number is made of) forced onto the same inputs.
-    VLGP_ESTEP_SPLIT is read per call by launch_estep_split."""
+    The library reads its switches when a handle is created: the engines of these tests are created after this fixture ran."""
     if request.param == "split":
         monkeypatch.setenv("VLGP_ESTEP_SPLIT", "1")
         monkeypatch.setenv("VLGP_ESTEP_LSPLIT", "1")   # long units: one workgroup per (unit, latent) task
@@ -41,6 +41,13 @@ def estep_path(request, monkeypatch):
         monkeypatch.delenv("VLGP_ESTEP_SPLIT", raising=False)
         monkeypatch.delenv("VLGP_ESTEP_LSPLIT", raising=False)
     return request.param
+
+
+def _handle_holds(V, name, value):
+    """A handle created in the present environment -- as the temporary engines of V.estep / V.mstep are -- holds `value`
+    for the library switch `name`: the toggle of a test that compares two settings took."""
+    with V.Engine(4, 2, 1, 50) as eng:
+        assert eng.switch(name) == value, (name, eng.switch(name), value)
 
 
 def _ran(V, path, *calls):
@@ -136,6 +143,7 @@ def test_ichol_one_wave_kernel_equals_block_kernel_and_oracle_bitwise(V, monkeyp
                 if block:
                     monkeypatch.setenv("VLGP_ICHOL_BLOCK", "1")
                 with V.Engine(4, 3, 1, R) as eng:
+                    assert eng.switch("VLGP_ICHOL_BLOCK") == float(block)
                     eng.build_prior([T], om, sg)
                     got.append(eng.get_prior(T, with_rank=True))
                 monkeypatch.delenv("VLGP_ICHOL_BLOCK", raising=False)
@@ -144,6 +152,63 @@ def test_ichol_one_wave_kernel_equals_block_kernel_and_oracle_bitwise(V, monkeyp
                 Go = O.ichol_gauss(T, om[l], R) * sg[l]
                 assert np.array_equal(got[0][0][l], Go), (T, R, om[l])
                 assert got[0][1][l] == int((np.abs(Go).sum(0) > 0).sum())
+
+
+def test_switches_are_validated_reloaded_and_readable(V, monkeypatch):
+    """The library's switch table on a live handle: an out-of-range or malformed value falls back to the default (and is
+    reported on stderr), a valid one is held after vlgp_debug_reload_switches, an unset one returns to its default; one
+    integer (VLGP_NORMS_BLOCKS, 1 ... 1024), one real (VLGP_HSTEP_LR_TOL, > 0), one flag (VLGP_ESTEP_GENERIC).
+    VLGP_NORMS_BLOCKS=4096 used to let norms_kernel write its partial sums over its ticket word and past the buffer: now
+    the default grid runs, and the two norms are the default's to 1e-14 relative (two sums of squares of doubles; the
+    summation order follows the block count, hence not bit for bit at a VALID other count)."""
+    for name in ("VLGP_NORMS_BLOCKS", "VLGP_HSTEP_LR_TOL", "VLGP_ESTEP_GENERIC"):
+        monkeypatch.delenv(name, raising=False)
+    rng = np.random.default_rng(8)
+    units, params, gauss = _random_problem(rng, [50] * 400, 12, 3, 1, 0)  # 60 000 values: 59 blocks of 1024
+    with V.Engine(12, 3, 1, 50) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(0, units)
+        eng.set_prior(50, params["cholesky"][50])
+        eng.estep(0, 2)  # (a dmu to sum)
+
+        def norms():
+            eng.norms_begin(0)
+            return np.array(eng.norms_end())
+
+        def setting(name, value):
+            if value is None:
+                monkeypatch.delenv(name, raising=False)
+            else:
+                monkeypatch.setenv(name, value)
+            eng.reload_switches()
+            return eng.switch(name)
+
+        assert eng.switch("VLGP_NORMS_BLOCKS") == 256 and eng.switch("VLGP_HSTEP_LR_TOL") == 1e-12
+        assert eng.switch("VLGP_ESTEP_GENERIC") == 0
+        ref = norms()
+        assert np.all(ref > 0)
+        for bad in ("4096", "0", "-3", "12abc", ""):
+            assert setting("VLGP_NORMS_BLOCKS", bad) == 256, bad
+        assert setting("VLGP_NORMS_BLOCKS", "4096") == 256
+        got = norms()
+        assert np.all(np.abs(got - ref) <= 1e-14 * ref), (got, ref)
+        assert setting("VLGP_NORMS_BLOCKS", "7") == 7
+        got = norms()
+        assert np.all(np.abs(got - ref) <= 1e-14 * ref), (got, ref)
+        assert setting("VLGP_NORMS_BLOCKS", "1024") == 1024
+        assert setting("VLGP_NORMS_BLOCKS", None) == 256
+        for bad in ("0", "-1e-9", "nan", "tight"):
+            assert setting("VLGP_HSTEP_LR_TOL", bad) == 1e-12, bad
+        assert setting("VLGP_HSTEP_LR_TOL", "1e-10") == 1e-10
+        assert setting("VLGP_HSTEP_LR_TOL", None) == 1e-12
+        assert setting("VLGP_ESTEP_GENERIC", "1") == 1
+        eng.estep(0, 1)
+        assert eng.last_estep_path == "generic"
+        assert setting("VLGP_ESTEP_GENERIC", None) == 0
+        eng.estep(0, 1)
+        assert eng.last_estep_path != "generic"
+        with pytest.raises(V.VlgpError, match="unknown switch"):
+            eng.switch("VLGP_NO_SUCH_SWITCH")
 
 
 def test_iteration_tail_entry_points(V):
@@ -438,8 +503,10 @@ def test_estep_mixed_rank_launches_vs_oracle(V, omegas, mixed, rerouted, estep_p
         for k, r in zip(("mu", "v", "w", "dmu"), ref):
             assert relerr(u[k], r) < STAGE, k
     if estep_path == "split" and (mixed or rerouted):
+        _handle_holds(V, "VLGP_ESTEP_MIX", -1.0)
         os.environ["VLGP_ESTEP_MIX"] = "0"
         try:
+            _handle_holds(V, "VLGP_ESTEP_MIX", 0.0)
             V.estep(units0, params, V.get_config(Eniter=4))
             assert E.TRACE["estep"] == "split"
         finally:
@@ -507,12 +574,14 @@ def test_noise_from_sufficient_statistics_vs_two_passes_and_oracle(V, L, P, gene
     (1e-12), both with the oracle (1e-9), a / b bit for bit; regressors and the loop-based kernels included."""
     if generic:
         monkeypatch.setenv("VLGP_MSTEP_GENERIC", "1")
+    _handle_holds(V, "VLGP_MSTEP_GENERIC", float(generic))
     out = []
     for passes in (False, True):
         rng = np.random.default_rng(300 + L + P)
         units, params, gauss = _random_problem(rng, [50, 120, 64, 50, 50, 77], 45, L, P, 0)
         if passes:
             monkeypatch.setenv("VLGP_NOISE_PASSES", "1")
+        _handle_holds(V, "VLGP_NOISE_PASSES", float(passes))
         cat = lambda k: np.concatenate([u[k] for u in units], axis=0)
         want = O.mstep_arrays(cat("y"), cat("x"), cat("mu"), cat("v"), params["a"], params["b"], gauss, 4)
         V.mstep(units, params, V.get_config(Mniter=4))
@@ -528,6 +597,7 @@ def test_mstep_golden_through_the_loop_based_kernels(V, golden, tag, monkeypatch
     """The M-step fallback for more than 16 latents / 8 regressors (mstep_cache_gen, mstep_accum_gen, latent_moments_gen,
     Newton systems in global memory), forced at the golden sizes: same reference fixtures, same tolerance."""
     monkeypatch.setenv("VLGP_MSTEP_GENERIC", "1")
+    _handle_holds(V, "VLGP_MSTEP_GENERIC", 1.0)
     for key in ("H_25", "G_1"):
         test_mstep_golden(V, golden, tag, key)
 
@@ -979,8 +1049,9 @@ def test_headline_size_properties(V, monkeypatch):
     y = np.concatenate([t["y"] for t in trials]).reshape(4000, 50, N)
     mu = 0.2 * rng.standard_normal((4000, 50, L))
 
-    def run(order, splits):
+    def run(order, splits, lanes=0):
         with V.Engine(N, L, 1, 50) as eng:
+            assert eng.switch("VLGP_ESTEP_LANES") == lanes  # (0: unset, the lanes follow the set's size)
             eng.set_params(a, b, np.ones(N))
             eng.upload(0, [{"y": y[i], "mu": mu[i]} for i in order])
             eng.build_prior([50], omega, np.ones(L))
@@ -1000,7 +1071,7 @@ def test_headline_size_properties(V, monkeypatch):
         assert np.array_equal(one[k], two[k]), k
     # the two lanes (streams) the unit set runs on by default change nothing: one lane, bit for bit
     monkeypatch.setenv("VLGP_ESTEP_LANES", "1")
-    lane1, _ = run(ident, [25])
+    lane1, _ = run(ident, [25], lanes=1)
     monkeypatch.delenv("VLGP_ESTEP_LANES")
     for k in ("mu", "v", "w", "dmu"):
         assert np.array_equal(one[k], lane1[k]), k

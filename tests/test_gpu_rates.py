@@ -320,6 +320,8 @@ def test_mstep_per_channel_over_nine_decades_of_rate(V, generic, monkeypatch):
         monkeypatch.setenv("VLGP_MSTEP_GENERIC", "1")
     else:
         monkeypatch.delenv("VLGP_MSTEP_GENERIC", raising=False)
+    with V.Engine(4, 2, 1, 50) as probe:  # a handle created now, as V.mstep's is, holds the setting
+        assert probe.switch("VLGP_MSTEP_GENERIC") == float(generic)
     y, mu, v, a0, b0, _ = mstep_spread_problem()
     T, N, L = 50, y.shape[1], mu.shape[1]
     x = np.ones((y.shape[0], 1, N))

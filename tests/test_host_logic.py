@@ -30,6 +30,62 @@ def test_library_exports_every_header_symbol():
     assert lib.vlgp_abi_version() == _lib.ABI_VERSION
 
 
+CSRC = os.path.join(ROOT, "vlgp_amd", "csrc")
+TRANSPORT_SETTINGS = {"VLGP_COMM_TRANSPORT", "VLGP_SHM_TIMEOUT_S", "VLGP_FORCE_RCCL", "VLGP_NO_HOST_EXCHANGE"}
+
+
+def _switch_table():
+    """Names in the one table of library-side debug switches (VLGP_SWITCHES, csrc/ctx.h)."""
+    text = open(os.path.join(CSRC, "ctx.h")).read()
+    body = text[text.index("#define VLGP_SWITCHES(X)"):text.index("#define VLGP_SW_T_FLAG")]
+    return re.findall(r'X\("(VLGP_[A-Z0-9_]+)"', body)
+
+
+def test_the_environment_is_read_by_the_switch_reader_and_the_communicator_only():
+    """One lifetime for every library-side switch: vlgp_read_switches (create, reload) is the only reader.  The only
+    other getenv calls name the transport settings the communicator set-up shares with dist.py."""
+    reader_calls = 0
+    for f in sorted(os.listdir(CSRC)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        src = open(os.path.join(CSRC, f)).read()
+        for m in re.finditer(r"getenv\s*\(([^)]*)\)", src):
+            arg = m.group(1).strip()
+            if f == "api.hip" and arg == "name":
+                reader_calls += 1
+                continue
+            assert arg.strip('"') in TRANSPORT_SETTINGS and f == "api.hip", (f, m.group(0))
+    assert reader_calls == 1
+    api = open(os.path.join(CSRC, "api.hip")).read()
+    reader = api[api.index("static double read_switch("):api.index("void vlgp_read_switches(")]
+    assert "getenv(name)" in reader
+    callers = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))
+               and re.search(r"vlgp_read_switches\(ctx\);", open(os.path.join(CSRC, f)).read())]
+    assert callers == ["api.hip"] and api.count("vlgp_read_switches(ctx);") == 2  # vlgp_create and the reload
+
+
+def test_design_lists_exactly_the_switches_of_the_table():
+    names = _switch_table()
+    assert len(names) == len(set(names)) >= 20
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = design[design.index("## 7. Limits, switches"):design.index("## 8. Out of scope")]
+    listed = sec[sec.index("<!-- library switches"):sec.index("<!-- end of library switches -->")]
+    lines = [ln for ln in listed.splitlines() if ln.startswith("- ")]
+    in_design = [re.match(r"- `(VLGP_[A-Z0-9_]+)`", ln).group(1) for ln in lines]  # one line each
+    assert sorted(in_design) == sorted(names), set(in_design) ^ set(names)
+    assert set(re.findall(r"VLGP_[A-Z0-9_]+", listed)) == set(names)
+    # the rest of the section names no library switch that the table lacks: only the Python layer's and the transport's
+    others = set(re.findall(r"VLGP_[A-Z0-9_]+", sec)) - set(names)
+    python_side = {"VLGP_LBFGSB", "VLGP_LBFGSB_BLAS", "VLGP_LOCKSTEP_PYTHON", "VLGP_M_SEQUENTIAL", "VLGP_LIB_PATH",
+                   "VLGP_DEVICE", "VLGP_RENDEZVOUS_DIR"}
+    assert others <= python_side | TRANSPORT_SETTINGS, others
+
+
+def test_split_estep_has_no_thread_local_state():
+    src = open(os.path.join(CSRC, "estep_split.hip")).read()
+    assert "thread_local" not in src and "NEED_LANE" not in src
+
+
 def test_no_gpu_fails_loudly():
     import vlgp_amd
     from vlgp_amd import _lib

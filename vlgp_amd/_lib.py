@@ -15,7 +15,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlgp_hip.so")
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 MAX_SETS = 4
 UNIQUE_ID_BYTES = 128
 PROF_ESTEP, PROF_MSTEP, PROF_HSTEP, PROF_PRIOR = 0, 1, 2, 3
@@ -98,6 +98,7 @@ _SIGNATURES = {
     "vlgp_debug_last_estep_path": (C.c_int, [_h, _ip]),
     "vlgp_debug_last_hstep_path": (C.c_int, [_h, _ip]),
     "vlgp_debug_reload_switches": (C.c_int, [_h]),
+    "vlgp_debug_switch": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "vlgp_debug_hstep_stats": (C.c_int, [_h, _dp]),
 }
 EXPORTS = tuple(_SIGNATURES)

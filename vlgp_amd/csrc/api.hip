@@ -1657,21 +1657,48 @@ extern "C" int vlgp_debug_last_estep_path(vlgp_ctx* ctx, int* path) {
     return VLGP_OK;
 }
 
+// One value of the table VLGP_SWITCHES (ctx.h) from the environment; `warned`: that switch was reported already.
+enum SwKind { SW_FLAG, SW_TRI, SW_INT, SW_REAL };
+static double read_switch(const char* name, SwKind kind, double def, double lo, double hi, bool* warned) {
+    const char* s = getenv(name);
+    if (kind == SW_FLAG) return s != nullptr;
+    if (!s) return def;
+    if (kind == SW_TRI && (s[0] == '0' || s[0] == '1')) return s[0] - '0';
+    if (kind == SW_INT || kind == SW_REAL) {
+        char* end = nullptr;
+        const double v = kind == SW_INT ? (double)strtol(s, &end, 10) : strtod(s, &end);
+        if (end != s && *end == '\0' && (kind == SW_INT ? v >= lo : v > lo) && v <= hi) return v;
+    }
+    if (!*warned) fprintf(stderr, "vlgp: %s=\"%s\" is malformed or out of range: the default holds\n", name, s);
+    *warned = true;
+    return def;
+}
+
 void vlgp_read_switches(vlgp_ctx* ctx) {
-    HstepSwitches& w = ctx->hsw;
-    w.dense = getenv("VLGP_HSTEP_DENSE") != nullptr;
-    w.generic = getenv("VLGP_HSTEP_GENERIC") != nullptr;
-    w.lowrank = getenv("VLGP_HSTEP_LOWRANK") != nullptr;
-    w.generic_seg = getenv("VLGP_HSTEP_GENERIC_SEG") != nullptr;
-    w.debug_occ = getenv("VLGP_DEBUG_OCC") != nullptr;
-    w.fuse_tables = getenv("VLGP_HSTEP_FUSE_TABLES") != nullptr;
-    w.lr_tol = getenv("VLGP_HSTEP_LR_TOL") ? atof(getenv("VLGP_HSTEP_LR_TOL")) : 1e-12;
+    Switches& w = ctx->sw;
+#define X(name, field, kind, def, lo, hi, what)                                                        \
+    {                                                                                                  \
+        static bool warned = false;                                                                    \
+        w.field = (VLGP_SW_T_##kind)read_switch(name, SW_##kind, (double)(def), (double)(lo), (double)(hi), &warned); \
+    }
+    VLGP_SWITCHES(X)
+#undef X
 }
 
 extern "C" int vlgp_debug_reload_switches(vlgp_ctx* ctx) {
     NEED_CTX(ctx);
     vlgp_read_switches(ctx);
     return VLGP_OK;
+}
+
+extern "C" int vlgp_debug_switch(vlgp_ctx* ctx, const char* name, double* value) {
+    NEED_CTX(ctx);
+    if (!name || !value) return vlgp_fail(ctx, VLGP_ERR_ARG, "null switch name or value");
+#define X(sname, field, kind, def, lo, hi, what) \
+    if (!strcmp(name, sname)) { *value = (double)ctx->sw.field; return VLGP_OK; }
+    VLGP_SWITCHES(X)
+#undef X
+    return vlgp_fail(ctx, VLGP_ERR_ARG, "unknown switch %s", name);
 }
 
 extern "C" int vlgp_debug_last_hstep_path(vlgp_ctx* ctx, int* path) {

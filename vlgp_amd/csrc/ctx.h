@@ -68,12 +68,45 @@ struct UnitSet {
     int rep_users = 0;
 };
 
-// Debug / test switches of the H-step dispatch (environment VLGP_HSTEP_*, VLGP_DEBUG_OCC), read ONCE when the handle is
-// created and again on vlgp_debug_reload_switches: the objective call itself -- ~40 times per EM iteration, on the
-// optimiser's critical path -- reads this struct, not the environment.
-struct HstepSwitches {
-    bool dense = false, generic = false, lowrank = false, generic_seg = false, debug_occ = false, fuse_tables = false;
-    double lr_tol = 1e-12;
+// Every debug / test switch the library reads from the environment, ONE table: X(name, field, kind, default, lo, hi, what).
+// Kinds: FLAG  on when the variable is set, whatever its value;
+//        TRI   -1 unset, 0 / 1 by the first character of the value;
+//        INT   lo <= value <= hi;   REAL  lo < value <= hi.
+// A malformed or out-of-range value is reported on stderr (once per switch) and the default holds.  One lifetime for
+// all of them: vlgp_read_switches fills vlgp_ctx::sw when the handle is created and again on
+// vlgp_debug_reload_switches; nothing else reads the environment (the communicator set-up apart): no launch pays for it.
+#define VLGP_SWITCHES(X)                                                                                                 \
+    X("VLGP_ESTEP_SPLIT", estep_split, TRI, -1, 0, 1, "split E-step (chip-wide launches per phase): 0 never, 1 whatever the set's size") \
+    X("VLGP_ESTEP_LSPLIT", estep_lsplit, TRI, -1, 0, 1, "long units (T > 64) on the split E-step: 0 never, 1 below 128 tasks too") \
+    X("VLGP_ESTEP_GENERIC", estep_generic, FLAG, false, 0, 1, "E-step: the generic kernels only (a replicated set keeps the split E-step)") \
+    X("VLGP_ESTEP_LANEPT", estep_lanept, TRI, -1, 0, 1, "split E-step: 0 keeps the wave-per-task kernels for ranks <= 14") \
+    X("VLGP_ESTEP_NO_SHARED_G", estep_no_shared_g, FLAG, false, 0, 1, "split E-step: per-wave staging of G in the rank <= 16 launches, no lane-per-task launches") \
+    X("VLGP_ESTEP_MIX", estep_mix, TRI, -1, 0, 1, "split E-step: 0 launches lane-per-task and wave-per-task latents separately") \
+    X("VLGP_ESTEP_LANES", estep_lanes, INT, 0, 1, VLGP_E_LANES, "split E-step: number of stream lanes (default: by set size, one or two)") \
+    X("VLGP_LANE_PRIO", lane_prio, INT, 0, 0, 3, "instruction priority of the lane-per-task launches' waves")                \
+    X("VLGP_LANE_CLOCK", lane_clock, INT, 0, 0, 2, "phase clock of the lane-per-task launches: 1 factor, 2 mean (vlgp_debug_phase_clock)") \
+    X("VLGP_MSTEP_GENERIC", mstep_generic, FLAG, false, 0, 1, "M-step: the loop-based kernels at any size")                    \
+    X("VLGP_MSTEP_WG_PER_CU", mstep_wg_per_cu, REAL, 1.0, 0.0, 1e300, "M-step accumulation: workgroups per compute unit")       \
+    X("VLGP_NOISE_PASSES", noise_passes, FLAG, false, 0, 1, "M-step: the noise variance by two passes over the rows, not from the moments") \
+    X("VLGP_NO_MGRAPH", no_mgraph, FLAG, false, 0, 1, "M-step: enqueue every launch instead of replaying the captured graph") \
+    X("VLGP_ICHOL_BLOCK", ichol_block, FLAG, false, 0, 1, "prior factor: lengths <= 64 through the workgroup kernel of the long ones") \
+    X("VLGP_NORMS_BLOCKS", norms_blocks, INT, 256, 1, 1024, "norms pass: largest number of workgroups (its partial sums have 1024 slots)") \
+    X("VLGP_HSTEP_DENSE", hstep_dense, FLAG, false, 0, 1, "H-step: the dense matrix-pipe round, never the low-rank one")     \
+    X("VLGP_HSTEP_GENERIC", hstep_generic, FLAG, false, 0, 1, "H-step: the generic kernels (the reference's omega retry)")     \
+    X("VLGP_HSTEP_LOWRANK", hstep_lowrank, FLAG, false, 0, 1, "H-step: the low-rank round whatever the size rule says")        \
+    X("VLGP_HSTEP_GENERIC_SEG", hstep_generic_seg, FLAG, false, 0, 1, "H-step: windows 65 ... 128 on the generic kernels")     \
+    X("VLGP_HSTEP_FUSE_TABLES", hstep_fuse_tables, FLAG, false, 0, 1, "H-step: every low-rank round workgroup factors its kernel blocks itself (rejected: slower)") \
+    X("VLGP_HSTEP_NO_WLM", hstep_no_wlm, FLAG, false, 0, 1, "H-step: the rounds read w row-major, no latent-major copy")       \
+    X("VLGP_HSTEP_LR_TOL", hstep_lr_tol, REAL, 1e-12, 0.0, 1e300, "H-step: relative tolerance of the low-rank round's rank prediction") \
+    X("VLGP_DEBUG_OCC", debug_occ, FLAG, false, 0, 1, "print occupancy of the fast E-step launch and the H-step's fall-backs on stderr")
+#define VLGP_SW_T_FLAG bool
+#define VLGP_SW_T_TRI int
+#define VLGP_SW_T_INT int
+#define VLGP_SW_T_REAL double
+struct Switches {
+#define X(name, field, kind, def, lo, hi, what) VLGP_SW_T_##kind field = def;
+    VLGP_SWITCHES(X)
+#undef X
 };
 void vlgp_read_switches(struct vlgp_ctx* ctx);
 
@@ -153,7 +186,7 @@ struct vlgp_ctx {
     // low-rank H-step round (hstep_lr.h): per (window, dt, tol) the largest omega whose folded kernel blocks have rank <= r
     struct LrThr { int T; double dt, tol; std::vector<double> om; };
     std::vector<LrThr> lr_thr;
-    HstepSwitches hsw;
+    Switches sw;                  // the environment's switches as read at create / reload (VLGP_SWITCHES)
     std::vector<const void*> lds_attr_done;  // kernels whose dynamic-LDS ceiling was raised on this handle's device
     // instruction priority of the round kernels' waves beside the M-step lane: high while the H-step bracket is the longer
     // of the two (durations of the previous EM iteration; hstep.hip, hstep_wave_prio)

@@ -435,21 +435,9 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
         CHK(vlgp_refresh_xb(ctx, us));
     }
 
-    // LDS demand over the priors this set uses
-    int64_t gsz = 0, lcsz = 0;
-    for (auto& kv : ctx->priors) {
-        const Prior& pr = kv.second;
-        if (!need_prior || pr.T < us.Tmin || pr.T > us.Tmax) continue;
-        int64_t g = 0, lc = 0;
-        for (int l = 0; l < L; ++l) {
-            g += (int64_t)pr.T * (pr.rl[l] | 1);
-            lc += (int64_t)pr.rl[l] * (pr.rl[l] | 1);
-        }
-        gsz = g > gsz ? g : gsz;
-        lcsz = lc > lcsz ? lc : lcsz;
-    }
-    gsz = (gsz + 1) & ~1LL;
-    lcsz = (lcsz + 1) & ~1LL;
+    // ranks and LDS demands over the priors this set uses
+    const RankSummary rs = need_prior ? estep_rank_summary(ctx, us) : RankSummary();
+    const int64_t gsz = rs.g_odd, lcsz = rs.lc_odd;
 
     const int64_t LDS_MAX = 160 * 1024;
     const int LTl = L <= 2 ? 2 : (L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : (L <= 10 ? 10 : (L <= 16 ? 16 : (L <= 32 ? 32 : 64))))));  // as launch_l dispatches
@@ -473,7 +461,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     // SPLIT: many short units -> chip-wide launches per phase (estep_split.hip); declines for small sets
     {
         int handled = 0;
-        CHK(launch_estep_split(ctx, us, A, &handled));
+        CHK(launch_estep_split(ctx, us, A, rs, &handled));
         if (handled) { ctx->last_estep_path = handled == 2 ? VLGP_PATH_ESTEP_LSPLIT : (handled == 3 ? VLGP_PATH_ESTEP_SPLIT_MIXED : VLGP_PATH_ESTEP_SPLIT); return VLGP_OK; }
         if (us.rep_src >= 0)
             return vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: only the split E-step leaves a channel out, and it declined");
@@ -482,7 +470,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     // FAST: register-resident factorisations (estep_fast.hip); declines when it does not apply
     {
         int handled = 0;
-        CHK(launch_estep_fast(ctx, us, A, &handled));
+        CHK(launch_estep_fast(ctx, us, A, rs, &handled));
         if (handled) { ctx->last_estep_path = VLGP_PATH_ESTEP_FAST; return VLGP_OK; }
     }
 

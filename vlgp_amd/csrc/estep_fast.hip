@@ -537,7 +537,7 @@ static int launch_fast_t(vlgp_ctx* ctx, const EstepArgs& A, int M, int nthr, siz
     if (lds > 64 * 1024)
         HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (getenv("VLGP_DEBUG_OCC")) {
+    if (ctx->sw.debug_occ) {
         int nb = -1;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, nthr, lds);
         fprintf(stderr, "estep_fast<%d,%d,%d>: %d threads, %zu B LDS -> %d blocks per CU\n", LT, RP, RA, nthr, lds, nb);
@@ -559,32 +559,19 @@ static int launch_fast_l(vlgp_ctx* ctx, const EstepArgs& A, int M, int nthr, siz
     return vlgp_fail(ctx, VLGP_ERR_STATE, "no fast E-step instantiation for %d latents at this rank", A.L);
 }
 
-int launch_estep_fast(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled) {
+int launch_estep_fast(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, const RankSummary& rs, int* handled) {
     *handled = 0;
     const int N = ctx->N, L = ctx->L;
-    if (getenv("VLGP_ESTEP_GENERIC")) return VLGP_OK;
+    if (ctx->sw.estep_generic) return VLGP_OK;
     if (us.Tmax > 64 || L > 10) return VLGP_OK;
-    const bool need_prior = (A.mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
-    int rmax = 0;
-    int64_t gsz = 0;
-    if (need_prior) {
-        for (auto& kv : ctx->priors) {
-            const Prior& pr = kv.second;
-            if (pr.T < us.Tmin || pr.T > us.Tmax) continue;
-            int64_t g = 0;
-            for (int l = 0; l < L; ++l) {
-                rmax = pr.rl[l] > rmax ? pr.rl[l] : rmax;
-                g += (int64_t)pr.T * ((pr.rl[l] + 1) & ~1);
-            }
-            gsz = g > gsz ? g : gsz;
-        }
-    }
+    const int rmax = rs.rmax;
+    const int64_t gsz = rs.g_even;
     if (rmax > 32 || (L > 8 && rmax > 16)) return VLGP_OK;  // nine or ten latents: only the rank <= 16 instantiation
     const int RP = rmax <= 16 ? 16 : 32;
     const int LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
     const int nw = L < 4 ? 4 : L;  // L <= 8
     const int Tc = us.Tmax;
-    const int RA = rmax <= 16 ? 16 : (rmax <= 24 && !getenv("VLGP_ESTEP_NO_RA24") ? 24 : 32);
+    const int RA = rmax <= 16 ? 16 : (rmax <= 24 ? 24 : 32);
     const int64_t PK = tri_packed_size(RA);
     int64_t scr = (int64_t)nw * Tc * L;                       // partial sums of the passes
     if (scr < (int64_t)nw * 256) scr = (int64_t)nw * 256;     // 16 x 16 MFMA staging tiles

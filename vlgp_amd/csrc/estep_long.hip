@@ -548,7 +548,7 @@ int launch_long_t(vlgp_ctx* ctx, const EstepArgs& A, int M, size_t lds) {
 int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled) {
     *handled = 0;
     const int N = ctx->N, L = ctx->L;
-    if (ctx->R > RPL || L > 10 || getenv("VLGP_ESTEP_GENERIC")) return VLGP_OK;
+    if (ctx->R > RPL || L > 10 || ctx->sw.estep_generic) return VLGP_OK;
     const int LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
     const int64_t doubles = 2LL * LT * N + 2LL * N + ((L + 1) & ~1) + 2LL * L * 64 + (int64_t)L * PKL;
     const int64_t ints = ((int64_t)N + 3 * L + 1) / 2 + 1;

@@ -266,72 +266,58 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
 // CS: the channels of one row group are split over CS waves of the workgroup (a lone wave walking all N channels
 // is a chain of N dependent record loads + exponentials: measured 35 us at two waves per SIMD and 41 us at four --
 // latency, not throughput); the partial sums meet in LDS and are added in wave order (deterministic).
-// RPL: rows per lane (rows row0 + 64 q): one channel record serves RPL rows -- fewer scalar loads per (row, channel)
-// and RPL independent exp chains per record.
-template <int LT, int KIND, bool HASXB, int CS, int RPL, bool EXCL = false>
+template <int LT, int KIND, bool HASXB, int CS, bool EXCL = false>
 __global__ void __launch_bounds__(256)
 esplit_pass(SplitArgs A, const double* __restrict__ cols) {
     constexpr int REC = rec_len<LT>();
-    constexpr int RPB = (256 / CS) * RPL;  // rows per workgroup
+    constexpr int RPB = 256 / CS;  // rows per workgroup
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int part = CS == 1 ? 0 : wid % CS;
-    const int64_t row0 = (int64_t)blockIdx.x * RPB + (wid / CS) * (64 * RPL) + lane;
+    const int64_t row0 = (int64_t)blockIdx.x * RPB + (wid / CS) * 64 + lane;
     __shared__ double etab[256];  // 2^(j/256) for fast_exp_tab256
     if constexpr (KIND != SP_YA) {
         fast_exp_tab256_init(etab, threadIdx.x);
         __syncthreads();
     }
     const int N = A.N, L = A.L;
-    bool in[RPL];
-    int64_t rr[RPL];
-    double mr[RPL][LT], vr[RPL][LT], acc[RPL][LT];
-    const double* yrow[RPL];
-    const double* xbrow[RPL];
+    const bool in = row0 < A.rows;
+    const int64_t rr = in ? row0 : 0;
+    double mr[LT], vr[LT], acc[LT];
 #pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-        in[q] = row0 + 64 * q < A.rows;
-        rr[q] = in[q] ? row0 + 64 * q : 0;
-#pragma unroll
-        for (int l = 0; l < LT; ++l) {
-            const bool use = l < L && KIND != SP_YA;
-            mr[q][l] = use ? A.mu[(int64_t)l * A.ld + rr[q]] : 0.0;
-            vr[q][l] = use ? A.v[(int64_t)l * A.ld + rr[q]] : 0.0;
-            acc[q][l] = 0.0;
-        }
-        yrow[q] = A.y + rr[q] * N;
-        xbrow[q] = HASXB ? A.xb + rr[q] * N : nullptr;
+    for (int l = 0; l < LT; ++l) {
+        const bool use = l < L && KIND != SP_YA;
+        mr[l] = use ? A.mu[(int64_t)l * A.ld + rr] : 0.0;
+        vr[l] = use ? A.v[(int64_t)l * A.ld + rr] : 0.0;
+        acc[l] = 0.0;
     }
-    int ex[RPL], rk[RPL];  // EXCL: replica of each row and the channel it leaves out
+    const double* yrow = A.y + rr * N;
+    const double* xbrow = HASXB ? A.xb + rr * N : nullptr;
+    int ex = 0, rk = 0;  // EXCL: replica of the row and the channel it leaves out
     ExclArgs X;
     if constexpr (EXCL) {
         X = *A.excl;
         X.row_base = A.mu - X.mu_lm;
-#pragma unroll
-        for (int q = 0; q < RPL; ++q) {
-            const int64_t ar = X.row_base + rr[q], k = ar / X.rows_src, sr = ar - k * X.rows_src;
-            rk[q] = (int)k;
-            ex[q] = X.ch[k];
-            yrow[q] = X.y + sr * N;
-            xbrow[q] = HASXB ? X.xb + sr * N : nullptr;
-        }
+        const int64_t ar = X.row_base + rr, k = ar / X.rows_src, sr = ar - k * X.rows_src;
+        rk = (int)k;
+        ex = X.ch[k];
+        yrow = X.y + sr * N;
+        xbrow = HASXB ? X.xb + sr * N : nullptr;
     }
-    // entry i < 2 LT of a channel record as row q sees it: 0 for the channel its replica leaves out (EXCL)
-    auto rec = [&](const double (&rv)[REC], int q, int i) -> double {
-        if constexpr (EXCL) return (int)__double_as_longlong(rv[2 * LT + 2]) == ex[q] ? 0.0 : rv[i];
+    // entry i < 2 LT of a channel record as the row sees it: 0 for the channel its replica leaves out (EXCL)
+    auto rec = [&](const double (&rv)[REC], int i) -> double {
+        if constexpr (EXCL) return (int)__double_as_longlong(rv[2 * LT + 2]) == ex ? 0.0 : rv[i];
         else return rv[i];
     };
     // the residual pass subtracts from ya at the end: fetched here, by the wave that writes (a load after the channel
     // loop is one more trip to memory in the life of a short wave)
-    double yav[RPL][LT], wv[RPL][LT];
+    double yav[LT], wv[LT];
     if constexpr (KIND == SP_RES) {
 #pragma unroll
-        for (int q = 0; q < RPL; ++q)
-#pragma unroll
-            for (int l = 0; l < LT; ++l) {
-                yav[q][l] = (part == 0 && l < L) ? A.ya[(int64_t)l * A.ld + rr[q]] : 0.0;
-                wv[q][l] = (part == 0 && l < L && A.sv) ? A.w[(int64_t)l * A.ld + rr[q]] : 0.0;
-            }
+        for (int l = 0; l < LT; ++l) {
+            yav[l] = (part == 0 && l < L) ? A.ya[(int64_t)l * A.ld + rr] : 0.0;
+            wv[l] = (part == 0 && l < L && A.sv) ? A.w[(int64_t)l * A.ld + rr] : 0.0;
+        }
     }
     if constexpr (KIND == SP_W) {
         // the step of the lane-per-task mean launch, applied here: mu += clip(dl - mu) (core.py:91, 96); every wave of
@@ -339,14 +325,12 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
         // have read the old value by then)
         if (A.dmask) {
 #pragma unroll
-            for (int q = 0; q < RPL; ++q)
-#pragma unroll
-                for (int l = 0; l < LT; ++l)
-                    if (l < L && ((A.dmask >> l) & 1u)) {
-                        double st = A.dl[(int64_t)l * A.ld + rr[q]] - mr[q][l];
-                        st = fmin(fmax(st, -A.dmu_bound), A.dmu_bound);
-                        mr[q][l] += st;
-                    }
+            for (int l = 0; l < LT; ++l)
+                if (l < L && ((A.dmask >> l) & 1u)) {
+                    double st = A.dl[(int64_t)l * A.ld + rr] - mr[l];
+                    st = fmin(fmax(st, -A.dmu_bound), A.dmu_bound);
+                    mr[l] += st;
+                }
         }
     }
     auto load_rec = [&](int i, double (&rv)[REC]) {
@@ -364,12 +348,12 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
     const int g_lo = CS == 1 ? A.np : A.np + ((A.ntot - A.np) * part) / CS;
     const int ntot = CS == 1 ? A.ntot : A.np + ((A.ntot - A.np) * (part + 1)) / CS;
     if constexpr (KIND == SP_YA) {
-        static_assert(CS == 1 && RPL == 1, "the y pass is not split");
+        static_assert(CS == 1, "the y pass is not split");
         auto body = [&](const double (&rv)[REC]) {
             const int n = (int)__double_as_longlong(rv[2 * LT + 2]);
-            const double yc = yrow[0][n] * rv[2 * LT + 1];
+            const double yc = yrow[n] * rv[2 * LT + 1];
 #pragma unroll
-            for (int l = 0; l < LT; ++l) acc[0][l] = fma(yc, rec(rv, 0, l), acc[0][l]);
+            for (int l = 0; l < LT; ++l) acc[l] = fma(yc, rec(rv, l), acc[l]);
         };
         double ra_[REC], rb_[REC];
         load_rec(0, ra_);
@@ -384,17 +368,14 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
     } else {
         // one Poisson channel: rate = exp(min(eta + v.a^2/2, 10)) (math.trunc_exp, vlgp/math.py:24-38)
         auto poisson = [&](const double (&rv)[REC]) {
+            double eta = HASXB ? xbrow[(int)__double_as_longlong(rv[2 * LT + 2])] : rv[2 * LT];
 #pragma unroll
-            for (int q = 0; q < RPL; ++q) {
-                double eta = HASXB ? xbrow[q][(int)__double_as_longlong(rv[2 * LT + 2])] : rv[2 * LT];
+            for (int l = 0; l < LT; ++l) eta = fma(mr[l], rec(rv, l), eta);
 #pragma unroll
-                for (int l = 0; l < LT; ++l) eta = fma(mr[q][l], rec(rv, q, l), eta);
+            for (int l = 0; l < LT; ++l) eta = fma(vr[l], rec(rv, LT + l), eta);
+            const double rate = trunc_exp_tab256(eta, etab);
 #pragma unroll
-                for (int l = 0; l < LT; ++l) eta = fma(vr[q][l], rec(rv, q, LT + l), eta);
-                const double rate = trunc_exp_tab256(eta, etab);
-#pragma unroll
-                for (int l = 0; l < LT; ++l) acc[q][l] = fma(rate, rec(rv, q, KIND == SP_RES ? l : LT + l), acc[q][l]);
-            }
+            for (int l = 0; l < LT; ++l) acc[l] = fma(rate, rec(rv, KIND == SP_RES ? l : LT + l), acc[l]);
         };
         double ra_[REC], rb_[REC];
         if (np > p_lo) {
@@ -411,54 +392,44 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
         if constexpr (KIND == SP_RES) {  // Gaussian channels: the residual mean is eta itself
             for (int i = g_lo; i < ntot; ++i) {
                 load_rec(i, ra_);
+                double eta = HASXB ? xbrow[(int)__double_as_longlong(ra_[2 * LT + 2])] : ra_[2 * LT];
 #pragma unroll
-                for (int q = 0; q < RPL; ++q) {
-                    double eta = HASXB ? xbrow[q][(int)__double_as_longlong(ra_[2 * LT + 2])] : ra_[2 * LT];
+                for (int l = 0; l < LT; ++l) eta = fma(mr[l], rec(ra_, l), eta);
+                const double mval = eta * ra_[2 * LT + 1];
 #pragma unroll
-                    for (int l = 0; l < LT; ++l) eta = fma(mr[q][l], rec(ra_, q, l), eta);
-                    const double mval = eta * ra_[2 * LT + 1];
-#pragma unroll
-                    for (int l = 0; l < LT; ++l) acc[q][l] = fma(mval, rec(ra_, q, l), acc[q][l]);
-                }
+                for (int l = 0; l < LT; ++l) acc[l] = fma(mval, rec(ra_, l), acc[l]);
             }
         }
     }
     if constexpr (CS > 1) {
-        __shared__ double part_acc[4][RPL][LT][64];
+        __shared__ double part_acc[4][LT][64];
         if (part > 0) {
 #pragma unroll
-            for (int q = 0; q < RPL; ++q)
-#pragma unroll
-                for (int l = 0; l < LT; ++l) part_acc[wid][q][l][lane] = acc[q][l];
+            for (int l = 0; l < LT; ++l) part_acc[wid][l][lane] = acc[l];
         }
         __syncthreads();
         if (part > 0) return;
 #pragma unroll
         for (int p = 1; p < CS; ++p)
 #pragma unroll
-            for (int q = 0; q < RPL; ++q)
-#pragma unroll
-                for (int l = 0; l < LT; ++l) acc[q][l] += part_acc[wid + p][q][l][lane];
+            for (int l = 0; l < LT; ++l) acc[l] += part_acc[wid + p][l][lane];
     }
+    if (in) {
+        const int64_t row = rr;
 #pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-        if (in[q]) {
-            const int64_t row = rr[q];
-#pragma unroll
-            for (int l = 0; l < LT; ++l) {
-                if (l < L) {
-                    if constexpr (KIND == SP_YA) A.ya[(int64_t)l * A.ld + row] = acc[q][l];
-                    else if constexpr (KIND == SP_RES) {
-                        const double rav = yav[q][l] - acc[q][l];
-                        if (A.ra) A.ra[(int64_t)l * A.ld + row] = rav;
-                        if (A.sv) A.sv[(int64_t)l * A.ld + row] = fma(wv[q][l], mr[q][l], rav);
-                    } else {
-                        double wc;
-                        if constexpr (EXCL) wc = X.wconst[rk[q] * 16 + l];
-                        else wc = A.wconst[l];
-                        A.w[(int64_t)l * A.ld + row] = fma(2.0, acc[q][l], wc);  // (the records hold a^2 / 2)
-                        if ((A.dmask >> l) & 1u) A.mu[(int64_t)l * A.ld + row] = mr[q][l];
-                    }
+        for (int l = 0; l < LT; ++l) {
+            if (l < L) {
+                if constexpr (KIND == SP_YA) A.ya[(int64_t)l * A.ld + row] = acc[l];
+                else if constexpr (KIND == SP_RES) {
+                    const double rav = yav[l] - acc[l];
+                    if (A.ra) A.ra[(int64_t)l * A.ld + row] = rav;
+                    if (A.sv) A.sv[(int64_t)l * A.ld + row] = fma(wv[l], mr[l], rav);
+                } else {
+                    double wc;
+                    if constexpr (EXCL) wc = X.wconst[rk * 16 + l];
+                    else wc = A.wconst[l];
+                    A.w[(int64_t)l * A.ld + row] = fma(2.0, acc[l], wc);  // (the records hold a^2 / 2)
+                    if ((A.dmask >> l) & 1u) A.mu[(int64_t)l * A.ld + row] = mr[l];
                 }
             }
         }
@@ -1651,101 +1622,65 @@ __global__ void __launch_bounds__(256, 4) elong_mean(SplitArgs A) {
     }
 }
 
-// the stream the launch helpers below enqueue on: the handle's main stream, or the second E-step lane (the unit set
-// split in two halves that run their sweeps side by side, launch_estep_split)
-static thread_local hipStream_t t_lane = nullptr;
-// (a helper reached without a lane would launch on the legacy null stream without a word)
-#define NEED_LANE(ctx) \
-    do { if (!t_lane) return vlgp_fail(ctx, VLGP_ERR_STATE, "split E-step launch helper called outside launch_estep_split"); } while (0)
-// the replica table of the set the row passes run on (its row_base that of the lane), or null: set beside t_lane
-static thread_local const ExclArgs* t_excl = nullptr;
-static thread_local const ExclArgs* t_excl_dev = nullptr;  // its device copy (the row passes read it through SplitArgs::excl)
+// Where a launch helper enqueues: the stream of its lane (the handle's main stream, or one of the extra lanes the unit
+// set is cut over, launch_estep_split) and, for a replicated set, the replica table the row passes leave a channel out by.
+struct Lane {
+    hipStream_t st;
+    const ExclArgs* excl;      // host copy (an argument of the y pass), or null: a plain set
+    const ExclArgs* excl_dev;  // its device copy (the row passes read it through SplitArgs::excl)
+};
 
-template <int LT, int CS, int RPL, bool EXCL>
-int run_passes_x(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) {
-    constexpr int RPB = (256 / CS) * RPL;
+// one row pass (KIND) with its channels split over CS waves per row group; a replicated set's launch reads the replica table
+template <int LT, int KIND, int CS>
+int run_pass_cs(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const double* cols) {
+    constexpr int RPB = 256 / CS;
     const dim3 grid((unsigned)((A.rows + RPB - 1) / RPB)), blk(256);
-    NEED_LANE(ctx);
-    hipStream_t st = t_lane;
-    if (A.xb) {
-        if (kind == SP_RES) hipLaunchKernelGGL((esplit_pass<LT, SP_RES, true, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
-        else hipLaunchKernelGGL((esplit_pass<LT, SP_W, true, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
+    if (ln.excl) {
+        A.excl = ln.excl_dev;
+        if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, KIND, true, CS, true>), grid, blk, 0, ln.st, A, cols);
+        else hipLaunchKernelGGL((esplit_pass<LT, KIND, false, CS, true>), grid, blk, 0, ln.st, A, cols);
     } else {
-        if (kind == SP_RES) hipLaunchKernelGGL((esplit_pass<LT, SP_RES, false, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
-        else hipLaunchKernelGGL((esplit_pass<LT, SP_W, false, CS, RPL, EXCL>), grid, blk, 0, st, A, cols);
+        if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, KIND, true, CS>), grid, blk, 0, ln.st, A, cols);
+        else hipLaunchKernelGGL((esplit_pass<LT, KIND, false, CS>), grid, blk, 0, ln.st, A, cols);
     }
     HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
 }
 
-template <int LT, int CS, int RPL>
-int run_passes_cs(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) {
-    if constexpr (RPL == 1) {
-        if (t_excl) {
-            SplitArgs Ax = A;
-            Ax.excl = t_excl_dev;
-            return run_passes_x<LT, CS, RPL, true>(ctx, Ax, kind, cols);
-        }
-    }
-    return run_passes_x<LT, CS, RPL, false>(ctx, A, kind, cols);
+// channel split: four waves per row group while a wave keeps >= 16 channels (measured at 200 k rows x 100
+// channels: 39.4 / 34.4 / 32.2 us for 1 / 2 / 4; at 131 k rows 35.9 / 24.8 / 24.6 us); the y pass is not split
+template <int LT, int KIND>
+int run_pass_kind(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, const double* cols) {
+    if (A.ntot >= 64) return run_pass_cs<LT, KIND, 4>(ctx, ln, A, cols);
+    if (A.ntot >= 32) return run_pass_cs<LT, KIND, 2>(ctx, ln, A, cols);
+    return run_pass_cs<LT, KIND, 1>(ctx, ln, A, cols);
 }
 
 template <int LT>
-int run_passes(vlgp_ctx* ctx, const SplitArgs& A, int kind, const double* cols) {
-    NEED_LANE(ctx);
-    if (kind == SP_YA) {
-        const dim3 grid((unsigned)((A.rows + 255) / 256)), blk(256);
-        if (t_excl) {
-            SplitArgs Ax = A;
-            Ax.excl = t_excl_dev;
-            if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, SP_YA, true, 1, 1, true>), grid, blk, 0, t_lane, Ax, cols);
-            else hipLaunchKernelGGL((esplit_pass<LT, SP_YA, false, 1, 1, true>), grid, blk, 0, t_lane, Ax, cols);
-        } else {
-            if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, SP_YA, true, 1, 1>), grid, blk, 0, t_lane, A, cols);
-            else hipLaunchKernelGGL((esplit_pass<LT, SP_YA, false, 1, 1>), grid, blk, 0, t_lane, A, cols);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        return VLGP_OK;
-    }
-    // channel split: four waves per row group while a wave keeps >= 16 channels (measured at 200 k rows x 100
-    // channels: 39.4 / 34.4 / 32.2 us for 1 / 2 / 4; at 131 k rows 35.9 / 24.8 / 24.6 us)
-    static const int forced = getenv("VLGP_PASS_SPLIT") ? atoi(getenv("VLGP_PASS_SPLIT")) : 0;
-    static const int forced_rpl = getenv("VLGP_PASS_RPL") ? atoi(getenv("VLGP_PASS_RPL")) : 0;
-    int cs = forced;
-    if (cs != 1 && cs != 2 && cs != 4) cs = A.ntot >= 64 ? 4 : (A.ntot >= 32 ? 2 : 1);
-    const int rpl = forced_rpl == 2 && LT <= 5 && !t_excl ? 2 : 1;  // (replicated sets: one row per lane)
-    if constexpr (LT <= 5) {
-        if (rpl == 2) {
-            if (cs == 4) return run_passes_cs<LT, 4, 2>(ctx, A, kind, cols);
-            if (cs == 2) return run_passes_cs<LT, 2, 2>(ctx, A, kind, cols);
-            return run_passes_cs<LT, 1, 2>(ctx, A, kind, cols);
-        }
-    }
-    if (cs == 4) return run_passes_cs<LT, 4, 1>(ctx, A, kind, cols);
-    if (cs == 2) return run_passes_cs<LT, 2, 1>(ctx, A, kind, cols);
-    return run_passes_cs<LT, 1, 1>(ctx, A, kind, cols);
+int run_passes(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int kind, const double* cols) {
+    if (kind == SP_YA) return run_pass_cs<LT, SP_YA, 1>(ctx, ln, A, cols);
+    if (kind == SP_RES) return run_pass_kind<LT, SP_RES>(ctx, ln, A, cols);
+    return run_pass_kind<LT, SP_W>(ctx, ln, A, cols);
 }
 
-int run_pass(vlgp_ctx* ctx, const SplitArgs& A, int LT, int kind, const double* cols) {
-    if (LT == 3) return run_passes<3>(ctx, A, kind, cols);
-    if (LT == 5) return run_passes<5>(ctx, A, kind, cols);
-    if (LT == 8) return run_passes<8>(ctx, A, kind, cols);
-    return run_passes<10>(ctx, A, kind, cols);
+int run_pass(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int LT, int kind, const double* cols) {
+    if (LT == 3) return run_passes<3>(ctx, ln, A, kind, cols);
+    if (LT == 5) return run_passes<5>(ctx, ln, A, kind, cols);
+    if (LT == 8) return run_passes<8>(ctx, ln, A, kind, cols);
+    return run_passes<10>(ctx, ln, A, kind, cols);
 }
 
 // the y pass: coalesced form while a lane's channels fit in registers (N <= 128), else the lane-per-row pass
-int run_ya(vlgp_ctx* ctx, const SplitArgs& A, int LT, const double* cols, const double* ycoef) {
-    static const bool old_form = getenv("VLGP_YA_ROWLANE") != nullptr;
-    if (A.N > 128 || old_form) return run_pass(ctx, A, LT, SP_YA, cols);
+int run_ya(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int LT, const double* cols, const double* ycoef) {
+    if (A.N > 128) return run_pass(ctx, ln, A, LT, SP_YA, cols);
     const int rows_per_wave = 64;
     const dim3 grid((unsigned)((A.rows + 4 * rows_per_wave - 1) / (4 * rows_per_wave))), blk(256);
-    NEED_LANE(ctx);
-    hipStream_t st = t_lane;
-    const ExclArgs X = t_excl ? *t_excl : ExclArgs{};
+    hipStream_t st = ln.st;
+    const ExclArgs X = ln.excl ? *ln.excl : ExclArgs{};
 #define ESPLIT_YA(LTV, NJV)                                                                                              \
     do {                                                                                                                 \
-        if (t_excl) hipLaunchKernelGGL((esplit_ya<LTV, NJV, true>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, \
-                                       A.ya, rows_per_wave, X);                                                          \
+        if (ln.excl) hipLaunchKernelGGL((esplit_ya<LTV, NJV, true>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, \
+                                        A.ya, rows_per_wave, X);                                                         \
         else hipLaunchKernelGGL((esplit_ya<LTV, NJV>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, A.ya,       \
                                 rows_per_wave, X);                                                                       \
     } while (0)
@@ -1759,14 +1694,12 @@ int run_ya(vlgp_ctx* ctx, const SplitArgs& A, int LT, const double* cols, const 
     return VLGP_OK;
 }
 
-int run_latent_class(vlgp_ctx* ctx, const SplitArgs& A, int maxra, bool mean) {
+int run_latent_class(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int maxra, bool mean) {
     const int tasks = A.M * A.n_lat;
     if (tasks == 0) return VLGP_OK;
     const dim3 grid(A.shg ? (unsigned)(((A.M + 3) / 4) * A.n_lat) : (unsigned)((tasks + 3) / 4)), blk(256);
-    static const int lds_pad = getenv("VLGP_LDS_PAD") ? atoi(getenv("VLGP_LDS_PAD")) : 0;  // occupancy experiments
-    const size_t lds = (size_t)(4 * (A.pkl + A.lds_g + 128 + (mean ? 192 : 0)) + (A.shg ? A.shg_cap : 0)) * 8 + (size_t)lds_pad;
-    NEED_LANE(ctx);
-    hipStream_t st = t_lane;
+    const size_t lds = (size_t)(4 * (A.pkl + A.lds_g + 128 + (mean ? 192 : 0)) + (A.shg ? A.shg_cap : 0)) * 8;
+    hipStream_t st = ln.st;
 #define ESPLIT_LAUNCH(RA, MEANV)                                                                                      \
     do {                                                                                                              \
         auto fn = (MEANV && A.last) ? esplit_latent<RA, MEANV, MEANV> : esplit_latent<RA, MEANV>;                                                                           \
@@ -1785,7 +1718,7 @@ int run_latent_class(vlgp_ctx* ctx, const SplitArgs& A, int maxra, bool mean) {
 }
 
 // one workgroup (four waves) per (latent, group of 64 units): estep_lane.h
-int run_latent_lane(vlgp_ctx* ctx, const SplitArgs& A, bool mean) {
+int run_latent_lane(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, bool mean) {
     const int groups = (A.M + 63) / 64;
     if (groups == 0 || A.n_lat == 0) return VLGP_OK;
     const bool last = mean && A.last;
@@ -1793,8 +1726,7 @@ int run_latent_lane(vlgp_ctx* ctx, const SplitArgs& A, bool mean) {
     if (lds > (size_t)ctx->lds_max)  // (162,304 bytes at T = 64 on the last sweep: 1.5 KB under gfx950's 160 KB)
         return vlgp_fail(ctx, VLGP_ERR_ARG, "lane-per-task E-step launch needs %zu bytes of LDS, the device has %d", lds, ctx->lds_max);
     const dim3 grid((unsigned)(groups * A.n_lat)), blk(256);
-    NEED_LANE(ctx);
-    hipStream_t st = t_lane;
+    hipStream_t st = ln.st;
     int rtop = 0;
     for (int i = 0; i < A.n_lat; ++i) rtop = A.shg_rk[i] > rtop ? A.shg_rk[i] : rtop;
     auto fn = rtop <= 13 ? (!mean ? esplit_lane<0, 13> : (last ? esplit_lane<2, 13> : esplit_lane<1, 13>))
@@ -1808,7 +1740,7 @@ int run_latent_lane(vlgp_ctx* ctx, const SplitArgs& A, bool mean) {
 }
 
 // the lane-per-task blocks of `Aln` and the wave-per-task blocks of `Alt` (class maxra: 20 / 24 / 32) as one grid (esplit_mix)
-int run_latent_mix(vlgp_ctx* ctx, const SplitArgs& Aln, const SplitArgs& Alt, int maxra, bool mean) {
+int run_latent_mix(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& Aln, const SplitArgs& Alt, int maxra, bool mean) {
     const int n_lane = ((Aln.M + 63) / 64) * Aln.n_lat;
     const int n_lat = (Alt.M * Alt.n_lat + 3) / 4;
     if (n_lane == 0 || n_lat == 0) return vlgp_fail(ctx, VLGP_ERR_STATE, "mixed E-step launch without both kinds of blocks");
@@ -1819,8 +1751,7 @@ int run_latent_mix(vlgp_ctx* ctx, const SplitArgs& Aln, const SplitArgs& Alt, in
     if (lds > (size_t)ctx->lds_max)
         return vlgp_fail(ctx, VLGP_ERR_ARG, "mixed E-step launch needs %zu bytes of LDS, the device has %d", lds, ctx->lds_max);
     const dim3 grid((unsigned)(n_lane + n_lat)), blk(256);
-    NEED_LANE(ctx);
-    hipStream_t st = t_lane;
+    hipStream_t st = ln.st;
     const int kind = !mean ? 0 : (last ? 2 : 1);
     for (int i = 0; i < Aln.n_lat; ++i)
         if (Aln.shg_rk[i] > 13) return vlgp_fail(ctx, VLGP_ERR_STATE, "mixed E-step launch with a lane-per-task rank above 13");
@@ -1846,12 +1777,11 @@ int run_latent_mix(vlgp_ctx* ctx, const SplitArgs& Aln, const SplitArgs& Alt, in
 }
 
 // long units: one workgroup per (unit, latent)
-int run_latent_long(vlgp_ctx* ctx, const SplitArgs& A, bool mean) {
+int run_latent_long(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, bool mean) {
     const unsigned tasks = (unsigned)(A.M * A.L);
     if (tasks == 0) return VLGP_OK;
-    NEED_LANE(ctx);
-    if (mean) hipLaunchKernelGGL(elong_mean, dim3(tasks), dim3(256), (size_t)(LPK + 384) * 8, t_lane, A);
-    else hipLaunchKernelGGL(elong_factor, dim3(tasks), dim3(256), (size_t)(LPK + LRED) * 8, t_lane, A);
+    if (mean) hipLaunchKernelGGL(elong_mean, dim3(tasks), dim3(256), (size_t)(LPK + 384) * 8, ln.st, A);
+    else hipLaunchKernelGGL(elong_factor, dim3(tasks), dim3(256), (size_t)(LPK + LRED) * 8, ln.st, A);
     HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
 }
@@ -1869,9 +1799,9 @@ struct LatentClasses {
     bool mix = false;  // lane-per-task and wave-per-task latents in one launch (esplit_mix)
 };
 
-int run_latent(vlgp_ctx* ctx, SplitArgs A, const LatentClasses& C, bool mean) {
+int run_latent(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const LatentClasses& C, bool mean) {
     // lane-per-task latents AND others: one mixed launch (esplit_mix) instead of two or three dependent ones; the latents
-    // of rank 15, 16 then ride in the class of the higher ones (VLGP_ESTEP_MIX=0: the separate launches; per call)
+    // of rank 15, 16 then ride in the class of the higher ones (VLGP_ESTEP_MIX=0: the separate launches)
     const bool mix = C.mix;
     SplitArgs Ahi = A;
     const int n_hi = C.n_hi + (mix ? C.n_lo : 0);
@@ -1888,7 +1818,7 @@ int run_latent(vlgp_ctx* ctx, SplitArgs A, const LatentClasses& C, bool mean) {
             Ahi.lds_g = maxra_hi * (maxra_hi + 2);
             Ahi.pkl = 0;
         }
-        if (!mix) CHK(run_latent_class(ctx, Ahi, maxra_hi, mean));
+        if (!mix) CHK(run_latent_class(ctx, ln, Ahi, maxra_hi, mean));
     }
     if (C.n_ln) {
         // ONE launch for all of them, the highest ranks first in the grid (their workgroups live longest)
@@ -1903,16 +1833,14 @@ int run_latent(vlgp_ctx* ctx, SplitArgs A, const LatentClasses& C, bool mean) {
         }
         A.shg = 1;
         A.shg_T = C.single_T;
-        static const int prio = getenv("VLGP_LANE_PRIO") ? atoi(getenv("VLGP_LANE_PRIO")) : 0;  // (measured: 3 is 5 % slower)
-        static const int clk_kind = getenv("VLGP_LANE_CLOCK") ? atoi(getenv("VLGP_LANE_CLOCK")) : 0;
-        A.prio = prio;
+        A.prio = ctx->sw.lane_prio;  // (measured: 3 is 5 % slower)
         A.clk = ctx->d_clk;
-        A.clk_kind = clk_kind;
+        A.clk_kind = ctx->sw.lane_clock;
         if (mix) {
             ctx->last_estep_mix = 1;
-            return run_latent_mix(ctx, A, Ahi, maxra_hi, mean);
+            return run_latent_mix(ctx, ln, A, Ahi, maxra_hi, mean);
         }
-        CHK(run_latent_lane(ctx, A, mean));
+        CHK(run_latent_lane(ctx, ln, A, mean));
     }
     if (C.n_lo) {
         A.n_lat = C.n_lo;
@@ -1920,8 +1848,7 @@ int run_latent(vlgp_ctx* ctx, SplitArgs A, const LatentClasses& C, bool mean) {
         A.pkl = tri_packed_size(16);
         A.lds_g = C.lds_g_lo;
         A.shg = 0;
-        static const bool no_shg = getenv("VLGP_ESTEP_NO_SHARED_G") != nullptr;
-        if (C.single_T > 0 && C.single && !no_shg) {
+        if (C.single_T > 0 && C.single && !ctx->sw.estep_no_shared_g) {
             for (int i = 0; i < C.n_lo; ++i) {
                 A.shg_rk[i] = C.single->rl[C.lo[i]];
                 A.shg_gl[i] = C.single->d_compact + C.single->goff[C.lo[i]];
@@ -1936,96 +1863,153 @@ int run_latent(vlgp_ctx* ctx, SplitArgs A, const LatentClasses& C, bool mean) {
             // sweeps keep X in registers
             if (!mean || !A.last) A.pkl = 0;
         }
-        CHK(run_latent_class(ctx, A, 16, mean));
+        CHK(run_latent_class(ctx, ln, A, 16, mean));
     }
     return VLGP_OK;
 }
 
-}  // namespace
+// What launch_estep_split decides before it touches the device: whether it takes the set (switches and size rules, DESIGN
+// 4.1) and with which kernels, classes, lanes and scratch layout (all from the set's own sizes: "path coupling").
+struct SplitPlan {
+    const char* decline = nullptr;  // not taken, and why; a replicated set turns the reason into an error (nothing else runs it)
+    bool lng = false;               // long units (T > 64): one workgroup per (unit, latent) task
+    int LT = 0, REC = 0;            // compiled latent count of the passes, doubles per channel record
+    int maxra = 16, pkg = 0;        // rank class of the set, doubles of packed X per task
+    bool use_lane = false;          // lane-per-task launches for the ranks <= LANE_RMAX (estep_lane.h)
+    LatentClasses C;
+    int n_it = 0;                   // sweeps
+    int n_lanes = 1;                // stream lanes; lane h runs the units [cut[h], cut[h + 1])
+    int cut[VLGP_E_LANES + 1] = {};
+    // scratch of the set, in doubles: ra | ya | mu | v | w (nRL each) | xg | failg (int) | xl | sv | dl (nRL each)
+    int64_t nRL = 0, o_failg = 0, o_xl = 0, xl_len = 0, scratch_len = 0;
+};
 
-int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
-    *handled = 0;
+SplitPlan plan_estep_split(const vlgp_ctx* ctx, const UnitSet& us, const RankSummary& rs, int mode, int n_iter) {
+    SplitPlan P;
     const int N = ctx->N, L = ctx->L;
+    const Switches& sw = ctx->sw;
     // a replicated set (vlgp_replicate_units) runs here or nowhere: only these row passes leave a channel out, so neither
-    // the switches nor the size heuristics below may send it to another kernel family -- a limit it exceeds is an error
+    // the switches nor the size heuristics may send it to another kernel family -- a limit it exceeds is an error
     const bool rep = us.rep_src >= 0;
-#define SPLIT_DECLINE(cond, what)                                                                                   \
-    do {                                                                                                            \
-        if (cond) {                                                                                                 \
-            if (rep) return vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: the split E-step cannot run it (%s)", what); \
-            return VLGP_OK;                                                                                         \
-        }                                                                                                           \
-    } while (0)
-    const char* sw = getenv("VLGP_ESTEP_SPLIT");
-    if (!rep && sw && sw[0] == '0') return VLGP_OK;
-    if (!rep && getenv("VLGP_ESTEP_GENERIC")) return VLGP_OK;
+#define SPLIT_DECLINE(cond, what) \
+    do { if (cond) { P.decline = what; return P; } } while (0)
+    SPLIT_DECLINE(!rep && sw.estep_split == 0, "VLGP_ESTEP_SPLIT=0");
+    SPLIT_DECLINE(!rep && sw.estep_generic, "VLGP_ESTEP_GENERIC");
     SPLIT_DECLINE(L > 10, "L > 10");
     SPLIT_DECLINE(N > 1024, "N > 1024");
     // long units (full-length trials): the same launch sequence with one workgroup per (unit, latent) task, once there
     // are enough tasks to fill the chip (VLGP_ESTEP_LSPLIT=0/1 never / always)
-    const bool lng = us.Tmax > 64;
+    const bool lng = P.lng = us.Tmax > 64;
     if (lng) {
-        const char* lsw = getenv("VLGP_ESTEP_LSPLIT");
-        if (!rep && lsw && lsw[0] == '0') return VLGP_OK;
+        SPLIT_DECLINE(!rep && sw.estep_lsplit == 0, "VLGP_ESTEP_LSPLIT=0");
         SPLIT_DECLINE(ctx->R > LRP, "long units with prior rank R above the long-unit split limit");
-        if (!rep && !(lsw && lsw[0] == '1') && (int64_t)us.M * L < 128) return VLGP_OK;
+        SPLIT_DECLINE(!rep && sw.estep_lsplit != 1 && (int64_t)us.M * L < 128, "long units: fewer than 128 tasks");
     }
     // the persistent kernel (one workgroup per unit, two or three per CU) wins while its workgroups are ONE generation
     // (measured at N = 100, L = 5: 500 units 0.89 ms persistent / 1.09 ms split; 1000 units 2.09 / 1.42 ms -- the second
     // generation costs as much as the first however few units it holds)
-    if (!rep && !lng && !(sw && sw[0] == '1') && (us.rows < 16LL * 1024 || us.M <= 2 * ctx->n_cu)) return VLGP_OK;
-    const bool need_prior = (E.mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
-    int rmax = 0;
-    int rlat[16] = {0};  // largest rank of each latent over the priors this set uses
-    int64_t gw_lo = 0;                       // doubles of staged G per (unit, latent) among the rank <= 16 latents
-    if (need_prior) {
-        for (auto& kv : ctx->priors) {
-            const Prior& pr = kv.second;
-            if (pr.T < us.Tmin || pr.T > us.Tmax) continue;
-            for (int l = 0; l < L; ++l) {
-                rmax = pr.rl[l] > rmax ? pr.rl[l] : rmax;
-                rlat[l] = pr.rl[l] > rlat[l] ? pr.rl[l] : rlat[l];
-            }
-        }
-        for (auto& kv : ctx->priors) {
-            const Prior& pr = kv.second;
-            if (pr.T < us.Tmin || pr.T > us.Tmax) continue;
-            for (int l = 0; l < L; ++l) {
-                if (rlat[l] > 16) continue;
-                const int64_t g = (int64_t)pr.T * ((pr.rl[l] + 1) & ~1);
-                gw_lo = g > gw_lo ? g : gw_lo;
-            }
-        }
-    }
-    SPLIT_DECLINE(!lng && rmax > 32, "short units at effective prior rank above 32");
-    const int maxra = rmax <= 16 ? 16 : (rmax <= 20 ? 20 : (rmax <= 24 ? 24 : 32));
-    const int LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
-    const int REC = (2 * LT + 3 + 1) & ~1;
-    const int pkg = lng ? LPK : tri_packed_size(maxra);
-    // scratch of the set: ra | ya | xg | failg(int) ; records + wconst in ctx->d_ecols
-    const int64_t nRL = us.rows * L;
+    SPLIT_DECLINE(!rep && !lng && sw.estep_split != 1 && (us.rows < 16LL * 1024 || us.M <= 2 * ctx->n_cu),
+                  "short units: one generation of persistent workgroups");
+    SPLIT_DECLINE(!lng && rs.rmax > 32, "short units at effective prior rank above 32");
+    const bool need_prior = (mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
+    const int maxra = P.maxra = rs.rmax <= 16 ? 16 : (rs.rmax <= 20 ? 20 : (rs.rmax <= 24 ? 24 : 32));
+    P.LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
+    P.REC = (2 * P.LT + 3 + 1) & ~1;
+    SPLIT_DECLINE(P.REC > 34, "channel records longer than 34 doubles");
+#undef SPLIT_DECLINE
+    P.pkg = lng ? LPK : tri_packed_size(maxra);
     // lane-per-task launches (estep_lane.h): one prior for the whole set, T <= 64; VLGP_ESTEP_LANEPT=0 keeps the
-    // wave-per-task kernels (per call: tests toggle it)
-    const char* lpt = getenv("VLGP_ESTEP_LANEPT");
-    const bool use_lane = !lng && need_prior && us.Tmin == us.Tmax && !(lpt && lpt[0] == '0') &&
-                          !getenv("VLGP_ESTEP_NO_SHARED_G");
-    const int64_t n_groups = ((int64_t)us.M + 63) / 64;
-    const int64_t xl_len = use_lane ? n_groups * L * 64 * LANE_EMAX : 0;
-    const int64_t need = 5 * nRL + (int64_t)us.M * L * pkg + ((int64_t)us.M * L + 1) / 2 + 8 + xl_len + (use_lane ? 2 * nRL : 0);
-    if (us.scratch_len < need) {
+    // wave-per-task kernels
+    P.use_lane = !lng && need_prior && us.Tmin == us.Tmax && sw.estep_lanept != 0 && !sw.estep_no_shared_g;
+
+    LatentClasses& C = P.C;
+    if (need_prior && us.Tmin == us.Tmax) {
+        C.single_T = us.Tmax;
+        C.single = rs.single;
+    }
+    for (int l = 0; l < L; ++l) {
+        if (P.use_lane && C.single && rs.rlat[l] <= LANE_RMAX) C.ln[C.n_ln++] = l;
+        else if (rs.rlat[l] <= 16) C.lo[C.n_lo++] = l;
+        else C.hi[C.n_hi++] = l;
+    }
+    {
+        // mixed launches carry the lane-per-task code compiled for ranks <= 13 (no scratch frame: a frame alone costs
+        // every wave of the launch, and ROCr allocates it per queue at first use -- milliseconds, seen as an 8.8 ms
+        // E-step in the middle of a fit); a latent at rank 14 rides with the wave-per-task ones there
+        const bool mix_on = sw.estep_mix != 0;
+        const bool others = C.n_hi > 0 || C.n_lo > 0;
+        if (mix_on && C.n_ln > 0 && others) {  // (nothing but lane-per-task latents: their launch as it is, rank 14 included)
+            int keep = 0;
+            for (int i = 0; i < C.n_ln; ++i) {
+                if (rs.rlat[C.ln[i]] >= 14) C.lo[C.n_lo++] = C.ln[i];
+                else C.ln[keep++] = C.ln[i];
+            }
+            C.n_ln = keep;
+        }
+        C.mix = mix_on && C.n_ln > 0 && (C.n_hi > 0 || C.n_lo > 0);
+    }
+    C.maxra_hi = maxra;
+    C.lds_g_lo = (int)((rs.g_even_lo + 1) & ~1LL);  // staged G of a rank <= 16 latent (and the 16 x 16 staging tile)
+    if (C.lds_g_lo < 256) C.lds_g_lo = 256;
+
+    // TWO LANES.  The units are independent inside an E-step call (core.estep is a loop over units, core.py:123-126),
+    // and every launch of a sweep is partly bound by the latency of one task's dependent chain (factor ~28 us, mean
+    // ~17 us of their 47 / 21 us at C3) and by the ~2.5 us of a dependent launch boundary: the set is cut in
+    // parts (two by default, VLGP_ESTEP_LANES = 1 .. 4) whose sweeps are enqueued on their own streams, so that one half's
+    // latency-bound stretches sit under the other half's issue-bound passes.  No dependency crosses the halves between
+    // the fork and the join; results are bit-identical to the single lane (same arithmetic per unit).
+    // 2000 units: 2.11 -> 1.77 ms; 1000 units: no change with the wave-per-task launches, 1.60 -> 1.54 ms (and the H-step
+    // that follows 2.60 -> 2.41 ms) with the lane-per-task ones.  (Measured: three or four lanes are SLOWER than one --
+    // E-step 5.7 ms against 3.5 / 3.0 for one / two at C3 -- and starting the second lane one or two launches late
+    // changes nothing.)
+    P.n_it = (mode & EM_MEAN) ? n_iter : ((mode & EM_W) ? 1 : 0);
+    int n_lanes = sw.estep_lanes ? sw.estep_lanes : (us.M >= 3 * ctx->n_cu && P.n_it >= 2 ? 2 : 1);
+    // (lane-per-task latents: the cuts are multiples of 64 units -- a half must not come out empty, ADVICE round 5)
+    while (n_lanes > 1 && us.M < (C.n_ln ? 64 : 8) * n_lanes) --n_lanes;
+    P.n_lanes = n_lanes;
+    // cuts at multiples of four units: the shared-G launches take four units per workgroup (64: a wave of the
+    // lane-per-task launches)
+    const int64_t cm = C.n_ln ? 63 : 3;
+    for (int h = 0; h < n_lanes; ++h) {
+        const int64_t m0 = ((int64_t)us.M * h / n_lanes + cm) & ~cm;
+        P.cut[h] = m0 > us.M ? us.M : (int)m0;
+    }
+    P.cut[n_lanes] = us.M;
+
+    const int64_t tasks = (int64_t)us.M * L;
+    P.nRL = us.rows * L;
+    P.xl_len = P.use_lane ? (((int64_t)us.M + 63) / 64) * L * 64 * LANE_EMAX : 0;
+    P.o_failg = 5 * P.nRL + tasks * P.pkg;
+    P.o_xl = P.o_failg + (tasks + 1) / 2 + 1;
+    P.scratch_len = P.o_failg + (tasks + 1) / 2 + 8 + P.xl_len + (P.use_lane ? 2 * P.nRL : 0);
+    return P;
+}
+
+}  // namespace
+
+int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummary& rs, int* handled) {
+    *handled = 0;
+    const SplitPlan P = plan_estep_split(ctx, us, rs, E.mode, E.n_iter);
+    const bool rep = us.rep_src >= 0;
+    if (P.decline)
+        return rep ? vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: the split E-step cannot run it (%s)", P.decline) : VLGP_OK;
+    const int N = ctx->N, L = ctx->L, LT = P.LT, pkg = P.pkg, n_lanes = P.n_lanes, n_it = P.n_it;
+    const bool lng = P.lng;
+    const LatentClasses& C = P.C;
+    const int64_t nRL = P.nRL;
+    if (us.scratch_len < P.scratch_len) {
         if (us.d_scratch) HIPCHK(ctx, hipFree(us.d_scratch));
         us.d_scratch = nullptr;
         us.scratch_len = 0;
-        HIPCHK(ctx, hipMalloc(&us.d_scratch, (size_t)need * 8));
-        us.scratch_len = need;
+        HIPCHK(ctx, hipMalloc(&us.d_scratch, (size_t)P.scratch_len * 8));
+        us.scratch_len = P.scratch_len;
     }
+    // records + wconst in ctx->d_ecols
     if (!ctx->d_ecols) HIPCHK(ctx, hipMalloc(&ctx->d_ecols, sizeof(double) * ((size_t)N * 50 + 32)));
-    SPLIT_DECLINE(REC > 34, "channel records longer than 34 doubles");
-#undef SPLIT_DECLINE
     double* cols = ctx->d_ecols;
     double* wconst = ctx->d_ecols + (int64_t)N * 34;
     double* ycoef = wconst + 32;  // (N, LT), LT <= 10
-    hipLaunchKernelGGL(esplit_cols_kernel, dim3(1), dim3(256), 0, ctx->stream, N, L, LT, REC, ctx->d_a, ctx->d_b,
+    hipLaunchKernelGGL(esplit_cols_kernel, dim3(1), dim3(256), 0, ctx->stream, N, L, LT, P.REC, ctx->d_a, ctx->d_b,
                        ctx->d_noise, ctx->d_gauss, cols, wconst, ycoef);
     HIPCHK(ctx, hipGetLastError());
     ExclArgs XA{};  // replicated set: its replica table, source rows, per-replica wconst
@@ -2062,51 +2046,15 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
         memcpy(us.rep_xh, &XA, sizeof(ExclArgs));
         HIPCHK(ctx, hipMemcpyAsync(us.d_rep_xa, us.rep_xh, sizeof(ExclArgs), hipMemcpyHostToDevice, ctx->stream));
     }
-    A.failg = reinterpret_cast<int*>(A.xg + (int64_t)us.M * L * pkg);
-    A.xl = reinterpret_cast<double*>(A.failg) + ((int64_t)us.M * L + 1) / 2 + 1;
-    A.sv = use_lane ? A.xl + xl_len : nullptr;
-    A.dl = use_lane ? A.sv + nRL : nullptr;
+    A.failg = reinterpret_cast<int*>(us.d_scratch + P.o_failg);
+    A.xl = us.d_scratch + P.o_xl;
+    A.sv = P.use_lane ? A.xl + P.xl_len : nullptr;
+    A.dl = P.use_lane ? A.sv + nRL : nullptr;
     A.dmask = 0;
     A.fail = E.fail;
     A.wconst = wconst;
     A.dmu_bound = E.dmu_bound;
     A.ntot = N; A.np = N - ctx->n_gauss;
-    LatentClasses C;
-    if (need_prior && us.Tmin == us.Tmax) {
-        C.single_T = us.Tmax;
-        for (auto& kv : ctx->priors)
-            if (kv.second.T == us.Tmax) C.single = &kv.second;
-    }
-    for (int l = 0; l < L; ++l) {
-        if (use_lane && C.single && rlat[l] <= LANE_RMAX) C.ln[C.n_ln++] = l;
-        else if (rlat[l] <= 16) C.lo[C.n_lo++] = l;
-        else C.hi[C.n_hi++] = l;
-    }
-    {
-        // mixed launches carry the lane-per-task code compiled for ranks <= 13 (no scratch frame: a frame alone costs
-        // every wave of the launch, and ROCr allocates it per queue at first use -- milliseconds, seen as an 8.8 ms
-        // E-step in the middle of a fit); a latent at rank 14 rides with the wave-per-task ones there
-        const char* mixsw = getenv("VLGP_ESTEP_MIX");
-        const bool mix_on = !(mixsw && mixsw[0] == '0');
-        bool others = C.n_hi > 0 || C.n_lo > 0;
-        if (mix_on && C.n_ln > 0) {
-            int keep = 0, moved = 0, mv[16];
-            for (int i = 0; i < C.n_ln; ++i) {
-                if (rlat[C.ln[i]] >= 14) mv[moved++] = C.ln[i];
-                else C.ln[keep++] = C.ln[i];
-            }
-            if (others && moved > 0) {  // (nothing but lane-per-task latents: their launch as it is, rank 14 included)
-                C.n_ln = keep;
-                for (int i = 0; i < moved; ++i) C.lo[C.n_lo++] = mv[i];
-            } else {  // restore
-                for (int i = 0; i < moved; ++i) C.ln[keep + i] = mv[i];
-            }
-        }
-        C.mix = mix_on && C.n_ln > 0 && (C.n_hi > 0 || C.n_lo > 0);
-    }
-    C.maxra_hi = maxra;
-    C.lds_g_lo = (int)((gw_lo + 1) & ~1LL);  // staged G of a rank <= 16 latent (and the 16 x 16 staging tile)
-    if (C.lds_g_lo < 256) C.lds_g_lo = 256;
     A.lds_g = 256; A.pkl = pkg; A.n_lat = 0;
     A.shg = 0; A.shg_cap = 0; A.shg_T = 0;
     A.do_v = 0; A.last = 0;
@@ -2116,104 +2064,83 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
 
     const int mode = E.mode;
     const bool with_mean = (mode & EM_MEAN) != 0;
-    const int n_it = with_mean ? E.n_iter : ((mode & EM_W) ? 1 : 0);
     const int kind = lng ? VLGP_PROF_ESTEP_LONG
-                         : (maxra <= 16 ? VLGP_PROF_ESTEP_RA16 : (maxra <= 24 ? VLGP_PROF_ESTEP_RA24 : VLGP_PROF_ESTEP_RA32));
+                         : (P.maxra <= 16 ? VLGP_PROF_ESTEP_RA16 : (P.maxra <= 24 ? VLGP_PROF_ESTEP_RA24 : VLGP_PROF_ESTEP_RA32));
     vlgp_prof_begin(ctx, kind);
-    t_lane = ctx->stream;
-    t_excl = rep ? &XA : nullptr;
-    t_excl_dev = rep ? reinterpret_cast<const ExclArgs*>(us.d_rep_xa) : nullptr;
+    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.d_rep_xa) : nullptr};
     int rc = VLGP_OK;
-    if (with_mean) rc = run_ya(ctx, A, LT, cols, ycoef);
+    if (with_mean) rc = run_ya(ctx, main_lane, A, LT, cols, ycoef);
 
-    // TWO LANES.  The units are independent inside an E-step call (core.estep is a loop over units, core.py:123-126),
-    // and every launch of a sweep is partly bound by the latency of one task's dependent chain (factor ~28 us, mean
-    // ~17 us of their 47 / 21 us at C3) and by the ~2.5 us of a dependent launch boundary: the set is cut in two
-    // parts (two by default, VLGP_ESTEP_LANES = 1 .. 4) whose sweeps are enqueued on their own streams, so that one half's latency-bound stretches sit under the other
-    // half's issue-bound passes.  No dependency crosses the halves between the fork and the join; results are
-    // bit-identical to the single lane (same arithmetic per unit).  VLGP_ESTEP_LANES=1 keeps one lane.
-    const int lanes_env = getenv("VLGP_ESTEP_LANES") ? atoi(getenv("VLGP_ESTEP_LANES")) : 0;  // (per call: tests toggle it)
-    int n_lanes = (lanes_env >= 1 && lanes_env <= VLGP_E_LANES) ? lanes_env : (us.M >= 3 * ctx->n_cu && n_it >= 2 ? 2 : 1);  // 2000 units: 2.11 -> 1.77 ms; 1000 units: no change with the wave-per-task launches, 1.60 -> 1.54 ms (and the H-step that follows 2.60 -> 2.41 ms) with the lane-per-task ones
-    // (lane-per-task latents: the cuts are multiples of 64 units -- a half must not come out empty, ADVICE round 5)
-    while (n_lanes > 1 && us.M < (C.n_ln ? 64 : 8) * n_lanes) --n_lanes;
     for (int h = 1; h < n_lanes; ++h) {
         if (ctx->elane[h - 1]) continue;
         HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->elane[h - 1], hipStreamNonBlocking));
         HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_e_join[h - 1], hipEventDisableTiming));
     }
     if (n_lanes > 1 && !ctx->ev_e_fork) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_e_fork, hipEventDisableTiming));
-    struct Half { SplitArgs pass, lat; hipStream_t st; int64_t rows; int M; };
+    // the arguments of each lane's launches: `lat` keeps last / do_v from one launch of the lane to its next
+    struct Half { SplitArgs pass, lat; Lane ln; int64_t rows; int M; };
     Half H[VLGP_E_LANES];
-    {
-        for (int h = 0; h < n_lanes; ++h) {
-            // cuts at multiples of four units: the shared-G launches take four units per workgroup (64: a wave of the
-            // lane-per-task launches)
-            const int64_t cm = C.n_ln ? 63 : 3;
-            int m0 = (int)(((int64_t)us.M * h / n_lanes + cm) & ~cm), m1 = (int)(((int64_t)us.M * (h + 1) / n_lanes + cm) & ~cm);
-            if (m0 > us.M) m0 = us.M;
-            if (m1 > us.M || h == n_lanes - 1) m1 = us.M;
-            const int64_t row_lo = us.off[m0], row_hi = us.off[m1];
-            Half& hf = H[h];
-            hf.st = h == 0 ? ctx->stream : ctx->elane[h - 1];
-            hf.M = m1 - m0;
-            hf.rows = row_hi - row_lo;
-            // per-unit kernels: unit tables shifted, rows stay absolute (off[] holds absolute rows)
-            hf.lat = A;
-            hf.lat.M = hf.M;
-            hf.lat.off = A.off + m0;
-            hf.lat.unit_prior = A.unit_prior ? A.unit_prior + m0 : nullptr;
-            hf.lat.xg = A.xg + (int64_t)m0 * L * pkg;
-            hf.lat.xl = A.xl + (int64_t)(m0 / 64) * L * 64 * LANE_EMAX;
-            hf.lat.failg = A.failg + (int64_t)m0 * L;
-            // row passes: every row-indexed pointer shifted to the half's first row
-            hf.pass = A;
-            hf.pass.rows = hf.rows;
-            hf.pass.y = A.y + row_lo * N;
-            hf.pass.xb = A.xb ? A.xb + row_lo * N : nullptr;
-            hf.pass.mu = A.mu + row_lo; hf.pass.v = A.v + row_lo; hf.pass.w = A.w + row_lo;
-            hf.pass.ra = A.ra + row_lo; hf.pass.ya = A.ya + row_lo;
-            if (A.sv) { hf.pass.sv = A.sv + row_lo; hf.pass.dl = A.dl + row_lo; }
-        }
+    for (int h = 0; h < n_lanes; ++h) {
+        const int m0 = P.cut[h], m1 = P.cut[h + 1];
+        const int64_t row_lo = us.off[m0], row_hi = us.off[m1];
+        Half& hf = H[h];
+        hf.ln = main_lane;
+        if (h > 0) hf.ln.st = ctx->elane[h - 1];
+        hf.M = m1 - m0;
+        hf.rows = row_hi - row_lo;
+        // per-unit kernels: unit tables shifted, rows stay absolute (off[] holds absolute rows)
+        hf.lat = A;
+        hf.lat.M = hf.M;
+        hf.lat.off = A.off + m0;
+        hf.lat.unit_prior = A.unit_prior ? A.unit_prior + m0 : nullptr;
+        hf.lat.xg = A.xg + (int64_t)m0 * L * pkg;
+        hf.lat.xl = A.xl + (int64_t)(m0 / 64) * L * 64 * LANE_EMAX;
+        hf.lat.failg = A.failg + (int64_t)m0 * L;
+        // row passes: every row-indexed pointer shifted to the half's first row
+        hf.pass = A;
+        hf.pass.rows = hf.rows;
+        hf.pass.y = A.y + row_lo * N;
+        hf.pass.xb = A.xb ? A.xb + row_lo * N : nullptr;
+        hf.pass.mu = A.mu + row_lo; hf.pass.v = A.v + row_lo; hf.pass.w = A.w + row_lo;
+        hf.pass.ra = A.ra + row_lo; hf.pass.ya = A.ya + row_lo;
+        if (A.sv) { hf.pass.sv = A.sv + row_lo; hf.pass.dl = A.dl + row_lo; }
     }
-    // (measured: three or four lanes are SLOWER than one -- E-step 5.7 ms against 3.5 / 3.0 for one / two at C3 -- and
-    // starting the second lane one or two launches late changes nothing)
     if (n_lanes > 1 && rc == VLGP_OK) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_e_fork, ctx->stream));
         for (int h = 1; h < n_lanes; ++h) HIPCHK(ctx, hipStreamWaitEvent(ctx->elane[h - 1], ctx->ev_e_fork, 0));
     }
+    unsigned ln_mask = 0;  // the latents whose mean launch (lane-per-task) leaves its step for the curvature pass to apply
+    for (int i = 0; i < C.n_ln; ++i) ln_mask |= 1u << C.ln[i];
     for (int it = (mode & EM_FACTOR0) ? -1 : 0; it < n_it && rc == VLGP_OK; ++it) {
         const bool last = it == n_it - 1;
         for (int h = 0; h < n_lanes && rc == VLGP_OK; ++h) {
             Half& hf = H[h];
-            t_lane = hf.st;
+            const Lane& ln = hf.ln;
             bool do_factor, do_v;
             // per-kernel timing: the launches of ONE sweep per call (first lane) are bracketed (events on every launch
             // would cost more than they measure); with two lanes the other lane's launches run beside the bracketed one
             const bool sample = ctx->prof_on && h == 0 && it == (n_it > 1 ? 1 : 0);
             const double share = (double)hf.rows, tasks = (double)hf.M * L;
             if (it >= 0) {
+                SplitArgs pass = hf.pass;  // this sweep's row passes
                 if (with_mean) {
-                    if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_PASS, hf.st);
+                    if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_PASS, ln.st);
                     // ra itself is read by the wave-per-task mean launches and by the last sweep's dmu form only: with
                     // every latent on the lane-per-task launch the pass writes s = ra + w mu alone (4 MB less per lane
                     // and sweep at C3)
-                    double* const ra_keep = hf.pass.ra;
-                    if (C.n_ln && !C.n_lo && !C.n_hi && !last) hf.pass.ra = nullptr;
-                    rc = run_pass(ctx, hf.pass, LT, SP_RES, cols);
-                    hf.pass.ra = ra_keep;
-                    if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_PASS, share, hf.st);
+                    if (C.n_ln && !C.n_lo && !C.n_hi && !last) pass.ra = nullptr;
+                    rc = run_pass(ctx, ln, pass, LT, SP_RES, cols);
+                    pass.ra = hf.pass.ra;
+                    if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_PASS, share, ln.st);
                     hf.lat.last = last ? 1 : 0;
-                    if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_MEAN, hf.st);
-                    if (rc == VLGP_OK) rc = lng ? run_latent_long(ctx, hf.lat, true) : run_latent(ctx, hf.lat, C, true);
-                    if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_MEAN, tasks, hf.st);
+                    if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_MEAN, ln.st);
+                    if (rc == VLGP_OK) rc = lng ? run_latent_long(ctx, ln, hf.lat, true) : run_latent(ctx, ln, hf.lat, C, true);
+                    if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_MEAN, tasks, ln.st);
+                    pass.dmask = ln_mask;
                 }
-                if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_PASS, hf.st);
-                hf.pass.dmask = 0;  // the mean launch of the lane-per-task latents left its step for this pass to apply
-                if (with_mean)
-                    for (int i = 0; i < C.n_ln; ++i) hf.pass.dmask |= 1u << C.ln[i];
-                if (rc == VLGP_OK) rc = run_pass(ctx, hf.pass, LT, SP_W, cols);
-                hf.pass.dmask = 0;
-                if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_PASS, share, hf.st);
+                if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_PASS, ln.st);
+                if (rc == VLGP_OK) rc = run_pass(ctx, ln, pass, LT, SP_W, cols);
+                if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_PASS, share, ln.st);
                 do_factor = with_mean && (E.vb || !last);
                 do_v = E.vb != 0;
             } else {
@@ -2222,14 +2149,12 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, int* handled) {
             }
             if (do_factor && rc == VLGP_OK) {
                 hf.lat.do_v = do_v ? 1 : 0;
-                if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_FACTOR, hf.st);
-                rc = lng ? run_latent_long(ctx, hf.lat, false) : run_latent(ctx, hf.lat, C, false);
-                if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_FACTOR, tasks, hf.st);
+                if (sample) vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_FACTOR, ln.st);
+                rc = lng ? run_latent_long(ctx, ln, hf.lat, false) : run_latent(ctx, ln, hf.lat, C, false);
+                if (sample) vlgp_prof_end(ctx, VLGP_PROF_ESTEP_FACTOR, tasks, ln.st);
             }
         }
     }
-    t_lane = ctx->stream;
-    t_excl = nullptr;
     for (int h = 1; h < n_lanes; ++h) {  // join whatever happened above: the extra lanes must never outlive the call
         (void)hipEventRecord(ctx->ev_e_join[h - 1], ctx->elane[h - 1]);
         (void)hipStreamWaitEvent(ctx->stream, ctx->ev_e_join[h - 1], 0);

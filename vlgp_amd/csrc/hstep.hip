@@ -1102,8 +1102,8 @@ int launch_hstep(vlgp_ctx* ctx, UnitSet& us, int window, double dt, int n_eval, 
 // the units only, so vlgp_hstep_prepare can enqueue them the moment the E-step is done -- under the host's way to the
 // first objective call -- instead of in front of the first round.  Buffers of their own (not the round workspace).
 static bool hstep_round_kernels_apply(vlgp_ctx* ctx, const UnitSet& us, int T) {
-    const HstepSwitches& sw = ctx->hsw;
-    return us.Tmin == T && us.Tmax == T && T <= 64 && T >= (sw.dense ? 24 : 4) && !sw.generic;
+    const Switches& sw = ctx->sw;
+    return us.Tmin == T && us.Tmax == T && T <= 64 && T >= (sw.hstep_dense ? 24 : 4) && !sw.hstep_generic;
 }
 static int hstep_prepare_units(vlgp_ctx* ctx, UnitSet& us, int T, bool want_wlm, bool want_mom, hipStream_t st) {
     const int L = ctx->L, M = us.M;
@@ -1148,11 +1148,10 @@ static int hstep_prepare_units(vlgp_ctx* ctx, UnitSet& us, int T, bool want_wlm,
     return VLGP_OK;
 }
 int hstep_prepare(vlgp_ctx* ctx, UnitSet& us, int T, hipStream_t st) {
-    static const bool no_wlm = getenv("VLGP_HSTEP_NO_WLM") != nullptr;
     if (!hstep_round_kernels_apply(ctx, us, T)) return VLGP_OK;  // (the objective call reports what is wrong, if anything)
     ctx->hmom_us = nullptr;  // units as they are when everything queued so far is done
     ctx->hwlm_valid = false;
-    return hstep_prepare_units(ctx, us, T, !no_wlm, true, st);
+    return hstep_prepare_units(ctx, us, T, !ctx->sw.hstep_no_wlm, true, st);
 }
 
 static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, int n_eval, const int* latent,
@@ -1171,9 +1170,9 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
     // (round 4: the round-1 / round-2 kernels behind VLGP_HSTEP_UNFUSED / _PADDED / _LEAN / _TWOSET are gone; what is left
     // is the low-rank round, the dense matrix-pipe round (VLGP_HSTEP_DENSE=1 forces it), and the generic kernels
     // (VLGP_HSTEP_GENERIC=1), which also implement the reference's omega retry)
-    const HstepSwitches& sw = ctx->hsw;  // (the environment is read at vlgp_create / vlgp_debug_reload_switches)
-    const bool lr_allowed = !force_dense && !sw.dense;
-    const bool fast = T <= 64 && T >= (lr_allowed ? 4 : 24) && !sw.generic;
+    const Switches& sw = ctx->sw;
+    const bool lr_allowed = !force_dense && !sw.hstep_dense;
+    const bool fast = T <= 64 && T >= (lr_allowed ? 4 : 24) && !sw.hstep_generic;
     const int TC = T <= 50 ? 50 : 64;  // compiled window
     const int64_t TT = fast ? (int64_t)TC * TC : (int64_t)T * T;
     // workspace: kinv | q | dk | scal | seg_out | red | logp | latent(int)
@@ -1203,8 +1202,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
         for (int i = 0; i < 3 * n_eval; ++i) F.logp[i] = logp[i];
         F.kinv = W + o_kinv; F.kcol = W + o_q; F.scal = W + o_scal; F.out = W + o_out;
         F.wlm = nullptr; F.wld = 0;
-        static const bool no_wlm = getenv("VLGP_HSTEP_NO_WLM") != nullptr;
-        if (ctx->hmom_bracket && !no_wlm) {  // mu, w are fixed inside the bracket: one transposed copy of w serves every round
+        if (ctx->hmom_bracket && !sw.hstep_no_wlm) {  // mu, w are fixed inside the bracket: one transposed copy of w serves every round
             CHK(hstep_prepare_units(ctx, us, T, true, false, ctx->stream));
             F.wlm = ctx->d_hwlm; F.wld = us.rows;
         }
@@ -1226,8 +1224,8 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
             const bool mfma = true;
             // the exact low-rank round (hstep_lr.h) when every evaluation's kernel matrix has numerical rank <= LR_RCAP
             // (omega below about 2e-2 on a 50-bin window); VLGP_HSTEP_DENSE=1 keeps the dense matrix-pipe round
-            const bool lr_off = sw.dense;
-            const double lr_tol = sw.lr_tol;
+            const bool lr_off = sw.hstep_dense;
+            const double lr_tol = sw.hstep_lr_tol;
             bool lr = !lr_off && !force_dense;
             int rcap[16], rmax = 0;
             // evaluations whose kernel matrix has a numerical rank above LR_RCAP (omega above ~2e-2 at window 50: a fit's first
@@ -1250,7 +1248,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                 if (n_lr == 0) lr = false;
             }
             const int n_rough = lr ? n_eval - n_lr : 0;
-            if (lr && !sw.lowrank) {
+            if (lr && !sw.hstep_lowrank) {
                 // Which round is faster depends on how much there is to do (measured on MI355X, tools/lr_round_bench.py,
                 // us per round over n = n_eval x M segment-evaluations, 4000 of them = one "generation"):
                 //   dense      41 + 28 (n / 4000 - 1): one wave per segment, 4096 resident waves, ~25 us wave lifetime
@@ -1298,7 +1296,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                 // (Measured: the tables built by blocks of the round kernel itself, the segment blocks waiting on a flag,
                 // is SLOWER than this extra launch -- 57 against 26 + 12 us for one evaluation: the waiting blocks fill
                 // the chip before the table blocks finish.)
-                const bool fuse_tables = sw.fuse_tables && rmax <= 24;  // (the classes without tables in global memory)
+                const bool fuse_tables = sw.hstep_fuse_tables && rmax <= 24;  // (the classes without tables in global memory)
                 if (!fuse_tables) {
                     HRoundArgs Rt = R;
                     int k = 0;
@@ -1360,7 +1358,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                     const size_t lds_bytes = (size_t)need * 8;
                     const int grid = Rc.k_blocks + Rc.lr_nev * R.nb;
                     Rc.lds_doubles = need;
-                    const bool fuse = sw.fuse_tables && rmax <= 24;
+                    const bool fuse = sw.hstep_fuse_tables && rmax <= 24;
                     if (fuse && TC == 50 && ci == 0) CHK((launch_round_lr<50, 16, false, true>(ctx, Rc, grid, lds_bytes)));
                     else if (fuse && TC == 50 && ci == 1) CHK((launch_round_lr<50, 24, false, true>(ctx, Rc, grid, lds_bytes)));
                     else if (fuse && ci == 0) CHK((launch_round_lr<64, 16, false, true>(ctx, Rc, grid, lds_bytes)));
@@ -1482,7 +1480,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
     if (lds_prep > 64 * 1024)
         HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(hstep_prep_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-    const bool big = T > 64 && T <= 128 && !sw.generic_seg;  // hstep_prep_big / hstep_seg_big
+    const bool big = T > 64 && T <= 128 && !sw.hstep_generic_seg;  // hstep_prep_big / hstep_seg_big
     ctx->last_hstep_path = big ? VLGP_PATH_HSTEP_BIG : VLGP_PATH_HSTEP_GENERIC;
     if (big) {
         const size_t lds_pb = (size_t)(4 * 64 * 66 + HmGeom<64>::TASK + 2 * 128) * 8;

@@ -206,7 +206,8 @@ norms_kernel(int64_t n, const double* __restrict__ mu, const double* __restrict_
 int launch_norms(vlgp_ctx* ctx, UnitSet& us, double* d_part, unsigned* d_ticket, double* d_host, unsigned long long seq) {
     const int64_t n = us.rows * ctx->L;
     // (at most 256 blocks: every block ends with an atomic on ONE ticket word, ~25 ns each -- 977 blocks: 31 us)
-    static const int gmax = getenv("VLGP_NORMS_BLOCKS") ? atoi(getenv("VLGP_NORMS_BLOCKS")) : 256;
+    // (VLGP_NORMS_BLOCKS: 1 .. 1024, the slots of partial sums in front of the ticket word)
+    const int gmax = ctx->sw.norms_blocks;
     int g = (int)((n + 1023) / 1024);
     if (g > gmax) g = gmax;
     if (g < 1) g = 1;

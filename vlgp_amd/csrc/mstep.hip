@@ -937,8 +937,7 @@ static Geometry plan(vlgp_ctx* ctx, int64_t rows) {
     // round instead of three.  C3: H-step 4.3 -> 4.0 ms, 133-134 -> 137-141 EM it/s on the same boxes; 0.75 or 0.5 per CU
     // make the M-step itself the longer lane (125-131), and so do smaller workgroups (320 / 256 threads instead of 448:
     // 119 / 127 against 132-133 on the same box).  VLGP_MSTEP_WG_PER_CU overrides.
-    static const double wg_per_cu = getenv("VLGP_MSTEP_WG_PER_CU") ? atof(getenv("VLGP_MSTEP_WG_PER_CU")) : 1.0;
-    const int64_t cap = (int64_t)((wg_per_cu > 0 ? wg_per_cu : 1.0) * ctx->n_cu);
+    const int64_t cap = (int64_t)(ctx->sw.mstep_wg_per_cu * ctx->n_cu);
     if (G > cap) G = cap;
     if (G < 1) G = 1;
     g.rows_per_wg = (int)((rows + G - 1) / G);
@@ -979,7 +978,7 @@ static int launch_accum_p(vlgp_ctx* ctx, int kind, const Geometry& g, const MArg
 }
 // the loop-based fallback (mstep_cache_gen + mstep_accum_gen): cache = (rows x N) doubles of the M-step workspace
 // (VLGP_MSTEP_GENERIC=1 takes it at any size: the tests compare it with the specialised kernels)
-static bool mstep_generic(int L, int P) { return L > 16 || P > 8 || getenv("VLGP_MSTEP_GENERIC") != nullptr; }
+static bool mstep_generic(const vlgp_ctx* ctx, int L, int P) { return L > 16 || P > 8 || ctx->sw.mstep_generic; }
 static int launch_accum_gen(vlgp_ctx* ctx, int kind, const Geometry& g, const MArgs& A, double* cache) {
     hipStream_t st = ctx->mstream;
     if (kind != K_PREP) {
@@ -996,7 +995,7 @@ static int launch_accum_gen(vlgp_ctx* ctx, int kind, const Geometry& g, const MA
 
 static int launch_accum(vlgp_ctx* ctx, int kind, const Geometry& g, const MArgs& A, double* cache = nullptr) {
     const int L = A.L;
-    if (mstep_generic(A.L, A.P)) return launch_accum_gen(ctx, kind, g, A, cache);
+    if (mstep_generic(ctx, A.L, A.P)) return launch_accum_gen(ctx, kind, g, A, cache);
     if (L <= 2) return launch_accum_p<2>(ctx, kind, g, A);
     if (L <= 3) return launch_accum_p<3>(ctx, kind, g, A);
     if (L <= 5) return launch_accum_p<5>(ctx, kind, g, A);
@@ -1019,7 +1018,7 @@ static int latent_moments_st(vlgp_ctx* ctx, UnitSet& us, double* d_partial, doub
     if (G > 256) G = 256;
     if (G < 1) G = 1;
     const int K = tri(L) + 3 * L + 1;
-    if (L > 16 || getenv("VLGP_MSTEP_GENERIC"))
+    if (L > 16 || ctx->sw.mstep_generic)
         hipLaunchKernelGGL(latent_moments_gen, dim3(G, (K + MG_CH - 1) / MG_CH), dim3(256), 0, st, L, us.rows, us.mu, us.v,
                            us.dmu, d_partial);
     else if (L <= 2) launch_lat_t<2>(st, G, L, us.rows, us.mu, us.v, us.dmu, d_partial);
@@ -1053,7 +1052,7 @@ int launch_moments(vlgp_ctx* ctx, UnitSet& us) {
 int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double eps, double lr,
                  double da_bound, double db_bound) {
     const int N = ctx->N, L = ctx->L, P = ctx->P;
-    const bool gen = mstep_generic(L, P);  // beyond the compiled sizes: loop-based kernels, solves in global memory
+    const bool gen = mstep_generic(ctx, L, P);  // beyond the compiled sizes: loop-based kernels, solves in global memory
     const Geometry g = plan(ctx, us.rows);
     const int Kp = nstat_rt(L, P, K_PREP), Kn = nstat_rt(L, P, K_NEWTON);
     const int Kl = tri(L) + 3 * L + 1;
@@ -1074,16 +1073,15 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
     unsigned* d_ticket = reinterpret_cast<unsigned*>(W + o_tick);
 
     // Single rank, no per-launch timing: record the whole sequence once and replay it (see ctx.h).
-    static const bool no_graph = getenv("VLGP_NO_MGRAPH") != nullptr;
-    const bool use_graph = ctx->world == 1 && !ctx->prof_on && !no_graph;
-    const bool noise_passes = ctx->n_gauss > 0 || P > 2 || getenv("VLGP_NOISE_PASSES") != nullptr;  // (see noise_stats_kernel)
+    const bool use_graph = ctx->world == 1 && !ctx->prof_on && !ctx->sw.no_mgraph;
+    const bool noise_passes = ctx->n_gauss > 0 || P > 2 || ctx->sw.noise_passes;  // (see noise_stats_kernel)
     std::vector<double> key;
     if (use_graph) {
         auto pk = [&](const void* p_) { key.push_back((double)(uintptr_t)p_); };
         pk(us.y); pk(us.x_ones ? nullptr : us.x); pk(us.mu); pk(us.v); pk(us.w); pk(us.dmu); pk(W); pk(ctx->d_a); pk(ctx->d_b);
         pk(ctx->d_noise); pk(ctx->d_da); pk(ctx->d_db); pk(ctx->d_fail_m); pk(ctx->d_gauss);
         for (double v_ : {(double)us.rows, (double)N, (double)L, (double)P, (double)ctx->n_gauss, (double)n_iter,
-                          (double)use_hessian, eps, lr, da_bound, db_bound, (double)noise_passes})
+                          (double)use_hessian, eps, lr, da_bound, db_bound, (double)noise_passes, (double)gen, ctx->sw.mstep_wg_per_cu})
             key.push_back(v_);
         if (ctx->m_graph_exec && key == ctx->m_graph_key) {
             HIPCHK(ctx, hipGraphLaunch(static_cast<hipGraphExec_t>(ctx->m_graph_exec), st));

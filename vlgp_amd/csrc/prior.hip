@@ -466,7 +466,7 @@ int launch_ichol_all(vlgp_ctx* ctx, const std::vector<Prior*>& prs, const double
             vlgp_prof_begin(ctx, VLGP_PROF_PRIOR);
             const int RS = R | 1;
             const size_t lds_wave = 8 * ((size_t)pr.T * RS + 128) + 4 * 64;
-            if (pr.T <= 64 && lds_wave <= 60 * 1024 && !getenv("VLGP_ICHOL_BLOCK")) {
+            if (pr.T <= 64 && lds_wave <= 60 * 1024 && !ctx->sw.ichol_block) {
                 hipLaunchKernelGGL(ichol_exact_wave_kernel, dim3(L), dim3(64), lds_wave, ctx->stream, A, RS);
             } else if (pr.T <= 64) CHK(launch_ichol_t<64>(ctx, A, lds));
             else if (pr.T <= 512) CHK(launch_ichol_t<256>(ctx, A, lds));

@@ -457,8 +457,14 @@ class Engine:
         return _lib.HSTEP_PATHS[p.value]
 
     def reload_switches(self):
-        """Read the VLGP_HSTEP_* debug switches from the environment again (they are cached at creation)."""
+        """Read the library's VLGP_* debug switches from the environment again (all are cached at creation)."""
         self._ck(self.lib.vlgp_debug_reload_switches(self.h))
+
+    def switch(self, name):
+        """The value this handle holds for the debug switch `name` (flag 0 / 1, tri-state -1 / 0 / 1, integer or real)."""
+        v = C.c_double(0)
+        self._ck(self.lib.vlgp_debug_switch(self.h, name.encode(), C.byref(v)))
+        return v.value
 
     def hstep_stats(self):
         """(low-rank evaluations, sum of their predicted ranks, dense evaluations, low-rank rounds re-run densely)."""
