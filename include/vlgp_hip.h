@@ -121,16 +121,19 @@ int vlgp_free_units(vlgp_ctx* ctx, int set);
  * `src` return VLGP_ERR_STATE.  A replicated set takes vlgp_estep (split E-step only: a configuration that kernel
  * family cannot run -- L > 10, N > 1024, long units at R above its limit, short units at effective rank > 32 -- is
  * VLGP_ERR_STATE, never another kernel), vlgp_download_units, vlgp_free_units and vlgp_loglik; every other entry point
- * refuses it with VLGP_ERR_STATE. */
+ * refuses it with VLGP_ERR_STATE.  The same as vlgp_replicate_groups (below) with one channel per group. */
 int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel);
 /* Plug-in rate and log-likelihood of the observations under the set's current posterior (mu, v):
  *   Poisson   rate = trunc_exp(a_n.mu_t + (b x)_tn + 1/2 (a_n^2).v_t)  (the E-step's rate; vb == 0 drops the v term)
  *             ll = y log rate - rate - lgamma(y + 1);   sums[n] = {sum ll, sum y, sum rate, sum lgamma(y + 1)}
  *   Gaussian  rate = eta = a_n.mu_t + (b x)_tn
  *             ll = -log(2 pi noise_n) / 2 - (y - eta)^2 / (2 noise_n);   sums[n] = {sum ll, sum y, sum eta, sum y^2}
- * Plain set: rate (rows, N) row-major or NULL, sums (N, 4), channels in plain order.  Replicated set: only replica k's
- * own held-out channel, on the source rows: rate (rows_src, n_rep) or NULL, sums (n_rep, 4).  Sums cover this handle's
- * units only (no reduction over ranks) and are bitwise reproducible (fixed-order two-stage reduction, no atomics). */
+ * Plain set: rate (rows, N) row-major or NULL, sums (N, 4), channels in plain order.  Replicated set: one slot per
+ * (replica, left-out channel) pair, in the order of the channel list the set was made with -- pair p is channel[p] under
+ * the posterior of the replica that leaves it out, on the source rows: rate (rows_src, n_pairs) or NULL, sums
+ * (n_pairs, 4).  A set made by vlgp_replicate_units has n_pairs == n_rep.  At most 65535 pairs per set (VLGP_ERR_ARG
+ * beyond).  Sums cover this handle's units only (no reduction over ranks) and are bitwise reproducible (fixed-order
+ * two-stage reduction, no atomics). */
 int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums);
 /* Terms of the variational lower bound of a plain set (uploaded or cut; a replicated set is VLGP_ERR_STATE) under its
  * current posterior (mu, v, w), the current parameters and the prior factors the set's lengths are bound to.
@@ -353,6 +356,17 @@ int vlgp_debug_switch(vlgp_ctx* ctx, const char* name, double* value);
  * out[1] the sum of their predicted ranks (even + odd block), out[2] evaluations that took the dense round,
  * out[3] low-rank rounds re-run densely because a rank exceeded the prediction. */
 int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]);
+
+
+/* ---- held-out evaluation: groups of channels --------------------------- */
+/* Leave-group-out replicas (co-smoothing): as vlgp_replicate_units, but replica k leaves out the channels
+ * channel[group_start[k] .. group_start[k+1]) -- vlgp_estep on `dst` runs for replica k what it would run on the units of
+ * `src` with a[:, g] = 0 for every g of that group, bit for bit.  group_start has n_rep + 1 non-decreasing entries,
+ * group_start[0] == 0; every group is non-empty, its channels distinct and in [0, N) (two replicas may share a channel):
+ * otherwise VLGP_ERR_ARG, the message naming the replica, and nothing is changed.  src, dst, aliasing, lifetime and the
+ * entry points that accept the set are those of vlgp_replicate_units.  vlgp_loglik scores the set per (replica, channel)
+ * pair, n_pairs = group_start[n_rep], in the order of channel[]. */
+int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* group_start, const int* channel);
 
 #ifdef __cplusplus
 }

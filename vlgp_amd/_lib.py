@@ -100,6 +100,7 @@ _SIGNATURES = {
     "vlgp_debug_reload_switches": (C.c_int, [_h]),
     "vlgp_debug_switch": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "vlgp_debug_hstep_stats": (C.c_int, [_h, _dp]),
+    "vlgp_replicate_groups": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -116,7 +117,10 @@ def load():
             "or `make -C vlgp_amd/csrc` (hipcc, gfx950). There is no CPU fallback." % path)
     lib = C.CDLL(path)
     for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the header and the library disagree
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # a library built from an older tree
+            raise ImportError("%s does not export %s: rebuild it (`make -C vlgp_amd/csrc`)" % (path, name)) from None
         fn.restype = res
         fn.argtypes = args
     if lib.vlgp_abi_version() != ABI_VERSION:

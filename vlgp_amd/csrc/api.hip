@@ -491,7 +491,8 @@ static void free_set(vlgp_ctx* ctx, UnitSet& us) {
     (void)hipStreamSynchronize(ctx->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     if (us.rep_src >= 0) {  // replicas: y, x, xb are the source's
-        fr(us.mu); fr(us.v); fr(us.w); fr(us.d_rep_ch); fr(us.d_rep_wconst); fr(us.d_rep_xa);
+        fr(us.mu); fr(us.v); fr(us.w); fr(us.d_rep_ch); fr(us.d_rep_pair); fr(us.d_rep_mask); fr(us.d_rep_wconst);
+        fr(us.d_rep_xa);
         ctx->sets[us.rep_src].rep_users--;
         us.d_xb = nullptr;
     } else if (!us.alias) {
@@ -809,8 +810,9 @@ extern "C" int vlgp_free_units(vlgp_ctx* ctx, int set) {
     return VLGP_OK;
 }
 
-// ---- leave-one-out replicas and held-out likelihood ---------------------------
-extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel) {
+// ---- leave-group-out replicas and held-out likelihood --------------------------
+extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* group_start,
+                                     const int* channel) {
     NEED_CTX(ctx);
     ctx->hmom_us = nullptr;
     CHK(vlgp_join_m(ctx));
@@ -818,10 +820,27 @@ extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, 
     UnitSet* s = vlgp_get_set(ctx, src, true);
     UnitSet* d = vlgp_get_set(ctx, dst, false);
     if (!s || !d) return VLGP_ERR_ARG;
-    if (src == dst || n_rep < 1 || !channel) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad replicate arguments");
-    for (int k = 0; k < n_rep; ++k)
-        if (channel[k] < 0 || channel[k] >= ctx->N)
-            return vlgp_fail(ctx, VLGP_ERR_ARG, "replica %d leaves out channel %d, outside [0, %d)", k, channel[k], ctx->N);
+    if (src == dst || n_rep < 1 || !channel || !group_start || group_start[0] != 0)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "bad replicate arguments");
+    // the groups as bit masks (one bit per channel), the pairs' replicas: every argument is checked before any state moves
+    const int nw = (ctx->N + 63) / 64;
+    std::vector<unsigned long long> mask((size_t)n_rep * nw, 0ull);
+    std::vector<int> pair_rep;
+    for (int k = 0; k < n_rep; ++k) {
+        if (group_start[k + 1] <= group_start[k])
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "replica %d leaves out an empty group of channels", k);
+        for (int p = group_start[k]; p < group_start[k + 1]; ++p) {
+            const int n = channel[p];
+            if (n < 0 || n >= ctx->N)
+                return vlgp_fail(ctx, VLGP_ERR_ARG, "replica %d leaves out channel %d, outside [0, %d)", k, n, ctx->N);
+            unsigned long long& wd = mask[(size_t)k * nw + (n >> 6)];
+            if ((wd >> (n & 63)) & 1ull)
+                return vlgp_fail(ctx, VLGP_ERR_ARG, "replica %d leaves out channel %d twice", k, n);
+            wd |= 1ull << (n & 63);
+            pair_rep.push_back(k);
+        }
+    }
+    const int n_pairs = group_start[n_rep];
     if (s->rep_src >= 0 || s->parent >= 0 || s->alias || !s->stage_start.empty())
         return vlgp_fail(ctx, VLGP_ERR_STATE, "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)", src);
     if (d->rep_users > 0)
@@ -840,7 +859,9 @@ extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, 
     d->rep_src = src;
     d->n_rep = n_rep;
     d->rows_src = rs;
-    d->rep_ch.assign(channel, channel + n_rep);
+    d->n_pairs = n_pairs;
+    d->rep_nw = nw;
+    d->rep_ch.assign(channel, channel + n_pairs);
     d->x_ones = s->x_ones;
     d->y = s->y;  // aliased: a copy per replica would be rows x N doubles each
     d->x = s->x;
@@ -851,10 +872,15 @@ extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, 
     CHK(dev_alloc(ctx, &d->v, n_rep * rs * L, false));
     CHK(dev_alloc(ctx, &d->w, n_rep * rs * L, false));
     CHK(dev_alloc(ctx, &d->dmu, n_rep * rs * L, false));
-    HIPCHK(ctx, hipMalloc(&d->d_rep_ch, sizeof(int) * n_rep));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_ch, sizeof(int) * n_pairs));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_pair, sizeof(int) * n_pairs));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_mask, sizeof(unsigned long long) * mask.size()));
     HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * 16 * n_rep));
     HIPCHK(ctx, hipMalloc(&d->d_rep_xa, sizeof(d->rep_xh)));
-    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_ch, channel, sizeof(int) * n_rep, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_ch, channel, sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_pair, pair_rep.data(), sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_mask, mask.data(), sizeof(unsigned long long) * mask.size(), hipMemcpyHostToDevice,
+                               ctx->stream));
     for (int k = 0; k < n_rep; ++k) {
         const int64_t o = k * rs * L;
         HIPCHK(ctx, hipMemcpyAsync(d->mu + o, s->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
@@ -862,9 +888,16 @@ extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, 
         HIPCHK(ctx, hipMemcpyAsync(d->w + o, s->w, nb, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(d->dmu + o, s->dmu, nb, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the channel list is the caller's again)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the channel list is the caller's again, the host tables may go)
     d->valid = true;
     return VLGP_OK;
+}
+
+// leave-one-out replicas: singleton groups
+extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel) {
+    std::vector<int> start((size_t)(n_rep > 0 ? n_rep : 0) + 1);  // (n_rep < 1 is refused there, after the set checks)
+    for (size_t k = 0; k < start.size(); ++k) start[k] = (int)k;
+    return vlgp_replicate_groups(ctx, src, dst, n_rep, start.data(), channel);
 }
 
 extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums) {
@@ -880,8 +913,8 @@ extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double*
     const bool rep = us->rep_src >= 0;
     UnitSet& rows_of = rep ? ctx->sets[us->rep_src] : *us;  // the y / x rows
     if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
-    const int slots = rep ? us->n_rep : ctx->N;
-    const int64_t n_rate = rep ? us->rows_src * us->n_rep : us->rows * ctx->N;
+    const int slots = rep ? us->n_pairs : ctx->N;
+    const int64_t n_rate = rep ? us->rows_src * us->n_pairs : us->rows * ctx->N;
     const int64_t o_sums = rate ? n_rate : 0;
     double* d_rate = nullptr;
     double* d_out = nullptr;

@@ -54,14 +54,21 @@ struct UnitSet {
     int* d_links = nullptr;         // (n_links, 3): first unit, second unit, shared rows
     int n_links = 0;
     bool share_mu = true;           // false once the segments' mu was rebound (constrain_loading "svd")
-    // Replicated set (vlgp_replicate_units): n_rep copies of set rep_src's units, replica-major (unit k M_src + m), replica
-    // k leaving channel rep_ch[k] out of its E-step.  y and xb are the source's (aliased, never freed here); mu, v, w, dmu
-    // are the replicas' own.  The source counts the replica sets that alias it (rep_users) and refuses re-upload / free.
+    // Replicated set (vlgp_replicate_groups; vlgp_replicate_units = singleton groups): n_rep copies of set rep_src's units,
+    // replica-major (unit k M_src + m), replica k leaving a group of channels out of its E-step.  The n_pairs (replica,
+    // left-out channel) pairs are listed in the caller's order: pair p is channel rep_ch[p] of replica rep_pair[p].  The
+    // E-step reads the groups as bit masks, rep_nw = (N + 63) / 64 words per replica, bit n & 63 of word n >> 6 set when
+    // the replica leaves channel n out.  y and xb are the source's (aliased, never freed here); mu, v, w, dmu are the
+    // replicas' own.  The source counts the replica sets that alias it (rep_users) and refuses re-upload / free.
     int rep_src = -1;
     int n_rep = 0;
+    int n_pairs = 0;
+    int rep_nw = 0;
     int64_t rows_src = 0;
     std::vector<int> rep_ch;
-    int* d_rep_ch = nullptr;          // (n_rep)
+    int* d_rep_ch = nullptr;          // (n_pairs) left-out channel of each pair
+    int* d_rep_pair = nullptr;        // (n_pairs) replica of each pair
+    unsigned long long* d_rep_mask = nullptr;  // (n_rep, rep_nw) membership masks
     double* d_rep_wconst = nullptr;   // (n_rep, 16): Gaussian constant of w per replica (estep_split.hip)
     void* d_rep_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
     double rep_xh[8] = {};
@@ -308,7 +315,7 @@ int launch_project(vlgp_ctx* ctx, UnitSet& us, const double* d_proj, const doubl
                    double* d_out);  // mu = y proj - shift; d_out = column sums of y
 int launch_gather(vlgp_ctx* ctx, UnitSet& src, UnitSet& dst, int window);
 // plug-in rates and per-channel log-likelihood sums of a set (evaluate.hip): d_rate (rows, N) for a plain set, (rows_src,
-// n_rep) for a replicated one, or null; d_sums (slots, 4) with slots = N or n_rep, written in a fixed order
+// n_pairs) for a replicated one, or null; d_sums (slots, 4) with slots = N or n_pairs, written in a fixed order
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest

@@ -80,21 +80,24 @@ struct SplitArgs {
     int lat[16];       // their indices
 };
 
-// A replicated set (vlgp_replicate_units): n_rep copies of a source set's units, replica-major, replica k with channel
-// ch[k] left out.  Only the row passes read channels: their EXCL instantiations map a row of replica k to its source
-// row (row - k rows_src) for y and xb, and zero channel ch[k]'s loadings in the record they read -- a compare and select
-// in place, same summation order, so a replica runs bit for bit what the same kernels run with a[:, ch[k]] = 0.
+// A replicated set (vlgp_replicate_groups): n_rep copies of a source set's units, replica-major, replica k with a group
+// of channels left out.  The groups are bit masks, nw = (N + 63) / 64 words per replica: bit n & 63 of mask[k nw + (n >> 6)]
+// is set when replica k leaves channel n out.  Only the row passes read channels: their EXCL instantiations map a row of
+// replica k to its source row (row - k rows_src) for y and xb, and zero the loadings of the group's channels in the
+// record they read -- a bit test and select in place, same summation order, so a replica runs bit for bit what the same
+// kernels run with a[:, g] = 0 for every g of its group.
 // EXCL = false instantiations never read it.  (esplit_ya takes it by value; esplit_pass through SplitArgs::excl, so that
 // the kernel arguments of its existing instantiations -- and with them their code -- stay as they were.)
 struct ExclArgs {
-    const int* ch;         // (n_rep) excluded channel of each replica
+    const unsigned long long* mask;  // (n_rep, nw) the channels each replica leaves out, one bit per channel
     const double* wconst;  // (n_rep, 16): the Gaussian constant of w (wconst) without that channel
     const double* y;       // the source set's y and xb (row-major, rows_src rows)
     const double* xb;
     int64_t rows_src;
     int64_t row_base;      // absolute row of the launch's first row (esplit_ya: by value, set per launch)
     const double* mu_lm;   // the row passes: unshifted latent-major mu -- a lane's row base is A.mu - mu_lm
-};
+};  // (no field for nw: the kernels have N, and the struct -- an argument of every esplit_ya -- keeps its size)
+__host__ __device__ inline int excl_words(int N) { return (N + 63) >> 6; }
 
 // ---------------------------------------------------------------------------------------------------------
 // channel records, Poisson channels first: a[LT] | a^2 / 2 [LT] | b | c (1/noise or 1) | id (integer bits) | pad
@@ -164,19 +167,20 @@ esplit_cols_kernel(int N, int L, int LT, int REC, const double* __restrict__ a, 
     }
 }
 
-// the Gaussian constant of w per replica of a replicated set: wconst of esplit_cols_kernel with channel ch[k] left out
-// (the same fma chain in channel order, the left-out term skipped: with a[:, n] = 0 it adds exactly 0)
+// the Gaussian constant of w per replica of a replicated set: wconst of esplit_cols_kernel with the replica's group left
+// out (the same fma chain in channel order, the left-out terms skipped: with a[:, n] = 0 each adds exactly 0)
 __global__ void __launch_bounds__(256)
-esplit_excl_wconst(int N, int L, int n_rep, const double* __restrict__ a, const double* __restrict__ noise,
-                   const int* __restrict__ gauss, const int* __restrict__ ch, double* __restrict__ wconst) {
+esplit_excl_wconst(int N, int L, int n_rep, int nw, const double* __restrict__ a, const double* __restrict__ noise,
+                   const int* __restrict__ gauss, const unsigned long long* __restrict__ mask,
+                   double* __restrict__ wconst) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_rep * 16) return;
     const int k = i >> 4, l = i & 15;
     double s = 0.0;
     if (l < L) {
-        const int ex = ch[k];
+        const unsigned long long* mk = mask + (int64_t)k * nw;
         for (int n = 0; n < N; ++n)
-            if (gauss[n] && n != ex) s = fma(a[l * N + n] * a[l * N + n], 1.0 / noise[n], s);
+            if (gauss[n] && !((mk[n >> 6] >> (n & 63)) & 1ull)) s = fma(a[l * N + n] * a[l * N + n], 1.0 / noise[n], s);
     }
     wconst[i] = s;
 }
@@ -234,11 +238,14 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
         const int64_t row = w0 + it + r4;
         const bool in = row < rows;
         const double* yr = y + (in ? row : 0) * N;
-        int ex = -1;  // EXCL: the channel this row's replica leaves out
+        // EXCL: the channels this row's replica leaves out; a lane's channels c16 + 16 j (N <= 16 NJ <= 128) lie in
+        // word j / 4 of its mask, at bit c16 + 16 (j % 4)
+        unsigned long long ex[(NJ + 3) / 4] = {};
         if constexpr (EXCL) {
             const int64_t ar = X.row_base + (in ? row : 0), k = ar / X.rows_src;
             yr = X.y + (ar - k * X.rows_src) * N;
-            ex = X.ch[k];
+#pragma unroll
+            for (int q = 0; q < (NJ + 3) / 4; ++q) ex[q] = q < excl_words(N) ? X.mask[k * excl_words(N) + q] >> c16 : 0ull;
         }
         double acc[LT];
 #pragma unroll
@@ -248,7 +255,8 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
             const int n = c16 + 16 * j;
             const double yv = (in && n < N) ? yr[n] : 0.0;
 #pragma unroll
-            for (int l = 0; l < LT; ++l) acc[l] = fma(yv, (EXCL && n == ex) ? 0.0 : cf[j][l], acc[l]);
+            for (int l = 0; l < LT; ++l)
+                acc[l] = fma(yv, (EXCL && ((ex[j / 4] >> (16 * (j % 4))) & 1ull)) ? 0.0 : cf[j][l], acc[l]);
         }
 #pragma unroll
         for (int o = 8; o >= 1; o >>= 1)
@@ -293,20 +301,37 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
     }
     const double* yrow = A.y + rr * N;
     const double* xbrow = HASXB ? A.xb + rr * N : nullptr;
-    int ex = 0, rk = 0;  // EXCL: replica of the row and the channel it leaves out
+    // EXCL: replica of the row, and the word of its mask that holds the channel at hand.  The record id is wave-uniform
+    // and the records of a list come in channel order, so the word changes at most every 64 records (never for
+    // N <= 64); the replica is per lane -- a wave may straddle two -- and so is the word
+    int rk = 0, exw = 0;
+    unsigned long long ex = 0;
+    const unsigned long long* exm = nullptr;
     ExclArgs X;
     if constexpr (EXCL) {
         X = *A.excl;
         X.row_base = A.mu - X.mu_lm;
         const int64_t ar = X.row_base + rr, k = ar / X.rows_src, sr = ar - k * X.rows_src;
         rk = (int)k;
-        ex = X.ch[k];
+        exm = X.mask + k * excl_words(N);
+        ex = exm[0];
         yrow = X.y + sr * N;
         xbrow = HASXB ? X.xb + sr * N : nullptr;
     }
-    // entry i < 2 LT of a channel record as the row sees it: 0 for the channel its replica leaves out (EXCL)
-    auto rec = [&](const double (&rv)[REC], int i) -> double {
-        if constexpr (EXCL) return (int)__double_as_longlong(rv[2 * LT + 2]) == ex ? 0.0 : rv[i];
+    // whether the row's replica leaves the record's channel out (EXCL), and entry i < 2 LT of the record as the row
+    // sees it: 0 for such a channel
+    auto left_out = [&](const double (&rv)[REC]) -> bool {
+        if constexpr (EXCL) {
+            const int id = (int)__double_as_longlong(rv[2 * LT + 2]);
+            if ((id >> 6) != exw) {
+                exw = id >> 6;
+                ex = exm[exw];
+            }
+            return (ex >> (id & 63)) & 1ull;
+        } else return false;
+    };
+    auto rec = [&](const double (&rv)[REC], int i, bool out) -> double {
+        if constexpr (EXCL) return out ? 0.0 : rv[i];
         else return rv[i];
     };
     // the residual pass subtracts from ya at the end: fetched here, by the wave that writes (a load after the channel
@@ -352,8 +377,9 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
         auto body = [&](const double (&rv)[REC]) {
             const int n = (int)__double_as_longlong(rv[2 * LT + 2]);
             const double yc = yrow[n] * rv[2 * LT + 1];
+            const bool out = left_out(rv);
 #pragma unroll
-            for (int l = 0; l < LT; ++l) acc[l] = fma(yc, rec(rv, l), acc[l]);
+            for (int l = 0; l < LT; ++l) acc[l] = fma(yc, rec(rv, l, out), acc[l]);
         };
         double ra_[REC], rb_[REC];
         load_rec(0, ra_);
@@ -369,13 +395,14 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
         // one Poisson channel: rate = exp(min(eta + v.a^2/2, 10)) (math.trunc_exp, vlgp/math.py:24-38)
         auto poisson = [&](const double (&rv)[REC]) {
             double eta = HASXB ? xbrow[(int)__double_as_longlong(rv[2 * LT + 2])] : rv[2 * LT];
+            const bool out = left_out(rv);
 #pragma unroll
-            for (int l = 0; l < LT; ++l) eta = fma(mr[l], rec(rv, l), eta);
+            for (int l = 0; l < LT; ++l) eta = fma(mr[l], rec(rv, l, out), eta);
 #pragma unroll
-            for (int l = 0; l < LT; ++l) eta = fma(vr[l], rec(rv, LT + l), eta);
+            for (int l = 0; l < LT; ++l) eta = fma(vr[l], rec(rv, LT + l, out), eta);
             const double rate = trunc_exp_tab256(eta, etab);
 #pragma unroll
-            for (int l = 0; l < LT; ++l) acc[l] = fma(rate, rec(rv, KIND == SP_RES ? l : LT + l), acc[l]);
+            for (int l = 0; l < LT; ++l) acc[l] = fma(rate, rec(rv, KIND == SP_RES ? l : LT + l, out), acc[l]);
         };
         double ra_[REC], rb_[REC];
         if (np > p_lo) {
@@ -393,11 +420,12 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
             for (int i = g_lo; i < ntot; ++i) {
                 load_rec(i, ra_);
                 double eta = HASXB ? xbrow[(int)__double_as_longlong(ra_[2 * LT + 2])] : ra_[2 * LT];
+                const bool out = left_out(ra_);
 #pragma unroll
-                for (int l = 0; l < LT; ++l) eta = fma(mr[l], rec(ra_, l), eta);
+                for (int l = 0; l < LT; ++l) eta = fma(mr[l], rec(ra_, l, out), eta);
                 const double mval = eta * ra_[2 * LT + 1];
 #pragma unroll
-                for (int l = 0; l < LT; ++l) acc[l] = fma(mval, rec(ra_, l), acc[l]);
+                for (int l = 0; l < LT; ++l) acc[l] = fma(mval, rec(ra_, l, out), acc[l]);
             }
         }
     }
@@ -2015,7 +2043,7 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     ExclArgs XA{};  // replicated set: its replica table, source rows, per-replica wconst
     if (rep) {
         const UnitSet& src = ctx->sets[us.rep_src];
-        XA.ch = us.d_rep_ch;
+        XA.mask = us.d_rep_mask;
         XA.wconst = us.d_rep_wconst;
         XA.y = src.y;
         XA.xb = E.xb;  // (launch_estep points the replicas' xb at the source's, refreshed)
@@ -2023,7 +2051,7 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
         XA.row_base = 0;
         XA.mu_lm = nullptr;  // (set below, with the latent-major copies)
         hipLaunchKernelGGL(esplit_excl_wconst, dim3((unsigned)((us.n_rep * 16 + 255) / 256)), dim3(256), 0, ctx->stream, N,
-                           L, us.n_rep, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_ch, us.d_rep_wconst);
+                           L, us.n_rep, us.rep_nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_mask, us.d_rep_wconst);
         HIPCHK(ctx, hipGetLastError());
     }
 

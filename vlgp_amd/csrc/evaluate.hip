@@ -9,10 +9,11 @@
 //             sums = ll | y | eta | y^2
 //
 // ll_rows: one lane per row.  A plain set walks all N channels of the row in plain channel order (0 ... N-1); a
-// replicated set (vlgp_replicate_units) takes blockIdx.y as the replica and evaluates its one held-out channel on the
-// source rows.  The four sums of each (channel, workgroup) are reduced in a fixed order -- a butterfly over the wave,
-// then the four waves in order -- into a partial per workgroup; ll_finish adds the partials of a channel in workgroup
-// order.  No atomics: the sums are the same bits on every run.
+// replicated set (vlgp_replicate_groups) takes blockIdx.y as a (replica, left-out channel) pair, in the order the
+// caller listed the channels, and evaluates that channel under that replica's posterior on the source rows.  The four
+// sums of each (channel, workgroup) are reduced in a fixed order -- a butterfly over the wave, then the four waves in
+// order -- into a partial per workgroup; ll_finish adds the partials of a channel in workgroup order.  No atomics: the
+// sums are the same bits on every run.
 #include "ctx.h"
 #include "fast_exp.h"
 
@@ -30,9 +31,10 @@ struct LlArgs {
     const double* mu;      // (rows_total, L)
     const double* v;
     int vb;
-    const int* ch;         // replicated set: held-out channel per replica, else null
-    int n_rep;
-    double* rate;          // plain (rows, N), replicated (rows, n_rep), or null
+    const int* ch;         // replicated set: left-out channel of each pair, else null
+    const int* pair_rep;   // replicated set: replica of each pair
+    int n_pairs;
+    double* rate;          // plain (rows, N), replicated (rows, n_pairs), or null
     double* part;          // (slots, n_blk, 4)
 };
 
@@ -48,8 +50,8 @@ __global__ void __launch_bounds__(256) ll_rows(LlArgs A) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool in = r < A.rows;
     const int64_t row = in ? r : 0;
-    const int k = blockIdx.y;                       // replica (0 for a plain set)
-    const int64_t mrow = (int64_t)k * A.rows + row;  // row of mu, v in the (replicated) set
+    const int k = blockIdx.y;                       // pair (0 for a plain set)
+    const int64_t mrow = (int64_t)(A.ch ? A.pair_rep[k] : 0) * A.rows + row;  // row of mu, v in the (replicated) set
     const int n0 = A.ch ? A.ch[k] : 0, n1 = A.ch ? n0 + 1 : A.N;
     for (int n = n0; n < n1; ++n) {
         double eta = A.xb ? A.xb[row * A.N + n] : A.b[n];
@@ -61,7 +63,7 @@ __global__ void __launch_bounds__(256) ll_rows(LlArgs A) {
             s[0] = -0.5 * log(2.0 * M_PI * nz) - d * d / (2.0 * nz);
             s[2] = eta;
             s[3] = yv * yv;
-            if (A.rate && in) A.rate[A.ch ? row * A.n_rep + k : row * A.N + n] = eta;
+            if (A.rate && in) A.rate[A.ch ? row * A.n_pairs + k : row * A.N + n] = eta;
         } else {
             if (A.vb)
                 for (int l = 0; l < A.L; ++l) {
@@ -73,7 +75,7 @@ __global__ void __launch_bounds__(256) ll_rows(LlArgs A) {
             s[0] = yv * log(lam) - lam - lg;
             s[2] = lam;
             s[3] = lg;
-            if (A.rate && in) A.rate[A.ch ? row * A.n_rep + k : row * A.N + n] = lam;
+            if (A.rate && in) A.rate[A.ch ? row * A.n_pairs + k : row * A.N + n] = lam;
         }
         s[1] = yv;
         const int buf = n & 1;
@@ -118,14 +120,16 @@ int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_
     A.mu = us.mu; A.v = us.v;
     A.vb = vb ? 1 : 0;
     A.ch = rep ? us.d_rep_ch : nullptr;
-    A.n_rep = rep ? us.n_rep : 0;
+    A.pair_rep = rep ? us.d_rep_pair : nullptr;
+    A.n_pairs = rep ? us.n_pairs : 0;
     A.rate = d_rate;
-    const int slots = rep ? us.n_rep : ctx->N;
+    const int slots = rep ? us.n_pairs : ctx->N;
     if (A.rows < 1 || A.n_blk < 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on an empty set");
-    if (rep && us.n_rep > 65535) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: at most 65535 replicas per set");
+    if (rep && us.n_pairs > 65535)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: at most 65535 (replica, channel) pairs per set");
     CHK(vlgp_ensure_work(ctx, (int64_t)slots * A.n_blk * 4 + 8));
     A.part = ctx->d_work;
-    hipLaunchKernelGGL(ll_rows, dim3((unsigned)A.n_blk, (unsigned)(rep ? us.n_rep : 1)), dim3(256), 0, ctx->stream, A);
+    hipLaunchKernelGGL(ll_rows, dim3((unsigned)A.n_blk, (unsigned)(rep ? us.n_pairs : 1)), dim3(256), 0, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(ll_finish, dim3((unsigned)((slots * 4 + 255) / 256)), dim3(256), 0, ctx->stream, slots, A.n_blk,
                        ctx->d_work, d_sums);

@@ -66,7 +66,7 @@ class Engine:
             check(rc, None)
         self.h = h
         self.sets = {}  # set id -> (M, rows, offsets)
-        self.replicas = {}  # replicated set id -> its held-out channels (Engine.replicate)
+        self.replicas = {}  # replicated set id -> (replicas, its held-out channels, one per pair) (Engine.replicate)
         self.state_epoch = 0  # bumped by every call that can change a set's mu (em_iteration's norm cache keys on it)
         self.rank, self.world = 0, 1
         self.host_exchange = False
@@ -190,25 +190,38 @@ class Engine:
         self.sets.pop(set_id, None)
         self.replicas.pop(set_id, None)
 
-    def replicate(self, src, dst, channels):
-        """Set ``dst`` := one replica of set ``src`` per entry of ``channels``, replica k leaving channel
-        ``channels[k]`` out of its E-step (vlgp_replicate_units): replica-major units, y / x aliased to ``src``."""
+    def replicate(self, src, dst, channels=None, groups=None):
+        """Set ``dst`` := replicas of set ``src``, replica-major units, y / x aliased to ``src``.  ``channels``: one
+        replica per entry, replica k leaving channel ``channels[k]`` out of its E-step (vlgp_replicate_units).
+        ``groups``: one replica per list of channels, replica k leaving ``groups[k]`` out (vlgp_replicate_groups);
+        ``loglik`` then scores one slot per (replica, channel) pair, the groups concatenated in order."""
+        if (channels is None) == (groups is None):
+            raise ValueError("replicate takes channels or groups")
         self.state_epoch += 1
-        ch = np.ascontiguousarray(channels, dtype=np.int32)
-        self._ck(self.lib.vlgp_replicate_units(self.h, int(src), int(dst), len(ch), iptr(ch)))
+        if groups is None:
+            ch = np.ascontiguousarray(channels, dtype=np.int32)
+            k = len(ch)
+            self._ck(self.lib.vlgp_replicate_units(self.h, int(src), int(dst), k, iptr(ch)))
+        else:
+            groups = [np.asarray(g, dtype=np.int32).reshape(-1) for g in groups]
+            k = len(groups)
+            start = np.zeros(k + 1, dtype=np.int32)
+            np.cumsum([len(g) for g in groups], out=start[1:])
+            ch = np.ascontiguousarray(np.concatenate(groups) if k else np.zeros(0), dtype=np.int32)
+            self._ck(self.lib.vlgp_replicate_groups(self.h, int(src), int(dst), k, iptr(start), iptr(ch)))
         m, rows, off = self.sets[src]
-        k = len(ch)
         roff = np.concatenate([r * rows + off[:-1] for r in range(k)] + [np.array([k * rows], dtype=np.int64)])
         self.sets[dst] = (k * m, k * rows, roff)
-        self.replicas[dst] = ch
+        self.replicas[dst] = (k, ch)
 
     def loglik(self, set_id, vb=True, want_rate=False):
         """Plug-in rates and per-channel log-likelihood sums of a set (vlgp_loglik): ``(sums, rate)``, sums
-        (slots, 4) and rate (rows, slots) or None; slots = N for a plain set, the replicas for a replicated one."""
+        (slots, 4) and rate (rows, slots) or None; slots = N for a plain set, the (replica, left-out channel) pairs in
+        the order of the channel list for a replicated one (rows: the source set's)."""
         _, rows, _ = self.sets[set_id]
-        n_rep = self.replicas.get(set_id)
-        slots = self.N if n_rep is None else len(n_rep)
-        rows_out = rows if n_rep is None else rows // max(len(n_rep), 1)
+        rep = self.replicas.get(set_id)
+        slots = self.N if rep is None else len(rep[1])
+        rows_out = rows if rep is None else rows // max(rep[0], 1)
         sums = np.empty((slots, 4))
         rate = np.empty((rows_out, slots)) if want_rate else None
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))

@@ -12,9 +12,14 @@ Definitions (the tests hold the code to them).  For channel ``n`` at row ``t`` o
   ``mu = v = w = 0`` (channel ``n`` cannot leak in through the factor-analysis start), ``n_iter`` E-step iterations;
   channel ``n`` is then predicted from those latents with its ORIGINAL loading.  Its regressors (its own spike history
   when ``history > 0``) enter its prediction as the model defines: only the latents are inferred without it.
+- leave-group-out (co-smoothing) for a set ``g`` of channels: the same with ``a[:, g] = 0`` -- one inference for the
+  whole set -- and every channel of ``g`` predicted from those latents with its original loading.  Singleton groups are
+  leave-one-out, bit for bit.
 - bits per spike of a Poisson channel: ``(LL_model - LL_null) / (sum y * ln 2)``, ``LL_null`` the log-likelihood of a
   constant rate at the channel's mean count over the evaluated rows (the ``lgamma`` terms cancel).  Gaussian channels,
   and channels without a spike, get NaN.
+- co-smoothing bits per spike: ``co_bps = (sum ll - sum ll_null) / (sum n_spikes * ln 2)``, the sums over the Poisson
+  channels with at least one spike (in channel-list order); NaN when there is none.
 
 Variational lower bound (``elbo``).  For one trial of length ``T``, latent ``l``, ``G = params["cholesky"][T][l]`` with
 its all-zero columns dropped (``T x r``), ``w = w[:, l]``, ``mu = mu[:, l]``:
@@ -40,8 +45,8 @@ from . import engine as E
 from ._lib import VlgpError
 from .api import bind_priors
 
-__all__ = ["loglik", "leave_one_out", "plan_chunks", "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo",
-           "elbo_from_terms"]
+__all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
+           "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms"]
 
 SET_TEST, SET_REPLICAS = 0, 2
 
@@ -264,5 +269,123 @@ def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto
         "channels": channels,
         "rate": [rate[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))],
         "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
+        "n_failed": int(n_failed), "path": used,
+    }
+
+
+def channel_folds(n_channels, n_folds, seed=0):
+    """``n_folds`` sorted index lists that partition ``range(n_channels)``, sizes differing by at most one: the
+    channels in the order of ``np.random.default_rng(seed).permutation(n_channels)``, dealt round-robin.  A
+    deterministic function of its arguments."""
+    n_channels, n_folds = int(n_channels), int(n_folds)
+    if not 1 <= n_folds <= n_channels:
+        raise ValueError("need 1 <= n_folds <= n_channels, got %d folds for %d channels" % (n_folds, n_channels))
+    perm = np.random.default_rng(seed).permutation(n_channels)
+    return [sorted(int(c) for c in perm[f::n_folds]) for f in range(n_folds)]
+
+
+def co_bits_per_spike(ll, ll_null, n_spikes):
+    """``(sum ll - sum ll_null) / (sum n_spikes * ln 2)`` over the channels with a finite ``ll_null`` (Poisson) and at
+    least one spike; NaN when there is none."""
+    ll, ll_null, ny = (np.asarray(x, dtype=float) for x in (ll, ll_null, n_spikes))
+    use = np.isfinite(ll_null) & (ny > 0)
+    if not use.any():
+        return float("nan")
+    return float((np.sum(ll[use]) - np.sum(ll_null[use])) / (np.sum(ny[use]) * math.log(2.0)))
+
+
+def _check_groups(groups, N):
+    groups = [[int(c) for c in g] for g in groups]
+    flat = [c for g in groups for c in g]
+    if not groups or any(not g for g in groups):
+        raise ValueError("every group needs at least one channel")
+    if min(flat) < 0 or max(flat) >= N:
+        raise ValueError("group channels must lie in [0, %d)" % N)
+    if len(set(flat)) != len(flat):
+        raise ValueError("groups must be pairwise disjoint sets of distinct channels")
+    if any(len(g) == N for g in groups):
+        raise ValueError("a group may not hold every channel: nothing would be left to infer the latents from")
+    return groups
+
+
+def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_iter=None, path="auto",
+                    max_replicas=None, device=0):
+    """Leave-group-out (co-smoothing) prediction of held-out trials (module docstring for the definitions).
+
+    As ``leave_one_out``, with a set of channels where it has one.  ``groups``: a list of channel lists, non-empty,
+    pairwise disjoint, none holding every channel (default ``channel_folds(N, min(n_folds, N), seed)``).  For every
+    group the latents are inferred from a zero start, ``n_iter`` E-step iterations, with the group's loadings zeroed, and
+    every channel of the group is predicted from them with its original loading.  ``path``: ``"batched"`` runs one
+    replica of the test set per group in one E-step (``vlgp_replicate_groups``), ``max_replicas`` whole groups at a
+    time; ``"sequential"`` one E-step per group; ``"auto"`` the batched path unless the device refuses it.
+
+    Returns a dict: ``groups``; ``channels``, the groups concatenated in order; ``group_of``, the group index of each of
+    those channels; ``rate``, a list per trial of (T, len(channels)); per channel ``ll``, ``ll_null``, ``n_spikes``,
+    ``bits_per_spike``; ``co_bps``; ``n_failed``; ``path``."""
+    if path not in ("auto", "batched", "sequential"):
+        raise ValueError("path must be 'auto', 'batched' or 'sequential'")
+    N, L = int(params["ydim"]), int(params["zdim"])
+    groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
+    channels = [c for g in groups for c in g]
+    group_of = [k for k, g in enumerate(groups) for _ in g]
+    n_iter = int(config["max_iter"] if n_iter is None else n_iter)
+    vb = config["method"] == "VB"
+    dmu_bound = config["dmu_bound"]
+    a = np.array(params["a"], dtype=float)
+    b = np.array(params["b"], dtype=float)
+    noise = np.array(params["noise"], dtype=float)
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    rows = int(sum(lengths))
+    units = [{"y": tr["y"], "x": tr.get("x"), "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))}
+             for tr, T in zip(trials, lengths)]
+    K = len(channels)
+    rate = np.empty((rows, K))
+    sums = np.empty((K, 4))
+    n_failed = 0
+    used = "batched" if path != "sequential" else "sequential"
+    eng, gauss = _engine(params, device)
+    with eng:
+        eng.set_params(a, b, noise)
+        eng.upload(SET_TEST, units)
+        bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
+        if used == "batched":
+            cap = default_max_replicas(rows, L) if max_replicas is None else int(max_replicas)
+            done = 0
+            try:
+                for chunk in plan_chunks(groups, cap):
+                    n = sum(len(g) for g in chunk)
+                    eng.replicate(SET_TEST, SET_REPLICAS, groups=chunk)
+                    n_failed += eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
+                    s, r = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
+                    eng.free_units(SET_REPLICAS)
+                    sums[done:done + n] = s
+                    rate[:, done:done + n] = r
+                    done += n
+            except VlgpError as err:
+                if path == "batched" or not _is_refusal(err):
+                    raise
+                if SET_REPLICAS in eng.sets:
+                    eng.free_units(SET_REPLICAS)
+                used, n_failed = "sequential", 0
+        if used == "sequential":
+            done = 0
+            for g in groups:
+                a_out = a.copy()
+                a_out[:, g] = 0.0
+                eng.set_params(a_out, b, noise)
+                eng.upload(SET_TEST, units)  # (mu = v = w = 0 again)
+                n_failed += eng.estep(SET_TEST, n_iter, dmu_bound, vb)
+                eng.set_params(a, b, noise)
+                s, r = eng.loglik(SET_TEST, vb=vb, want_rate=True)
+                sums[done:done + len(g)] = s[g]
+                rate[:, done:done + len(g)] = r[:, g]
+                done += len(g)
+    ll, ll_null, ny, bps = bits_per_spike(sums, rows, gauss[channels])
+    bounds = np.cumsum([0] + lengths)
+    return {
+        "groups": groups, "channels": channels, "group_of": group_of,
+        "rate": [rate[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))],
+        "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
+        "co_bps": co_bits_per_spike(ll, ll_null, ny),
         "n_failed": int(n_failed), "path": used,
     }

@@ -1,0 +1,105 @@
+"""Choice of the number of latents by cross-validated co-smoothing.
+
+``cross_validate`` holds out folds of trials, fits every candidate ``n_factors`` on the others and scores it on the
+held-out trials with ``evaluation.leave_group_out``: the latents of a test trial are inferred from all channels but a
+fold, that fold is predicted, and the prediction is scored in bits per spike.  Trial folds and channel folds are drawn
+once and shared by every candidate, so the candidates are compared on paired folds.  One process, one GPU.
+"""
+import numpy as np
+
+from .api import fit
+from .evaluation import channel_folds, leave_group_out
+
+__all__ = ["cross_validate", "trial_folds"]
+
+
+def trial_folds(n_trials, n_folds, seed=0):
+    """``n_folds`` contiguous blocks (sizes differing by at most one) of a seeded permutation of ``range(n_trials)``."""
+    n_trials, n_folds = int(n_trials), int(n_folds)
+    if not 2 <= n_folds <= n_trials:
+        raise ValueError("need 2 <= n_trial_folds <= number of trials, got %d folds for %d trials" % (n_folds, n_trials))
+    perm = np.random.default_rng(seed).permutation(n_trials)
+    return [[int(i) for i in block] for block in np.array_split(perm, n_folds)]
+
+
+def _fresh(trials, index):
+    """New trial dicts holding copies of the observations (and regressors) of ``trials[i]``, nothing else."""
+    out = []
+    for i in index:
+        tr = {"y": np.array(trials[i]["y"], dtype=float)}
+        if trials[i].get("x") is not None:
+            tr["x"] = np.array(trials[i]["x"], dtype=float)
+        out.append(tr)
+    return out
+
+
+def _seeded_fit(seed, trials, n_factors, **kwargs):
+    """``fit`` with NumPy's global generator seeded (``fit`` draws the subsample of its factor-analysis start from it, as
+    the reference does), the caller's generator state put back afterwards: the same arguments give the same fit."""
+    state = np.random.get_state()
+    np.random.seed(seed)
+    try:
+        return fit(trials, n_factors, **kwargs)
+    finally:
+        np.random.set_state(state)
+
+
+def best_candidate(n_factors_list, mean_co_bps):
+    """The candidate with the largest mean; the smallest ``n_factors`` among equals; never one whose mean is NaN
+    (None when every mean is NaN)."""
+    best = None
+    for n, m in zip(n_factors_list, mean_co_bps):
+        if np.isnan(m):
+            continue
+        if best is None or m > best[1] or (m == best[1] and n < best[0]):
+            best = (n, m)
+    return None if best is None else best[0]
+
+
+def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, seed=0, n_iter=None, device=0,
+                   **fit_kwargs):
+    """Score every ``n_factors`` of ``n_factors_list`` by co-smoothing bits per spike on held-out trials.
+
+    For every trial fold and candidate: ``fit`` on fresh copies of the other trials (``fit_kwargs`` are ``fit``'s),
+    then ``leave_group_out`` on copies of the fold with the fit's parameters and the shared channel folds (``n_iter``
+    E-step iterations, default the fit's ``max_iter``).  Every fit starts with ``np.random.seed(seed)`` (the state of
+    the caller's generator is restored), so a second call returns the same bits.  The caller's trial dicts are not
+    written and their posteriors are not read.  A candidate whose fit or evaluation raises is recorded as NaN for that
+    fold, the exception text goes into ``errors`` and the sweep continues.
+
+    Returns a dict: ``n_factors``; ``trial_folds`` (test-trial indices per fold); ``channel_folds``; ``co_bps``
+    (candidates, trial folds); ``bits_per_spike`` (candidates, trial folds, N), per channel in plain order;
+    ``n_failed`` (candidates, trial folds); ``mean_co_bps`` (candidates); ``best``; ``errors``, a list of
+    ``(n_factors, fold, text)``."""
+    if "comm" in fit_kwargs:
+        raise ValueError("cross_validate runs on one process: it takes no comm")
+    n_factors_list = [int(n) for n in n_factors_list]
+    if not n_factors_list or min(n_factors_list) < 1:
+        raise ValueError("n_factors_list must hold positive integers")
+    N = int(trials[0]["y"].shape[1])
+    t_folds = trial_folds(len(trials), n_trial_folds, seed)
+    c_folds = channel_folds(N, n_channel_folds, seed)
+    order = np.argsort([c for g in c_folds for c in g])  # channel-list order -> plain channel order
+    shape = (len(n_factors_list), len(t_folds))
+    co_bps = np.full(shape, np.nan)
+    bps = np.full(shape + (N,), np.nan)
+    n_failed = np.zeros(shape, dtype=int)
+    errors = []
+    for f, test_idx in enumerate(t_folds):
+        held = set(test_idx)
+        train_idx = [i for i in range(len(trials)) if i not in held]
+        for c, n in enumerate(n_factors_list):
+            try:
+                fitted = _seeded_fit(seed, _fresh(trials, train_idx), n, device=device, verbose=False, **fit_kwargs)
+                got = leave_group_out(_fresh(trials, test_idx), fitted["params"], fitted["config"], groups=c_folds,
+                                      n_iter=n_iter, device=device)
+            except Exception as err:  # (the sweep goes on: one candidate's failure is a result, not the end)
+                errors.append((n, f, "%s: %s" % (type(err).__name__, err)))
+                continue
+            co_bps[c, f] = got["co_bps"]
+            bps[c, f] = got["bits_per_spike"][order]
+            n_failed[c, f] = got["n_failed"]
+    mean = np.array([np.mean(row) for row in co_bps])  # (NaN as soon as one fold of the candidate failed)
+    return {"n_factors": n_factors_list, "trial_folds": t_folds, "channel_folds": c_folds, "co_bps": co_bps,
+            "bits_per_spike": bps, "n_failed": n_failed, "mean_co_bps": mean,
+            "best": best_candidate(n_factors_list, mean), "errors": errors}
