@@ -8,11 +8,10 @@ import pytest
 from scipy.special import gammaln
 
 from conftest import relerr
-from oracle import vlgp_oracle as O
+from heldout_numpy import STAGE, problem, rate_ll, restated
 
 pytestmark = pytest.mark.gpu
 
-STAGE = 1e-9  # (tests/test_gpu_evaluation.py: the tolerance of one restated stage)
 GROUPS = [[0, 5, 13], [2], [7, 8, 9, 10]]
 
 
@@ -23,70 +22,12 @@ def V():
     return vlgp_amd
 
 
-def _problem(seed=3, M=6, T=150, N=14, L=3, n_gauss=0, lengths=None, method="VB", max_iter=4):
-    """The problems of tests/test_gpu_evaluation.py (x == 1)."""
-    from vlgp_amd import get_config, synth
-
-    trials = synth.make_trials(M, T, N, min(L, 3), seed=seed, n_gauss=n_gauss, lengths=lengths)
-    rng = np.random.default_rng(seed)
-    for tr in trials:
-        tr["x"] = np.ones((tr["y"].shape[0], 1, N))
-    y = np.concatenate([tr["y"] for tr in trials])
-    b = np.zeros((1, N))
-    b[0] = np.log(np.maximum(y.mean(0), 1e-3))
-    b[0, N - n_gauss:] = y[:, N - n_gauss:].mean(0) if n_gauss else b[0, N - n_gauss:]
-    a = 0.3 * rng.standard_normal((L, N))
-    if L > 10:
-        a *= 5.0 / L
-    lik = np.array(["poisson"] * (N - n_gauss) + ["gaussian"] * n_gauss)
-    noise = np.ones(N)
-    noise[N - n_gauss:] = 0.5 + rng.random(n_gauss)
-    params = {"ydim": N, "zdim": L, "xdim": 1, "a": a, "b": b, "noise": noise, "omega": np.linspace(2e-2, 1e-3, L),
-              "sigma": np.ones(L), "rank": 50, "likelihood": lik}
-    return trials, params, get_config(max_iter=max_iter, method=method)
-
-
-def _rate_ll(y, x, mu, v, a, b, noise, gauss, vb):
-    """Plug-in rate (Gaussian: eta) and log-likelihood, (T, N) each."""
-    eta = O.linear_predictor(x, mu, a, b)
-    lam = np.exp(np.minimum(eta + (0.5 * (v @ a ** 2) if vb else 0.0), 10.0))
-    llp = y * np.log(lam) - lam - gammaln(y + 1.0)
-    llg = -0.5 * np.log(2 * np.pi * noise) - (y - eta) ** 2 / (2 * noise)
-    return np.where(gauss, eta, lam), np.where(gauss, llg, llp)
-
-
-def _restated(trials, params, config, groups):
-    """Per trial (T, n_pairs) rates and per pair ll, pairs in the order of the concatenated groups."""
-    a, b, noise = params["a"], params["b"], params["noise"]
-    L = params["zdim"]
-    gauss = np.asarray(params["likelihood"]) == "gaussian"
-    vb = config["method"] == "VB"
-    rates, lls = [], np.zeros(sum(len(g) for g in groups))
-    for tr in trials:
-        T = tr["y"].shape[0]
-        G = O.build_prior([T], params["omega"], params["sigma"], 50)[T]
-        cols, i = [], 0
-        for g in groups:
-            a0 = a.copy()
-            a0[:, g] = 0.0
-            z = np.zeros((T, L))
-            mu, v, _, _, _ = O.estep_unit(tr["y"], tr["x"], z, z, z, a0, b, noise, gauss, G, config["max_iter"],
-                                          config["dmu_bound"], vb)
-            r, ll = _rate_ll(tr["y"], tr["x"], mu, v, a, b, noise, gauss, vb)
-            for n in g:
-                cols.append(r[:, n])
-                lls[i] += ll[:, n].sum()
-                i += 1
-        rates.append(np.stack(cols, axis=1))
-    return rates, lls
-
-
 def _assert_matches_restatement(got, trials, params, config, groups, path="batched"):
     chans = [c for g in groups for c in g]
     assert got["groups"] == groups and got["channels"] == chans
     assert got["group_of"] == [k for k, g in enumerate(groups) for _ in g]
     assert got["path"] == path and got["n_failed"] == 0
-    want_rate, want_ll = _restated(trials, params, config, groups)
+    want_rate, want_ll = restated(trials, params, config, groups)
     for g, w in zip(got["rate"], want_rate):
         assert g.shape == w.shape
         assert relerr(g, w) < STAGE
@@ -104,7 +45,7 @@ def test_leave_group_out_matches_restatement(V, case):
     # (900 rows: no multiple of 64, so waves of the row passes straddle two replicas)
     kw = {"mixed": {"n_gauss": 3}, "ragged": {"lengths": [150, 120, 150, 120, 150, 120]}, "short": {"T": 50},
           "map": {"method": "MAP"}}[case]
-    trials, params, config = _problem(seed=11, **kw)
+    trials, params, config = problem(seed=11, **kw)
     got = V.evaluation.leave_group_out(trials, params, config, groups=GROUPS)
     _assert_matches_restatement(got, trials, params, config, GROUPS)
 
@@ -112,7 +53,7 @@ def test_leave_group_out_matches_restatement(V, case):
 def test_group_of_several_gaussian_channels(V):
     # (the Gaussian channels are 11, 12, 13: the per-replica constant of w skips two terms of its chain for group 0)
     groups = [[11, 13, 4], [12], [0, 1]]
-    trials, params, config = _problem(seed=11, n_gauss=3)
+    trials, params, config = problem(seed=11, n_gauss=3)
     got = V.evaluation.leave_group_out(trials, params, config, groups=groups)
     _assert_matches_restatement(got, trials, params, config, groups)
 
@@ -121,7 +62,7 @@ def test_group_of_several_gaussian_channels(V):
 def test_groups_on_both_sides_of_a_mask_word(V, n_gauss):
     # (n_gauss = 6: channels 64 ... 69 are Gaussian, so the constant of w reads the second mask word too)
     groups = [[63, 64, 69], [0, 1], [31, 32, 33, 65]]
-    trials, params, config = _problem(seed=29, M=3, T=80, N=70, L=2, n_gauss=n_gauss)
+    trials, params, config = problem(seed=29, M=3, T=80, N=70, L=2, n_gauss=n_gauss)
     got = V.evaluation.leave_group_out(trials, params, config, groups=groups)
     _assert_matches_restatement(got, trials, params, config, groups)
 
@@ -130,10 +71,10 @@ def test_groups_on_both_sides_of_a_mask_word(V, n_gauss):
 def test_batched_equals_sequential_bit_for_bit(V, monkeypatch, shape):
     if shape == "long":
         monkeypatch.setenv("VLGP_ESTEP_LSPLIT", "1")
-        trials, params, config = _problem(seed=13, n_gauss=2)
+        trials, params, config = problem(seed=13, n_gauss=2)
     else:
         monkeypatch.setenv("VLGP_ESTEP_SPLIT", "1")
-        trials, params, config = _problem(seed=13, T=50, n_gauss=2)
+        trials, params, config = problem(seed=13, T=50, n_gauss=2)
     ev = V.evaluation
 
     def same(x, z):
@@ -151,7 +92,7 @@ def test_batched_equals_sequential_bit_for_bit(V, monkeypatch, shape):
 
 @pytest.mark.parametrize("channels", [None, [9, 2, 13]])
 def test_singleton_groups_equal_leave_one_out(V, channels):
-    trials, params, config = _problem(seed=11, n_gauss=3)
+    trials, params, config = problem(seed=11, n_gauss=3)
     chans = list(range(params["ydim"])) if channels is None else channels
     one = V.evaluation.leave_one_out(trials, params, config, channels=channels)
     grp = V.evaluation.leave_group_out(trials, params, config, groups=[[c] for c in chans])
@@ -165,7 +106,7 @@ def test_engine_scores_pairs_in_channel_list_order(V):
     from vlgp_amd.api import bind_priors
     from vlgp_amd.engine import Engine
 
-    trials, params, config = _problem(seed=31, M=4, T=100, N=10, n_gauss=2)
+    trials, params, config = problem(seed=31, M=4, T=100, N=10, n_gauss=2)
     L, N = params["zdim"], params["ydim"]
     gauss = np.asarray(params["likelihood"]) == "gaussian"
     groups = [[8, 1], [4], [9, 0, 3]]  # (unsorted on purpose: the slots follow the list, not the channel numbers)
@@ -187,7 +128,7 @@ def test_engine_scores_pairs_in_channel_list_order(V):
     p = 0
     for k, g in enumerate(groups):
         mu, v = post["mu"][k * rows:(k + 1) * rows], post["v"][k * rows:(k + 1) * rows]
-        r, ll = _rate_ll(y, x, mu, v, params["a"], params["b"], params["noise"], gauss, True)
+        r, ll = rate_ll(y, x, mu, v, params["a"], params["b"], params["noise"], gauss, True)
         for n in g:
             assert relerr(rate[:, p], r[:, n]) < 1e-12
             third = r[:, n].sum()
@@ -196,11 +137,35 @@ def test_engine_scores_pairs_in_channel_list_order(V):
             p += 1
 
 
+def test_replicate_channels_are_singleton_groups(V):
+    from vlgp_amd.api import bind_priors
+    from vlgp_amd.engine import Engine
+
+    trials, params, config = problem(seed=23, M=4, T=100, N=10)
+    L, N = params["zdim"], params["ydim"]
+    units = [{"y": t["y"], "x": None, "mu": np.zeros((t["y"].shape[0], L)), "v": None, "w": None} for t in trials]
+    got = []
+    with Engine(N, L, 1, 50) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(0, units)
+        bind_priors(eng, trials, dict(params))
+        for args, kw in (([1, 3, 5],), {}), ((), {"groups": [[1], [3], [5]]}):
+            eng.replicate(0, 2, *args, **kw)
+            eng.estep(2, 2)
+            mu = eng.download(2, ("mu",))["mu"]
+            sums, rate = eng.loglik(2, want_rate=True)
+            got.append((mu, sums, rate))
+            eng.free_units(2)
+    assert got[0][0].shape == (3 * 400, L) and got[0][1].shape == (3, 4) and got[0][2].shape == (400, 3)
+    for one, grp in zip(*got):
+        assert np.array_equal(one, grp)
+
+
 def test_bad_groups_are_refused_and_the_handle_lives_on(V):
     from vlgp_amd.api import bind_priors
     from vlgp_amd.engine import Engine
 
-    trials, params, config = _problem(seed=23, M=4, T=100, N=10)
+    trials, params, config = problem(seed=23, M=4, T=100, N=10)
     L, N = params["zdim"], params["ydim"]
     units = [{"y": t["y"], "x": None, "mu": np.zeros((t["y"].shape[0], L)), "v": None, "w": None} for t in trials]
     with Engine(N, L, 1, 50) as eng:
@@ -227,7 +192,7 @@ def test_bad_groups_are_refused_and_the_handle_lives_on(V):
 
 
 def test_many_latents_take_the_sequential_path(V):
-    trials, params, config = _problem(seed=19, M=3, T=80, N=8, L=12, max_iter=3)
+    trials, params, config = problem(seed=19, M=3, T=80, N=8, L=12, max_iter=3)
     groups = [[0, 5], [3]]
     got = V.evaluation.leave_group_out(trials, params, config, groups=groups)
     _assert_matches_restatement(got, trials, params, config, groups, path="sequential")

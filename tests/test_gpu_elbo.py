@@ -21,6 +21,7 @@ import pytest
 
 import elbo_numpy as EN
 from conftest import GOLDEN, ROOT
+from heldout_numpy import lagged
 
 pytestmark = pytest.mark.gpu
 
@@ -33,16 +34,6 @@ def V():
     import vlgp_amd
 
     return vlgp_amd
-
-
-def _lagged(y, history):
-    """x (T, 1 + history, N): a column of ones, then each channel's own values 1 ... history bins back."""
-    T, N = y.shape
-    x = np.ones((T, 1 + history, N))
-    for h in range(1, history + 1):
-        x[h:, h, :] = y[:-h]
-        x[:h, h, :] = 0.0
-    return x
 
 
 def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, in_range=False):
@@ -76,7 +67,7 @@ def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, in_range
         if in_range:
             mu = np.stack([EN.compact(chol[T][l]) @ (0.5 * rng.standard_normal(EN.compact(chol[T][l]).shape[1]))
                            for l in range(L)], axis=1)
-        units.append({"y": t["y"], "x": _lagged(t["y"], history) if history else None, "mu": mu,
+        units.append({"y": t["y"], "x": lagged(t["y"], history) if history else None, "mu": mu,
                       "v": 0.05 * rng.random((T, L)) if vb else np.zeros((T, L)), "w": rng.uniform(0.05, 2.0, (T, L))})
     params = {"ydim": N, "zdim": L, "xdim": P, "a": a, "b": b, "noise": noise, "omega": omega, "sigma": sigma,
               "rank": 50, "likelihood": np.where(gauss, "gaussian", "poisson"), "cholesky": chol}

@@ -1,18 +1,14 @@
-"""Held-out evaluation on the device (vlgp_loglik, vlgp_replicate_units, vlgp_amd.evaluation) against a NumPy
+"""Held-out evaluation on the device (vlgp_loglik, singleton replicas, vlgp_amd.evaluation) against a NumPy
 restatement: the oracle's E-step with a[:, n] = 0 from a zero start, then channel n's plug-in rate with its own
 loading, scored with the definitions of vlgp_amd/evaluation.py."""
-import math
-
 import numpy as np
 import pytest
-from scipy.special import gammaln
 
 from conftest import relerr
+from heldout_numpy import STAGE, problem, rate_ll, restated
 from oracle import vlgp_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-STAGE = 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -22,83 +18,10 @@ def V():
     return vlgp_amd
 
 
-def _lagged(y, history):
-    """x (T, 1 + history, N): a column of ones, then each channel's own counts 1 ... history bins back."""
-    T, N = y.shape
-    x = np.ones((T, 1 + history, N))
-    for h in range(1, history + 1):
-        x[h:, h, :] = y[:-h]
-        x[:h, h, :] = 0.0
-    return x
-
-
-def _problem(seed=3, M=6, T=150, N=14, L=3, n_gauss=0, lengths=None, history=0, method="VB", max_iter=4):
-    from vlgp_amd import synth
-
-    trials = synth.make_trials(M, T, N, min(L, 3), seed=seed, n_gauss=n_gauss, lengths=lengths)
-    rng = np.random.default_rng(seed)
-    for tr in trials:
-        tr["x"] = _lagged(tr["y"], history)
-    P = 1 + history
-    y = np.concatenate([tr["y"] for tr in trials])
-    b = np.zeros((P, N))
-    b[0] = np.log(np.maximum(y.mean(0), 1e-3))
-    b[0, N - n_gauss:] = y[:, N - n_gauss:].mean(0) if n_gauss else b[0, N - n_gauss:]
-    if history:
-        b[1:] = -0.05 * rng.random((history, N))
-    a = 0.3 * rng.standard_normal((L, N))
-    if L > 10:  # (as test_gpu_parity's problems: eta = mu a in the range of the few-latent cases -- the E-step's Newton
-        a *= 5.0 / L  # sweeps amplify rounding once rates grow, and the stage tolerance is about arithmetic, not conditioning)
-    lik = np.array(["poisson"] * (N - n_gauss) + ["gaussian"] * n_gauss)
-    noise = np.ones(N)
-    noise[N - n_gauss:] = 0.5 + rng.random(n_gauss)
-    omega = np.linspace(2e-2, 1e-3, L)
-    params = {"ydim": N, "zdim": L, "xdim": P, "a": a, "b": b, "noise": noise, "omega": omega,
-              "sigma": np.ones(L), "rank": 50, "likelihood": lik}
-    from vlgp_amd import get_config
-
-    config = get_config(max_iter=max_iter, method=method)
-    return trials, params, config
-
-
-def _rate_ll(y, x, mu, v, a, b, noise, gauss, vb):
-    """Plug-in rate (Gaussian: eta) and log-likelihood, (T, N) each."""
-    eta = O.linear_predictor(x, mu, a, b)
-    lam = np.exp(np.minimum(eta + (0.5 * (v @ a ** 2) if vb else 0.0), 10.0))
-    rate = np.where(gauss, eta, lam)
-    llp = y * np.log(lam) - lam - gammaln(y + 1.0)
-    llg = -0.5 * np.log(2 * np.pi * noise) - (y - eta) ** 2 / (2 * noise)
-    return rate, np.where(gauss, llg, llp)
-
-
-def _restated_loo(trials, params, config, channels, n_iter=None):
-    a, b, noise = params["a"], params["b"], params["noise"]
-    L = params["zdim"]
-    gauss = np.asarray(params["likelihood"]) == "gaussian"
-    vb = config["method"] == "VB"
-    n_iter = config["max_iter"] if n_iter is None else n_iter
-    rates, lls = [], np.zeros(len(channels))
-    for tr in trials:
-        T = tr["y"].shape[0]
-        G = O.build_prior([T], params["omega"], params["sigma"], 50)[T]
-        cols = []
-        for i, n in enumerate(channels):
-            a0 = a.copy()
-            a0[:, n] = 0.0
-            z = np.zeros((T, L))
-            mu, v, _, _, _ = O.estep_unit(tr["y"], tr["x"], z, z, z, a0, b, noise, gauss, G, n_iter,
-                                          config["dmu_bound"], vb)
-            r, ll = _rate_ll(tr["y"], tr["x"], mu, v, a, b, noise, gauss, vb)
-            cols.append(r[:, n])
-            lls[i] += ll[:, n].sum()
-        rates.append(np.stack(cols, axis=1))
-    return rates, lls
-
-
 @pytest.mark.parametrize("case", ["poisson", "mixed", "history"])
 def test_loglik_matches_restatement(V, case):
     kw = {"poisson": {}, "mixed": {"n_gauss": 3}, "history": {"history": 2}}[case]
-    trials, params, config = _problem(seed=5, **kw)
+    trials, params, config = problem(seed=5, **kw)
     rng = np.random.default_rng(1)
     L, N = params["zdim"], params["ydim"]
     for tr in trials:
@@ -110,7 +33,7 @@ def test_loglik_matches_restatement(V, case):
     want = np.zeros(N)
     rates = []
     for tr in trials:
-        r, ll = _rate_ll(tr["y"], tr["x"], tr["mu"], tr["v"], params["a"], params["b"], params["noise"], gauss, True)
+        r, ll = rate_ll(tr["y"], tr["x"], tr["mu"], tr["v"], params["a"], params["b"], params["noise"], gauss, True)
         want += ll.sum(0)
         rates.append(r)
     assert relerr(per, want) < 1e-12
@@ -140,11 +63,11 @@ def test_leave_one_out_matches_restatement(V, case):
         kw = {"method": "MAP"}
     elif case == "subset":
         channels = [9, 2, 13]
-    trials, params, config = _problem(seed=11, **kw)
+    trials, params, config = problem(seed=11, **kw)
     got = V.evaluation.leave_one_out(trials, params, config, channels=channels)
     chans = list(range(params["ydim"])) if channels is None else channels
     assert got["channels"] == chans and got["path"] == "batched" and got["n_failed"] == 0
-    want_rate, want_ll = _restated_loo(trials, params, config, chans)
+    want_rate, want_ll = restated(trials, params, config, [[c] for c in chans])
     for g, w in zip(got["rate"], want_rate):
         assert g.shape == w.shape
         assert relerr(g, w) < STAGE
@@ -158,10 +81,10 @@ def test_leave_one_out_matches_restatement(V, case):
 def test_batched_equals_sequential_bit_for_bit(V, monkeypatch, shape):
     if shape == "long":
         monkeypatch.setenv("VLGP_ESTEP_LSPLIT", "1")
-        trials, params, config = _problem(seed=13, n_gauss=2)
+        trials, params, config = problem(seed=13, n_gauss=2)
     else:
         monkeypatch.setenv("VLGP_ESTEP_SPLIT", "1")
-        trials, params, config = _problem(seed=13, T=50, n_gauss=2)
+        trials, params, config = problem(seed=13, T=50, n_gauss=2)
     ev = V.evaluation
     base = ev.leave_one_out(trials, params, config, path="batched")
     seq = ev.leave_one_out(trials, params, config, path="sequential")
@@ -179,7 +102,7 @@ def test_batched_equals_sequential_bit_for_bit(V, monkeypatch, shape):
 
 
 def test_zero_loading_channel_reproduces_transform_from_zero(V):
-    trials, params, config = _problem(seed=17)
+    trials, params, config = problem(seed=17)
     n = 4
     params["a"][:, n] = 0.0
     got = V.evaluation.leave_one_out(trials, params, config, channels=[n, 7])
@@ -190,15 +113,15 @@ def test_zero_loading_channel_reproduces_transform_from_zero(V):
         z = np.zeros((T, params["zdim"]))
         mu, v, _, _, _ = O.estep_unit(tr["y"], tr["x"], z, z, z, params["a"], params["b"], params["noise"], gauss, G,
                                       config["max_iter"], config["dmu_bound"], True)
-        r, _ = _rate_ll(tr["y"], tr["x"], mu, v, params["a"], params["b"], params["noise"], gauss, True)
+        r, _ = rate_ll(tr["y"], tr["x"], mu, v, params["a"], params["b"], params["noise"], gauss, True)
         assert relerr(g[:, 0], r[:, n]) < STAGE
 
 
 def test_many_latents_take_the_sequential_path(V):
-    trials, params, config = _problem(seed=19, M=3, T=80, N=8, L=12, max_iter=3)
+    trials, params, config = problem(seed=19, M=3, T=80, N=8, L=12, max_iter=3)
     got = V.evaluation.leave_one_out(trials, params, config, channels=[0, 5])
     assert got["path"] == "sequential"
-    want_rate, want_ll = _restated_loo(trials, params, config, [0, 5])
+    want_rate, want_ll = restated(trials, params, config, [[0], [5]])
     for g, w in zip(got["rate"], want_rate):
         assert relerr(g, w) < STAGE
     assert relerr(got["ll"], want_ll) < STAGE
@@ -210,7 +133,7 @@ def test_replicated_set_refuses_other_entry_points(V):
     from vlgp_amd.api import bind_priors
     from vlgp_amd.engine import Engine
 
-    trials, params, config = _problem(seed=23, M=4, T=100, N=10)
+    trials, params, config = problem(seed=23, M=4, T=100, N=10)
     L, N = params["zdim"], params["ydim"]
     units = [{"y": t["y"], "x": None, "mu": np.zeros((t["y"].shape[0], L)), "v": None, "w": None} for t in trials]
     with Engine(N, L, 1, 50) as eng:

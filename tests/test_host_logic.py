@@ -99,6 +99,23 @@ def test_no_gpu_fails_loudly():
         vlgp_amd.fit(trials, 2, verbose=False)
 
 
+def test_vlgp_error_carries_status_and_detail():
+    import vlgp_amd
+    from vlgp_amd import _lib
+
+    with pytest.raises(vlgp_amd.VlgpError) as info:
+        with vlgp_amd.Engine(4, 2, 1, 50) as eng:  # without a GPU this raises ("no HIP device"), with one the next line
+            eng.norms(3)                           # (an empty set)
+    err = info.value
+    assert isinstance(err.status, int) and err.status < 0 and err.detail
+    assert str(err) == "libvlgp_hip status %d: %s" % (err.status, err.detail)
+    if _lib.device_count() == 0:
+        assert err.status == -2 and "no HIP device" in err.detail  # VLGP_ERR_HIP
+    assert _lib.ERR_STATE == int(re.search(r"#define VLGP_ERR_STATE \((-\d+)\)", open(HEADER).read()).group(1))
+    plain = vlgp_amd.VlgpError("raised by the Python layer")
+    assert plain.status is None and plain.detail is None and str(plain) == "raised by the Python layer"
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "vlgp_amd")
     for base, _, files in os.walk(pkg):

@@ -24,12 +24,16 @@ PROF_ESTEP_PASS, PROF_ESTEP_FACTOR, PROF_ESTEP_MEAN = 9, 10, 11  # split E-step,
 PROF_HSTEP_LR, PROF_HSTEP_TAB = 12, 13  # low-rank H-step round and its tables kernel
 ESTEP_PATHS = ("none", "split", "fast", "long", "generic", "long_split", "split_mixed")  # VLGP_PATH_ESTEP_*
 HSTEP_PATHS = ("none", "lowrank", "dense", "big", "generic", "old", "mixed")  # VLGP_PATH_HSTEP_*
+ERR_STATE = -3  # VLGP_ERR_STATE: call sequence error (missing prior, a replicated set where a plain one is needed ...)
 
 _lib = None
 
 
 class VlgpError(RuntimeError):
-    """An entry point of libvlgp_hip.so returned a non-zero status."""
+    """An entry point of libvlgp_hip.so returned a non-zero status.  Raised by ``check``, it carries that integer as
+    ``status`` and the library's message as ``detail``; raised by the Python layer itself, both are None."""
+
+    status = detail = None
 
 
 _dp = C.POINTER(C.c_double)
@@ -156,8 +160,10 @@ def u8ptr(arr):
 
 def check(rc, handle=None):
     if rc != 0:
-        msg = load().vlgp_last_error(handle)
-        raise VlgpError("libvlgp_hip status %d: %s" % (rc, (msg or b"").decode(errors="replace")))
+        detail = (load().vlgp_last_error(handle) or b"").decode(errors="replace")
+        err = VlgpError("libvlgp_hip status %d: %s" % (rc, detail))
+        err.status, err.detail = int(rc), detail
+        raise err
 
 
 def device_count():

@@ -105,8 +105,7 @@ class FitSession:
 
         if echo:
             echo("Initializing")
-        eng = E.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"],
-                       np.asarray(params["likelihood"]) == "gaussian", device=device)
+        eng = E.Engine.for_params(params, device)
         self.eng = eng
         try:
             multi = comm is not None and comm.world > 1
@@ -265,8 +264,7 @@ def transform(trials, params, config, device=0):
     factor for), missing prior factors are built on the fly."""
     initialize(trials, params, config)
     fill_trials(trials)
-    with E.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"],
-                  np.asarray(params["likelihood"]) == "gaussian", device=device) as eng:
+    with E.Engine.for_params(params, device) as eng:
         eng.set_params(params["a"], params["b"], params["noise"])
         eng.upload(SET_TRIALS, trials)
         dev = E.DeviceTrials(trials, eng, SET_TRIALS)

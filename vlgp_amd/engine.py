@@ -71,6 +71,12 @@ class Engine:
         self.rank, self.world = 0, 1
         self.host_exchange = False
 
+    @classmethod
+    def for_params(cls, params, device=0):
+        """The handle a params dict describes: its ydim, zdim, xdim, rank and the Gaussian channels of ``likelihood``."""
+        return cls(params["ydim"], params["zdim"], params["xdim"], params["rank"],
+                   np.asarray(params["likelihood"]) == "gaussian", device=device)
+
     # -- lifetime ---------------------------------------------------------
     def close(self):
         if getattr(self, "h", None):
@@ -191,24 +197,21 @@ class Engine:
         self.replicas.pop(set_id, None)
 
     def replicate(self, src, dst, channels=None, groups=None):
-        """Set ``dst`` := replicas of set ``src``, replica-major units, y / x aliased to ``src``.  ``channels``: one
-        replica per entry, replica k leaving channel ``channels[k]`` out of its E-step (vlgp_replicate_units).
-        ``groups``: one replica per list of channels, replica k leaving ``groups[k]`` out (vlgp_replicate_groups);
-        ``loglik`` then scores one slot per (replica, channel) pair, the groups concatenated in order."""
+        """Set ``dst`` := replicas of set ``src``, replica-major units, y / x aliased to ``src``
+        (vlgp_replicate_groups).  ``groups``: one replica per list of channels, replica k leaving ``groups[k]`` out of
+        its E-step; ``loglik`` then scores one slot per (replica, channel) pair, the groups concatenated in order.
+        ``channels``: one replica per entry -- the singleton groups ``[[c] for c in channels]``."""
         if (channels is None) == (groups is None):
             raise ValueError("replicate takes channels or groups")
         self.state_epoch += 1
         if groups is None:
-            ch = np.ascontiguousarray(channels, dtype=np.int32)
-            k = len(ch)
-            self._ck(self.lib.vlgp_replicate_units(self.h, int(src), int(dst), k, iptr(ch)))
-        else:
-            groups = [np.asarray(g, dtype=np.int32).reshape(-1) for g in groups]
-            k = len(groups)
-            start = np.zeros(k + 1, dtype=np.int32)
-            np.cumsum([len(g) for g in groups], out=start[1:])
-            ch = np.ascontiguousarray(np.concatenate(groups) if k else np.zeros(0), dtype=np.int32)
-            self._ck(self.lib.vlgp_replicate_groups(self.h, int(src), int(dst), k, iptr(start), iptr(ch)))
+            groups = np.asarray(channels, dtype=np.int32).reshape(-1, 1)
+        groups = [np.asarray(g, dtype=np.int32).reshape(-1) for g in groups]
+        k = len(groups)
+        start = np.zeros(k + 1, dtype=np.int32)
+        np.cumsum([len(g) for g in groups], out=start[1:])
+        ch = np.ascontiguousarray(np.concatenate(groups) if k else np.zeros(0), dtype=np.int32)
+        self._ck(self.lib.vlgp_replicate_groups(self.h, int(src), int(dst), k, iptr(start), iptr(ch)))
         m, rows, off = self.sets[src]
         roff = np.concatenate([r * rows + off[:-1] for r in range(k)] + [np.array([k * rows], dtype=np.int64)])
         self.sets[dst] = (k * m, k * rows, roff)
@@ -531,10 +534,6 @@ class DeviceTrials(list):
                     tr[k][...] = got[k][sl]
 
 
-def _gauss_mask(params):
-    return np.asarray(params["likelihood"]) == "gaussian"
-
-
 def _push_params(eng, params):
     eng.set_params(params["a"], params["b"], params["noise"])
 
@@ -567,7 +566,7 @@ class _Bound:
         if isinstance(tr, DeviceTrials):
             return tr.engine, tr.set_id
         tr = list(tr)
-        eng = Engine(p["ydim"], p["zdim"], p["xdim"], p["rank"], _gauss_mask(p))
+        eng = Engine.for_params(p)
         self.temp = eng
         try:
             _push_params(eng, p)
@@ -630,7 +629,7 @@ def make_cholesky(trials, params, config=None):
         trials.engine.build_prior(lengths, params["omega"], params["sigma"])
         params["cholesky"] = _LazyPrior(trials.engine, lengths)
         return
-    with Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"], _gauss_mask(params)) as eng:
+    with Engine.for_params(params) as eng:
         eng.build_prior(lengths, params["omega"], params["sigma"])
         params["cholesky"] = {T: eng.get_prior(T) for T in lengths}
 

@@ -37,12 +37,13 @@ its all-zero columns dropped (``T x r``), ``w = w[:, l]``, ``mu = mu[:, l]``:
 
 Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``): the results are the same bits on every run.
 """
+import contextlib
 import math
 
 import numpy as np
 
 from . import engine as E
-from ._lib import VlgpError
+from ._lib import ERR_STATE, VlgpError
 from .api import bind_priors
 
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
@@ -85,9 +86,16 @@ def bits_per_spike(sums, rows, gauss=None):
     return ll, ll_null, ny, bps
 
 
-def _engine(params, device):
-    gauss = np.asarray(params["likelihood"]) == "gaussian"
-    return E.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"], gauss, device=device), gauss
+@contextlib.contextmanager
+def _resident(trials, params, units, device, priors=True):
+    """An engine that holds ``params`` and ``units`` (the trials' y, x and a posterior) as set ``SET_TEST`` and, with
+    ``priors``, a prior factor for every trial length (``bind_priors``); closed on exit."""
+    with E.Engine.for_params(params, device) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(SET_TEST, units)
+        if priors:
+            bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
+        yield eng
 
 
 def loglik(fit, per_channel=False, device=0):
@@ -103,10 +111,7 @@ def loglik(fit, per_channel=False, device=0):
     L = params["zdim"]
     units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "v": tr.get("v", np.zeros((tr["y"].shape[0], L))),
               "w": None} for tr in trials]
-    eng, _ = _engine(params, device)
-    with eng:
-        eng.set_params(params["a"], params["b"], params["noise"])
-        eng.upload(SET_TEST, units)
+    with _resident(trials, params, units, device, priors=False) as eng:
         sums, _ = eng.loglik(SET_TEST, vb=vb)
     per = sums[:, 0].copy()
     return per if per_channel else float(np.sum(per))
@@ -176,11 +181,7 @@ def elbo(fit, per_trial=False, device=0):
     units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
               "v": tr["v"] if tr.get("v") is not None else zeros(tr),
               "w": tr["w"] if tr.get("w") is not None else zeros(tr)} for tr in trials]
-    eng, _ = _engine(params, device)
-    with eng:
-        eng.set_params(params["a"], params["b"], params["noise"])
-        eng.upload(SET_TEST, units)
-        bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
+    with _resident(trials, params, units, device) as eng:
         sums, terms, bad, row_ell = eng.elbo(SET_TEST, vb=vb, want_rows=per_trial)
         ranks = eng.unit_ranks(SET_TEST)
         offsets = eng.sets[SET_TEST][2]
@@ -190,30 +191,16 @@ def elbo(fit, per_trial=False, device=0):
 
 
 def _is_refusal(err):
-    text = str(err)
-    return "status -3" in text and "replicated set" in text
+    return err.status == ERR_STATE and "replicated set" in err.detail
 
 
-def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto", max_replicas=None, device=0):
-    """Leave-one-neuron-out prediction of held-out trials (module docstring for the definitions).
-
-    ``trials``: dicts with ``y`` (T, N) and, with regressors, ``x`` (T, xdim, N); their ``mu``, ``v``, ``w`` are not
-    read or written.  ``channels``: the channels to leave out in turn (default all).  ``n_iter``: E-step iterations
-    (default ``config["max_iter"]``, as ``core.infer``).  ``path``: ``"batched"`` runs every left-out channel as a replica
-    of the test set in one E-step (``vlgp_replicate_units``), ``max_replicas`` at a time (default: what
-    ``REPLICA_BUDGET_BYTES`` holds); ``"sequential"`` runs one E-step per channel with its loading zeroed; ``"auto"``
-    takes the batched path unless the device refuses it (the split E-step cannot run the configuration, e.g. L > 10).
-    Both paths give the same bits when they run the same E-step kernels.
-
-    Returns a dict: ``channels``; ``rate``, a list per trial of (T, len(channels)) plug-in rates (Gaussian: means);
-    per channel ``ll``, ``ll_null``, ``n_spikes``, ``bits_per_spike``; ``n_failed`` (singular posterior updates);
-    ``path`` (``"batched"`` or ``"sequential"``)."""
-    if path not in ("auto", "batched", "sequential"):
-        raise ValueError("path must be 'auto', 'batched' or 'sequential'")
-    N, L = int(params["ydim"]), int(params["zdim"])
-    channels = list(range(N)) if channels is None else [int(c) for c in channels]
-    if not channels or len(set(channels)) != len(channels) or min(channels) < 0 or max(channels) >= N:
-        raise ValueError("channels must be distinct indices in [0, %d)" % N)
+def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device):
+    """What ``leave_one_out`` and ``leave_group_out`` share, for validated ``groups``: for every group one inference
+    without it from a zero start, then its channels scored with their original loadings.  Returns ``channels`` (the
+    groups concatenated), ``rate`` per trial, ``ll``, ``ll_null``, ``n_spikes``, ``bits_per_spike``, ``n_failed``,
+    ``path``."""
+    L = int(params["zdim"])
+    channels = [c for g in groups for c in g]
     n_iter = int(config["max_iter"] if n_iter is None else n_iter)
     vb = config["method"] == "VB"
     dmu_bound = config["dmu_bound"]
@@ -224,28 +211,24 @@ def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto
     rows = int(sum(lengths))
     units = [{"y": tr["y"], "x": tr.get("x"), "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))}
              for tr, T in zip(trials, lengths)]
-    K = len(channels)
-    rate = np.empty((rows, K))
-    sums = np.empty((K, 4))
+    rate = np.empty((rows, len(channels)))
+    sums = np.empty((len(channels), 4))
     n_failed = 0
     used = "batched" if path != "sequential" else "sequential"
-    eng, gauss = _engine(params, device)
-    with eng:
-        eng.set_params(a, b, noise)
-        eng.upload(SET_TEST, units)
-        bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
+    with _resident(trials, params, units, device) as eng:
         if used == "batched":
             cap = default_max_replicas(rows, L) if max_replicas is None else int(max_replicas)
             done = 0
             try:
-                for chunk in plan_chunks(channels, cap):
-                    eng.replicate(SET_TEST, SET_REPLICAS, chunk)
+                for chunk in plan_chunks(groups, cap):
+                    n = sum(len(g) for g in chunk)
+                    eng.replicate(SET_TEST, SET_REPLICAS, groups=chunk)
                     n_failed += eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
                     s, r = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
                     eng.free_units(SET_REPLICAS)
-                    sums[done:done + len(chunk)] = s
-                    rate[:, done:done + len(chunk)] = r
-                    done += len(chunk)
+                    sums[done:done + n] = s
+                    rate[:, done:done + n] = r
+                    done += n
             except VlgpError as err:
                 if path == "batched" or not _is_refusal(err):
                     raise
@@ -253,17 +236,19 @@ def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto
                     eng.free_units(SET_REPLICAS)
                 used, n_failed = "sequential", 0
         if used == "sequential":
-            for i, n in enumerate(channels):
+            done = 0
+            for g in groups:
                 a_out = a.copy()
-                a_out[:, n] = 0.0
+                a_out[:, g] = 0.0
                 eng.set_params(a_out, b, noise)
                 eng.upload(SET_TEST, units)  # (mu = v = w = 0 again)
                 n_failed += eng.estep(SET_TEST, n_iter, dmu_bound, vb)
                 eng.set_params(a, b, noise)
                 s, r = eng.loglik(SET_TEST, vb=vb, want_rate=True)
-                sums[i] = s[n]
-                rate[:, i] = r[:, n]
-    ll, ll_null, ny, bps = bits_per_spike(sums, rows, gauss[channels])
+                sums[done:done + len(g)] = s[g]
+                rate[:, done:done + len(g)] = r[:, g]
+                done += len(g)
+    ll, ll_null, ny, bps = bits_per_spike(sums, rows, eng.gauss[channels])
     bounds = np.cumsum([0] + lengths)
     return {
         "channels": channels,
@@ -271,6 +256,29 @@ def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto
         "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
         "n_failed": int(n_failed), "path": used,
     }
+
+
+def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto", max_replicas=None, device=0):
+    """Leave-one-neuron-out prediction of held-out trials (module docstring for the definitions).
+
+    ``trials``: dicts with ``y`` (T, N) and, with regressors, ``x`` (T, xdim, N); their ``mu``, ``v``, ``w`` are not
+    read or written.  ``channels``: the channels to leave out in turn (default all).  ``n_iter``: E-step iterations
+    (default ``config["max_iter"]``, as ``core.infer``).  ``path``: ``"batched"`` runs every left-out channel as a replica
+    of the test set in one E-step (``Engine.replicate``), ``max_replicas`` at a time (default: what
+    ``REPLICA_BUDGET_BYTES`` holds); ``"sequential"`` runs one E-step per channel with its loading zeroed; ``"auto"``
+    takes the batched path unless the device refuses it (the split E-step cannot run the configuration, e.g. L > 10).
+    Both paths give the same bits when they run the same E-step kernels.
+
+    Returns a dict: ``channels``; ``rate``, a list per trial of (T, len(channels)) plug-in rates (Gaussian: means);
+    per channel ``ll``, ``ll_null``, ``n_spikes``, ``bits_per_spike``; ``n_failed`` (singular posterior updates);
+    ``path`` (``"batched"`` or ``"sequential"``)."""
+    if path not in ("auto", "batched", "sequential"):
+        raise ValueError("path must be 'auto', 'batched' or 'sequential'")
+    N = int(params["ydim"])
+    channels = list(range(N)) if channels is None else [int(c) for c in channels]
+    if not channels or len(set(channels)) != len(channels) or min(channels) < 0 or max(channels) >= N:
+        raise ValueError("channels must be distinct indices in [0, %d)" % N)
+    return _leave_out(trials, params, config, [[c] for c in channels], n_iter, path, max_replicas, device)
 
 
 def channel_folds(n_channels, n_folds, seed=0):
@@ -324,68 +332,9 @@ def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_it
     ``bits_per_spike``; ``co_bps``; ``n_failed``; ``path``."""
     if path not in ("auto", "batched", "sequential"):
         raise ValueError("path must be 'auto', 'batched' or 'sequential'")
-    N, L = int(params["ydim"]), int(params["zdim"])
+    N = int(params["ydim"])
     groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
-    channels = [c for g in groups for c in g]
-    group_of = [k for k, g in enumerate(groups) for _ in g]
-    n_iter = int(config["max_iter"] if n_iter is None else n_iter)
-    vb = config["method"] == "VB"
-    dmu_bound = config["dmu_bound"]
-    a = np.array(params["a"], dtype=float)
-    b = np.array(params["b"], dtype=float)
-    noise = np.array(params["noise"], dtype=float)
-    lengths = [int(tr["y"].shape[0]) for tr in trials]
-    rows = int(sum(lengths))
-    units = [{"y": tr["y"], "x": tr.get("x"), "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))}
-             for tr, T in zip(trials, lengths)]
-    K = len(channels)
-    rate = np.empty((rows, K))
-    sums = np.empty((K, 4))
-    n_failed = 0
-    used = "batched" if path != "sequential" else "sequential"
-    eng, gauss = _engine(params, device)
-    with eng:
-        eng.set_params(a, b, noise)
-        eng.upload(SET_TEST, units)
-        bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
-        if used == "batched":
-            cap = default_max_replicas(rows, L) if max_replicas is None else int(max_replicas)
-            done = 0
-            try:
-                for chunk in plan_chunks(groups, cap):
-                    n = sum(len(g) for g in chunk)
-                    eng.replicate(SET_TEST, SET_REPLICAS, groups=chunk)
-                    n_failed += eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
-                    s, r = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
-                    eng.free_units(SET_REPLICAS)
-                    sums[done:done + n] = s
-                    rate[:, done:done + n] = r
-                    done += n
-            except VlgpError as err:
-                if path == "batched" or not _is_refusal(err):
-                    raise
-                if SET_REPLICAS in eng.sets:
-                    eng.free_units(SET_REPLICAS)
-                used, n_failed = "sequential", 0
-        if used == "sequential":
-            done = 0
-            for g in groups:
-                a_out = a.copy()
-                a_out[:, g] = 0.0
-                eng.set_params(a_out, b, noise)
-                eng.upload(SET_TEST, units)  # (mu = v = w = 0 again)
-                n_failed += eng.estep(SET_TEST, n_iter, dmu_bound, vb)
-                eng.set_params(a, b, noise)
-                s, r = eng.loglik(SET_TEST, vb=vb, want_rate=True)
-                sums[done:done + len(g)] = s[g]
-                rate[:, done:done + len(g)] = r[:, g]
-                done += len(g)
-    ll, ll_null, ny, bps = bits_per_spike(sums, rows, gauss[channels])
-    bounds = np.cumsum([0] + lengths)
-    return {
-        "groups": groups, "channels": channels, "group_of": group_of,
-        "rate": [rate[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))],
-        "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
-        "co_bps": co_bits_per_spike(ll, ll_null, ny),
-        "n_failed": int(n_failed), "path": used,
-    }
+    out = _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device)
+    out.update(groups=groups, group_of=[k for k, g in enumerate(groups) for _ in g],
+               co_bps=co_bits_per_spike(out["ll"], out["ll_null"], out["n_spikes"]))
+    return out
