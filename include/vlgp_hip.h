@@ -356,6 +356,15 @@ int vlgp_debug_switch(vlgp_ctx* ctx, const char* name, double* value);
  * out[1] the sum of their predicted ranks (even + odd block), out[2] evaluations that took the dense round,
  * out[3] low-rank rounds re-run densely because a rank exceeded the prediction. */
 int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]);
+/* What vlgp_mstep would launch on this handle for a set of `rows` rows (rows >= 1), computed by the functions the launches
+ * themselves use; launches nothing, needs no set.  out[0] G, the workgroups along the rows (partial sums per statistic),
+ * [1] rows per workgroup, [2] CT channels per tile, [3] S row slices per workgroup, [4] threads per workgroup, [5] channel
+ * tiles; [6] LT, [7] PT, the compiled accumulator sizes (0, 0: the loop-based kernels take the set, and of the
+ * geometry they use G and the rows per workgroup only); [8] 1 when the Newton accumulation of a set with x == 1 is the EXACT
+ * instantiation; [9] FIXED (0: the general solve) and [10] ANYG of the single-rank sum + solve launch; [11] 1 when the noise
+ * variance takes two passes over the rows, 0 when it comes from the moments.  G depends on the device's compute units and
+ * on VLGP_MSTEP_WG_PER_CU: the shape tests assert through this that they reach the geometry they name. */
+int vlgp_debug_mstep_plan(vlgp_ctx* ctx, int64_t rows, int out[12]);
 
 
 /* ---- held-out evaluation: groups of channels --------------------------- */

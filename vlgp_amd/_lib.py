@@ -104,6 +104,7 @@ _SIGNATURES = {
     "vlgp_debug_reload_switches": (C.c_int, [_h]),
     "vlgp_debug_switch": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "vlgp_debug_hstep_stats": (C.c_int, [_h, _dp]),
+    "vlgp_debug_mstep_plan": (C.c_int, [_h, C.c_int64, _ip]),
     "vlgp_replicate_groups": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -1748,6 +1748,12 @@ extern "C" int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]) {
     return VLGP_OK;
 }
 
+extern "C" int vlgp_debug_mstep_plan(vlgp_ctx* ctx, int64_t rows, int out[12]) {
+    NEED_CTX(ctx);
+    if (rows < 1 || !out) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad plan arguments");
+    return mstep_plan_report(ctx, rows, out);
+}
+
 extern "C" int vlgp_debug_npx(vlgp_ctx* ctx, int kind, int64_t n, const double* a, const double* b, double* out) {
     NEED_CTX(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->dev));

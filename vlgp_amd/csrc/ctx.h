@@ -291,6 +291,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
 // runs entirely on ctx->mstream with the M-step lane's workspace / communicator
 int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double eps, double lr,
                  double da_bound, double db_bound);
+int mstep_plan_report(vlgp_ctx* ctx, int64_t rows, int out[12]);  // vlgp_debug_mstep_plan: what launch_mstep would launch
 int launch_hstep(vlgp_ctx* ctx, UnitSet& us, int window, double dt, int n_eval, const int* latent,
                  const double* logp, double* ll, double* dll);
 // factor the listed priors (bit-exact ichol_gauss), ranks and compact copies included; returns with pr.rl set

@@ -895,7 +895,8 @@ __global__ void noise_stats_kernel(int N, int L, int P, double count, const doub
     const double mean = s1 / count;
     // a constant residual (silent channel, zero loading) cancels completely: rounding may leave -1e-15, a variance
     // never below zero (the comparison keeps a NaN)
-    const double var = s2 / count - mean * mean;
+    // (a single row in all has no variance: np.var gives 0 exactly, the two terms only cancel to rounding, +-1e-16)
+    const double var = count > 1.0 ? s2 / count - mean * mean : 0.0;
     noise[n] = var < 0.0 ? 0.0 : var;
 }
 __global__ void zero_kernel(int64_t n, double* p) {
@@ -950,10 +951,23 @@ static Geometry plan(vlgp_ctx* ctx, int64_t rows) {
     return g;
 }
 
+// Which instantiation a launch takes: ONE place, shared by the launchers below and by mstep_plan_report (what the tests
+// assert they hit).  Compiled accumulator sizes: the smallest bucket that holds L / P, 0 beyond the compiled family.
+static int accum_lt(int L) { return L <= 2 ? 2 : L <= 3 ? 3 : L <= 5 ? 5 : L <= 8 ? 8 : L <= 10 ? 10 : L <= 16 ? 16 : 0; }
+static int accum_pt(int P) { return P <= 1 ? 1 : P <= 2 ? 2 : P <= 4 ? 4 : P <= 8 ? 8 : 0; }
+// the EXACT instantiation of the NEWTON launch: the bucket is the size, no regressor besides the constant one
+static bool accum_exact(int LT, int PT, int L, int P, bool x_ones) { return L == LT && P == PT && PT == 1 && x_ones; }
+// register-resident solve (mstep_solve_poisson_fixed) for the usual latent counts, no regressors; 0: the general solve
+static int solve_fixed(int L, int P) { return P == 1 && (L == 3 || L == 5 || L == 8 || L == 10) ? L : 0; }
+// ... and whether the general solve is compiled in beside it (ANYG): always without a fixed size
+static bool solve_anyg(const vlgp_ctx* ctx, int fixed) { return fixed == 0 || ctx->n_gauss > 0; }
+// noise = var(y - eta) by two passes over the rows, not from the moments (see noise_stats_kernel)
+static bool noise_by_passes(const vlgp_ctx* ctx) { return ctx->n_gauss > 0 || ctx->P > 2 || ctx->sw.noise_passes; }
+
 template <int LT, int PT>
 static void launch_accum_k(hipStream_t st, int kind, const Geometry& g, const MArgs& A) {
     dim3 grid(g.G, g.tiles), blk(g.nthr);
-    if (kind == K_NEWTON && A.L == LT && A.P == PT && PT == 1 && A.x == nullptr) {  // the hot launch, specialised
+    if (kind == K_NEWTON && accum_exact(LT, PT, A.L, A.P, A.x == nullptr)) {  // the hot launch, specialised
         hipLaunchKernelGGL((mstep_accum<LT, PT, K_NEWTON, true>), grid, blk, g.lds, st, A);
         return;
     }
@@ -966,13 +980,14 @@ static void launch_accum_k(hipStream_t st, int kind, const Geometry& g, const MA
 }
 template <int LT>
 static int launch_accum_p(vlgp_ctx* ctx, int kind, const Geometry& g, const MArgs& A) {
-    const int P = A.P;
     hipStream_t mst = ctx->mstream;
-    if (P <= 1) launch_accum_k<LT, 1>(mst, kind, g, A);
-    else if (P <= 2) launch_accum_k<LT, 2>(mst, kind, g, A);
-    else if (P <= 4) launch_accum_k<LT, 4>(mst, kind, g, A);
-    else if (P <= 8) launch_accum_k<LT, 8>(mst, kind, g, A);
-    else return vlgp_fail(ctx, VLGP_ERR_ARG, "M-step kernel supports xdim <= 8, got %d", P);
+    switch (accum_pt(A.P)) {
+        case 1: launch_accum_k<LT, 1>(mst, kind, g, A); break;
+        case 2: launch_accum_k<LT, 2>(mst, kind, g, A); break;
+        case 4: launch_accum_k<LT, 4>(mst, kind, g, A); break;
+        case 8: launch_accum_k<LT, 8>(mst, kind, g, A); break;
+        default: return vlgp_fail(ctx, VLGP_ERR_ARG, "M-step kernel supports xdim <= 8, got %d", A.P);
+    }
     HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
 }
@@ -994,15 +1009,30 @@ static int launch_accum_gen(vlgp_ctx* ctx, int kind, const Geometry& g, const MA
 }
 
 static int launch_accum(vlgp_ctx* ctx, int kind, const Geometry& g, const MArgs& A, double* cache = nullptr) {
-    const int L = A.L;
     if (mstep_generic(ctx, A.L, A.P)) return launch_accum_gen(ctx, kind, g, A, cache);
-    if (L <= 2) return launch_accum_p<2>(ctx, kind, g, A);
-    if (L <= 3) return launch_accum_p<3>(ctx, kind, g, A);
-    if (L <= 5) return launch_accum_p<5>(ctx, kind, g, A);
-    if (L <= 8) return launch_accum_p<8>(ctx, kind, g, A);
-    if (L <= 10) return launch_accum_p<10>(ctx, kind, g, A);
-    if (L <= 16) return launch_accum_p<16>(ctx, kind, g, A);
-    return vlgp_fail(ctx, VLGP_ERR_ARG, "M-step kernel supports at most 16 latents, got %d", L);
+    switch (accum_lt(A.L)) {
+        case 2: return launch_accum_p<2>(ctx, kind, g, A);
+        case 3: return launch_accum_p<3>(ctx, kind, g, A);
+        case 5: return launch_accum_p<5>(ctx, kind, g, A);
+        case 8: return launch_accum_p<8>(ctx, kind, g, A);
+        case 10: return launch_accum_p<10>(ctx, kind, g, A);
+        case 16: return launch_accum_p<16>(ctx, kind, g, A);
+    }
+    return vlgp_fail(ctx, VLGP_ERR_ARG, "M-step kernel supports at most 16 latents, got %d", A.L);
+}
+
+// vlgp_debug_mstep_plan: what launch_mstep would launch for a set of `rows` rows on this handle, from the functions the
+// launches themselves call.  Launches nothing.
+int mstep_plan_report(vlgp_ctx* ctx, int64_t rows, int out[12]) {
+    const int L = ctx->L, P = ctx->P;
+    const Geometry g = plan(ctx, rows);
+    const bool gen = mstep_generic(ctx, L, P);
+    const int lt = gen ? 0 : accum_lt(L), pt = gen ? 0 : accum_pt(P);
+    const int fixed = solve_fixed(L, P);
+    const int v[12] = {g.G, g.rows_per_wg, g.CT, g.S, g.nthr, g.tiles, lt, pt,
+                       !gen && accum_exact(lt, pt, L, P, true), fixed, solve_anyg(ctx, fixed), noise_by_passes(ctx)};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return VLGP_OK;
 }
 
 template <int LT>
@@ -1074,7 +1104,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
 
     // Single rank, no per-launch timing: record the whole sequence once and replay it (see ctx.h).
     const bool use_graph = ctx->world == 1 && !ctx->prof_on && !ctx->sw.no_mgraph;
-    const bool noise_passes = ctx->n_gauss > 0 || P > 2 || ctx->sw.noise_passes;  // (see noise_stats_kernel)
+    const bool noise_passes = noise_by_passes(ctx);
     std::vector<double> key;
     if (use_graph) {
         auto pk = [&](const void* p_) { key.push_back((double)(uintptr_t)p_); };
@@ -1163,8 +1193,8 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
             if (ctx->world == 1) {  // no all-reduce between the sum and the solves: one launch for both
                 const int64_t n = (int64_t)Kn * N;
                 const dim3 sg((unsigned)((n + MS_OUT - 1) / MS_OUT));
-                const int fixed = P == 1 ? L : 0;  // register-resident solve for the usual latent counts, no regressors
-                const bool anyg = ctx->n_gauss > 0;
+                const int fixed = solve_fixed(L, P);
+                const bool anyg = solve_anyg(ctx, fixed);
 #define MS_SUM_SOLVE(F)                                                                                                  \
     do {                                                                                                                  \
         if (anyg) hipLaunchKernelGGL((mstep_sum_solve_kernel<F, true>), sg, dim3(512), 0, st, d_part, g.G, n, d_stats, d_ticket, S);  \

@@ -488,6 +488,17 @@ class Engine:
         self._ck(self.lib.vlgp_debug_hstep_stats(self.h, dptr(out)))
         return out
 
+    MSTEP_PLAN_KEYS = ("G", "rows_per_wg", "CT", "S", "nthr", "tiles", "LT", "PT", "exact", "fixed", "anyg", "noise_passes")
+
+    def mstep_plan(self, rows):
+        """What ``mstep`` would launch for a set of ``rows`` rows on this handle (vlgp_debug_mstep_plan): a dict of the
+        geometry (G, rows_per_wg, CT, S, nthr, tiles), the compiled sizes LT, PT (0, 0: the loop-based kernels), whether
+        the Newton launch of a set with x == 1 is the EXACT instantiation, FIXED and ANYG of the sum + solve launch, and
+        whether the noise takes two passes.  Launches nothing."""
+        out = np.zeros(12, dtype=np.int32)
+        self._ck(self.lib.vlgp_debug_mstep_plan(self.h, C.c_int64(int(rows)), iptr(out)))
+        return dict(zip(self.MSTEP_PLAN_KEYS, (int(v) for v in out)))
+
     def profile_get(self, kind):
         n, ms, units = C.c_int64(0), C.c_double(0), C.c_double(0)
         self._ck(self.lib.vlgp_profile_get(self.h, int(kind), C.byref(n), C.byref(ms), C.byref(units)))
