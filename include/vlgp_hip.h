@@ -365,6 +365,56 @@ int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]);
  * variance takes two passes over the rows, 0 when it comes from the moments.  G depends on the device's compute units and
  * on VLGP_MSTEP_WG_PER_CU: the shape tests assert through this that they reach the geometry they name. */
 int vlgp_debug_mstep_plan(vlgp_ctx* ctx, int64_t rows, int out[12]);
+/* What vlgp_estep (mode 1 | 2 | 4 | 8, or without the 8: vb off), vlgp_update_w (mode 4) or vlgp_update_v (mode 1 | 8) with
+ * `n_iter` sweeps would launch for the resident set `set` on this handle: launch_estep itself runs its dispatch with every
+ * kernel family deciding as it does before a launch, and reports instead of launching.  Binds the set's priors (they must
+ * exist when the mode needs them); launches no E-step kernel, changes no unit state.  It reports ONE launch_estep call:
+ * n_iter = 0, which vlgp_estep answers without a launch, is planned as if launched, and a set staged with
+ * vlgp_set_overlaps (vlgp_estep runs launch_estep once per stage, each with its own lengths and cuts) is an error.
+ * out, VLGP_ESTEP_PLAN_LEN ints, at the slots VLGP_EP_*:
+ *   FAMILY, VLGP_PATH_ESTEP_*;  DECLINE, why the split E-step declined, VLGP_ESPLIT_* (0: it took the set);
+ *   split families: LT, REC, MAXRA, USE_LANE, MIX, MAXRA_HI (maxra of the mixed or hi launch; 0: none), RTOP of the
+ *   lane-per-task launch (13, 14; 0: none), LO_SHG (1 when the rank <= 16 launch shares G per workgroup), N_LANES,
+ *   CUT ... CUT + n_lanes the cuts (unit indices), CS of the row passes, NJ of the y pass (4, 8; 0: the lane-per-row
+ *   form; -1: no y pass in this mode), RANK + l the rank and CLASS + l the class (VLGP_ECLASS_*) of latent l < 16;
+ *   fast: LT, RP, RA;   generic: LT, SMALL, RG;   long: the family only.
+ * Slots a family does not use hold 0. */
+#define VLGP_EP_FAMILY 0
+#define VLGP_EP_DECLINE 1
+#define VLGP_EP_LT 2
+#define VLGP_EP_REC 3
+#define VLGP_EP_MAXRA 4
+#define VLGP_EP_USE_LANE 5
+#define VLGP_EP_MIX 6
+#define VLGP_EP_MAXRA_HI 7
+#define VLGP_EP_RTOP 8
+#define VLGP_EP_LO_SHG 9
+#define VLGP_EP_N_LANES 10
+#define VLGP_EP_CUT 11             /* n_lanes + 1 slots, at most 5 */
+#define VLGP_EP_CS 16
+#define VLGP_EP_NJ 17
+#define VLGP_EP_RP 18
+#define VLGP_EP_RA 19
+#define VLGP_EP_SMALL 20
+#define VLGP_EP_RG 21
+#define VLGP_EP_RANK 22            /* 16 slots */
+#define VLGP_EP_CLASS 38           /* 16 slots */
+#define VLGP_ESTEP_PLAN_LEN 54
+#define VLGP_ESPLIT_TAKEN 0
+#define VLGP_ESPLIT_OFF 1          /* VLGP_ESTEP_SPLIT=0 */
+#define VLGP_ESPLIT_GENERIC 2      /* VLGP_ESTEP_GENERIC */
+#define VLGP_ESPLIT_L 3            /* L > 10 */
+#define VLGP_ESPLIT_N 4            /* N > 1024 */
+#define VLGP_ESPLIT_LSPLIT_OFF 5   /* long units, VLGP_ESTEP_LSPLIT=0 */
+#define VLGP_ESPLIT_LONG_RANK 6    /* long units, prior rank above the long-unit split limit */
+#define VLGP_ESPLIT_LONG_FEW 7     /* long units, fewer than 128 tasks */
+#define VLGP_ESPLIT_SMALL_SET 8    /* short units: one generation of persistent workgroups */
+#define VLGP_ESPLIT_RANK 9         /* short units at effective prior rank above 32 */
+#define VLGP_ESPLIT_REC 10         /* channel records longer than 34 doubles */
+#define VLGP_ECLASS_LANE 0         /* lane-per-task launch (estep_lane.h) */
+#define VLGP_ECLASS_LO 1           /* wave-per-task, rank <= 16 (in a mixed launch: rides in the hi class) */
+#define VLGP_ECLASS_HI 2           /* wave-per-task, rank > 16 */
+int vlgp_debug_estep_plan(vlgp_ctx* ctx, int set, int mode, int n_iter, int out[VLGP_ESTEP_PLAN_LEN]);
 
 
 /* ---- held-out evaluation: groups of channels --------------------------- */

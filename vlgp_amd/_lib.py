@@ -23,6 +23,13 @@ PROF_ESTEP_RA16, PROF_ESTEP_RA24, PROF_ESTEP_RA32, PROF_ESTEP_LONG, PROF_ESTEP_G
 PROF_ESTEP_PASS, PROF_ESTEP_FACTOR, PROF_ESTEP_MEAN = 9, 10, 11  # split E-step, sampled launches
 PROF_HSTEP_LR, PROF_HSTEP_TAB = 12, 13  # low-rank H-step round and its tables kernel
 ESTEP_PATHS = ("none", "split", "fast", "long", "generic", "long_split", "split_mixed")  # VLGP_PATH_ESTEP_*
+# vlgp_debug_estep_plan: the report's slots (VLGP_EP_*), its length, the decline reasons (VLGP_ESPLIT_*) and the latent
+# classes (VLGP_ECLASS_*), as include/vlgp_hip.h has them (tests/test_gpu_estep_shapes.py compares the two)
+EP = dict(FAMILY=0, DECLINE=1, LT=2, REC=3, MAXRA=4, USE_LANE=5, MIX=6, MAXRA_HI=7, RTOP=8, LO_SHG=9, N_LANES=10, CUT=11, CS=16,
+          NJ=17, RP=18, RA=19, SMALL=20, RG=21, RANK=22, CLASS=38)
+ESTEP_PLAN_LEN = 54
+ESPLIT = ("TAKEN", "OFF", "GENERIC", "L", "N", "LSPLIT_OFF", "LONG_RANK", "LONG_FEW", "SMALL_SET", "RANK", "REC")
+ECLASS = ("LANE", "LO", "HI")
 HSTEP_PATHS = ("none", "lowrank", "dense", "big", "generic", "old", "mixed")  # VLGP_PATH_HSTEP_*
 ERR_STATE = -3  # VLGP_ERR_STATE: call sequence error (missing prior, a replicated set where a plain one is needed ...)
 
@@ -105,6 +112,7 @@ _SIGNATURES = {
     "vlgp_debug_switch": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "vlgp_debug_hstep_stats": (C.c_int, [_h, _dp]),
     "vlgp_debug_mstep_plan": (C.c_int, [_h, C.c_int64, _ip]),
+    "vlgp_debug_estep_plan": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip]),
     "vlgp_replicate_groups": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
 }
 EXPORTS = tuple(_SIGNATURES)

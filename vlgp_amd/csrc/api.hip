@@ -1754,6 +1754,21 @@ extern "C" int vlgp_debug_mstep_plan(vlgp_ctx* ctx, int64_t rows, int out[12]) {
     return mstep_plan_report(ctx, rows, out);
 }
 
+extern "C" int vlgp_debug_estep_plan(vlgp_ctx* ctx, int set, int mode, int n_iter, int out[VLGP_ESTEP_PLAN_LEN]) {
+    NEED_CTX(ctx);
+    if (!out || n_iter < 0 || mode < 1 || mode > (EM_FACTOR0 | EM_MEAN | EM_W | EM_V))
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "bad plan arguments");
+    CHK(vlgp_prior_collect(ctx));
+    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    UnitSet* us = vlgp_get_set(ctx, set, true);
+    if (!us) return VLGP_ERR_ARG;
+    // (vlgp_estep runs a staged set through launch_estep once per stage view: lengths, lanes and cuts differ per stage)
+    if (us->stage_start.size() > 2)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is staged (vlgp_set_overlaps): there is one plan per stage, not one for the set", set);
+    for (int i = 0; i < VLGP_ESTEP_PLAN_LEN; ++i) out[i] = 0;
+    return launch_estep(ctx, *us, mode, n_iter, 1.0, (mode & EM_V) != 0, out);
+}
+
 extern "C" int vlgp_debug_npx(vlgp_ctx* ctx, int kind, int64_t n, const double* a, const double* b, double* out) {
     NEED_CTX(ctx);
     HIPCHK(ctx, hipSetDevice(ctx->dev));

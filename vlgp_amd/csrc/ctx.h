@@ -221,7 +221,6 @@ struct vlgp_ctx {
     hipStream_t elane[VLGP_E_LANES - 1] = {};
     hipEvent_t ev_e_fork = nullptr, ev_e_join[VLGP_E_LANES - 1] = {};
     int last_estep_path = 0;      // VLGP_PATH_ESTEP_* of the most recent E-step / update_w / update_v launch
-    int last_estep_mix = 0;       // that call ran mixed lane-per-task / wave-per-task launches (esplit_mix)
     int lds_max = 64 * 1024;      // hipDeviceAttributeMaxSharedMemoryPerBlock (gfx950: 160 KB)
 
     // Pieces of an EM iteration's tail taken off its critical path (api.hip):
@@ -287,7 +286,19 @@ void vlgp_prof_end(vlgp_ctx* ctx, int kind, double units = 0.0, hipStream_t st =
 #define EM_MEAN 2      // run mean-update sweeps (n_iter of them)
 #define EM_W 4         // recompute w
 #define EM_V 8         // update v from the factor
-int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bound, int vb);
+// report != null (vlgp_debug_estep_plan): the same dispatch, every family deciding as it does before a launch and
+// writing what it would launch into report[EP_*] instead of touching the device; priors are bound, nothing is launched
+int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bound, int vb, int* report = nullptr);
+// slots of that report (include/vlgp_hip.h documents them); EP_CUT: n_lanes + 1 unit indices, EP_RANK / EP_CLASS: per latent
+enum { EP_FAMILY = 0, EP_DECLINE, EP_LT, EP_REC, EP_MAXRA, EP_USE_LANE, EP_MIX, EP_MAXRA_HI, EP_RTOP, EP_LO_SHG, EP_N_LANES,
+       EP_CUT, EP_CS = EP_CUT + VLGP_E_LANES + 1, EP_NJ, EP_RP, EP_RA, EP_SMALL, EP_RG, EP_RANK, EP_CLASS = EP_RANK + 16,
+       EP_LEN = EP_CLASS + 16 };
+#define EP_SAME(name) static_assert(EP_##name == VLGP_EP_##name, "vlgp_debug_estep_plan: slot " #name " is part of the ABI")
+EP_SAME(FAMILY); EP_SAME(DECLINE); EP_SAME(LT); EP_SAME(REC); EP_SAME(MAXRA); EP_SAME(USE_LANE); EP_SAME(MIX); EP_SAME(MAXRA_HI);
+EP_SAME(RTOP); EP_SAME(LO_SHG); EP_SAME(N_LANES); EP_SAME(CUT); EP_SAME(CS); EP_SAME(NJ); EP_SAME(RP); EP_SAME(RA); EP_SAME(SMALL);
+EP_SAME(RG); EP_SAME(RANK); EP_SAME(CLASS);
+#undef EP_SAME
+static_assert(EP_LEN == VLGP_ESTEP_PLAN_LEN, "vlgp_debug_estep_plan: the report's length is part of the ABI");
 // runs entirely on ctx->mstream with the M-step lane's workspace / communicator
 int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double eps, double lr,
                  double da_bound, double db_bound);

@@ -393,19 +393,24 @@ static int launch_t(vlgp_ctx* ctx, const EstepArgs& A, int M, int nthr, size_t l
     return VLGP_OK;
 }
 
+// the compiled latent count of the generic kernels (launch_l; the LDS demands; vlgp_debug_estep_plan)
+static int generic_lt(int L) { return L <= 2 ? 2 : (L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : (L <= 10 ? 10 : (L <= 16 ? 16 : (L <= 32 ? 32 : 64)))))); }
+
 template <bool SMALL>
 static int launch_l(vlgp_ctx* ctx, const EstepArgs& A, int M, int nthr, size_t lds) {
     const int L = A.L;
-    if (L <= 2) return launch_t<SMALL, 2>(ctx, A, M, nthr, lds);
-    if (L <= 3) return launch_t<SMALL, 3>(ctx, A, M, nthr, lds);
-    if (L <= 5) return launch_t<SMALL, 5>(ctx, A, M, nthr, lds);
-    if (L <= 8) return launch_t<SMALL, 8>(ctx, A, M, nthr, lds);
-    if (L <= 10) return launch_t<SMALL, 10>(ctx, A, M, nthr, lds);
-    if (L <= 16) return launch_t<SMALL, 16>(ctx, A, M, nthr, lds);
-    // beyond sixteen latents the per-latent register arrays of the (T x N) passes spill: slow, same arithmetic
-    if (L <= 32) return launch_t<SMALL, 32>(ctx, A, M, nthr, lds);
-    if (L <= 64) return launch_t<SMALL, 64>(ctx, A, M, nthr, lds);
-    return vlgp_fail(ctx, VLGP_ERR_ARG, "E-step kernel supports at most 64 latents, got %d", L);
+    if (L > 64) return vlgp_fail(ctx, VLGP_ERR_ARG, "E-step kernel supports at most 64 latents, got %d", L);
+    switch (generic_lt(L)) {
+        case 2: return launch_t<SMALL, 2>(ctx, A, M, nthr, lds);
+        case 3: return launch_t<SMALL, 3>(ctx, A, M, nthr, lds);
+        case 5: return launch_t<SMALL, 5>(ctx, A, M, nthr, lds);
+        case 8: return launch_t<SMALL, 8>(ctx, A, M, nthr, lds);
+        case 10: return launch_t<SMALL, 10>(ctx, A, M, nthr, lds);
+        case 16: return launch_t<SMALL, 16>(ctx, A, M, nthr, lds);
+        // beyond sixteen latents the per-latent register arrays of the (T x N) passes spill: slow, same arithmetic
+        case 32: return launch_t<SMALL, 32>(ctx, A, M, nthr, lds);
+    }
+    return launch_t<SMALL, 64>(ctx, A, M, nthr, lds);
 }
 
 static int pick_rg(int T, int N, int nthr) {
@@ -423,11 +428,22 @@ static int pick_rg(int T, int N, int nthr) {
     return best;
 }
 
-int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bound, int vb) {
+// SMALL (the whole unit state in LDS) or LONG (in HBM / L2) form of the generic kernel: SMALL while it fits
+struct SmallPlan { bool fits; int nthr; int64_t d; };
+static SmallPlan plan_generic_small(const UnitSet& us, int L, int64_t common, int64_t gsz, int64_t lcsz, int64_t ints,
+                                    int64_t lds_max) {
+    const int nw_s = L < 4 ? 4 : (L > 8 ? 8 : L);
+    const int64_t small_d = common + 2LL * nw_s * 64 + 6LL * us.Tmax * L + gsz + lcsz + ints;
+    return SmallPlan{us.Tmax <= 256 && small_d * 8 <= lds_max, nw_s * 64, small_d};
+}
+
+int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bound, int vb, int* report) {
     const int N = ctx->N, L = ctx->L;
     const bool need_prior = (mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
     if (need_prior) CHK(vlgp_bind_priors(ctx, us));
-    if (us.rep_src >= 0) {  // replicated set: x.b of the source rows, the split E-step or an error (never another family)
+    if (report) {
+        // (no x.b refresh: the families choose by sizes and switches only)
+    } else if (us.rep_src >= 0) {  // replicated set: x.b of the source rows, the split E-step or an error (never another family)
         UnitSet& src = ctx->sets[us.rep_src];
         if (!src.x_ones) CHK(vlgp_refresh_xb(ctx, src));
         us.d_xb = src.d_xb;
@@ -440,7 +456,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     const int64_t gsz = rs.g_odd, lcsz = rs.lc_odd;
 
     const int64_t LDS_MAX = 160 * 1024;
-    const int LTl = L <= 2 ? 2 : (L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : (L <= 10 ? 10 : (L <= 16 ? 16 : (L <= 32 ? 32 : 64))))));  // as launch_l dispatches
+    const int LTl = generic_lt(L);
     const int64_t common = 2LL * LTl * N + 2LL * N + ((L + 1) & ~1);
     const int64_t ints = ((int64_t)N + 4 * L + 1) / 2 + 1;
 
@@ -458,11 +474,14 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     A.cols_g = nullptr; A.wconst_g = nullptr;
     A.lds_T = us.Tmax; A.lds_gsz = (int)gsz; A.lds_lcsz = (int)lcsz;
 
+    // the family that takes the set: recorded on the handle, or in the report
+    int* path = report ? &report[EP_FAMILY] : &ctx->last_estep_path;
+
     // SPLIT: many short units -> chip-wide launches per phase (estep_split.hip); declines for small sets
     {
         int handled = 0;
-        CHK(launch_estep_split(ctx, us, A, rs, &handled));
-        if (handled) { ctx->last_estep_path = handled == 2 ? VLGP_PATH_ESTEP_LSPLIT : (handled == 3 ? VLGP_PATH_ESTEP_SPLIT_MIXED : VLGP_PATH_ESTEP_SPLIT); return VLGP_OK; }
+        CHK(launch_estep_split(ctx, us, A, rs, &handled, report));
+        if (handled) { *path = handled == 2 ? VLGP_PATH_ESTEP_LSPLIT : (handled == 3 ? VLGP_PATH_ESTEP_SPLIT_MIXED : VLGP_PATH_ESTEP_SPLIT); return VLGP_OK; }
         if (us.rep_src >= 0)
             return vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: only the split E-step leaves a channel out, and it declined");
     }
@@ -470,24 +489,28 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     // FAST: register-resident factorisations (estep_fast.hip); declines when it does not apply
     {
         int handled = 0;
-        CHK(launch_estep_fast(ctx, us, A, rs, &handled));
-        if (handled) { ctx->last_estep_path = VLGP_PATH_ESTEP_FAST; return VLGP_OK; }
+        CHK(launch_estep_fast(ctx, us, A, rs, &handled, report));
+        if (handled) { *path = VLGP_PATH_ESTEP_FAST; return VLGP_OK; }
     }
 
     // LONG units: all waves on the per-latent phases, MFMA builds (estep_long.hip)
     if (us.Tmax > 64) {
         int handled = 0;
-        CHK(launch_estep_long(ctx, us, A, &handled));
-        if (handled) { ctx->last_estep_path = VLGP_PATH_ESTEP_LONG; return VLGP_OK; }
+        CHK(launch_estep_long(ctx, us, A, &handled, report));
+        if (handled) { *path = VLGP_PATH_ESTEP_LONG; return VLGP_OK; }
     }
 
     // SMALL: whole unit state lives in LDS
-    int nw_s = L < 4 ? 4 : (L > 8 ? 8 : L);
-    const int64_t small_d = common + 2LL * nw_s * 64 + 6LL * us.Tmax * L + gsz + lcsz + ints;
-    if (us.Tmax <= 256 && small_d * 8 <= LDS_MAX) {
-        const int nthr = nw_s * 64;
+    const SmallPlan sp = plan_generic_small(us, L, common, gsz, lcsz, ints, LDS_MAX);
+    if (sp.fits) {
+        const int nthr = sp.nthr;
+        const int64_t small_d = sp.d;
         A.rg = pick_rg(us.Tmax, N, nthr);
-        ctx->last_estep_path = VLGP_PATH_ESTEP_GENERIC;
+        *path = VLGP_PATH_ESTEP_GENERIC;
+        if (report) {
+            report[EP_LT] = LTl; report[EP_SMALL] = 1; report[EP_RG] = A.rg;
+            return VLGP_OK;
+        }
         vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_GENERIC);
         int rc = launch_l<true>(ctx, A, us.M, nthr, (size_t)small_d * 8);
         vlgp_prof_end(ctx, VLGP_PROF_ESTEP_GENERIC, (double)us.M * (A.n_iter > 0 ? A.n_iter : 1));
@@ -497,11 +520,15 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     // too big for LDS residency (many latents at high rank): the long-unit kernel streams G from L2
     {
         int handled = 0;
-        CHK(launch_estep_long(ctx, us, A, &handled));
-        if (handled) { ctx->last_estep_path = VLGP_PATH_ESTEP_LONG; return VLGP_OK; }
+        CHK(launch_estep_long(ctx, us, A, &handled, report));
+        if (handled) { *path = VLGP_PATH_ESTEP_LONG; return VLGP_OK; }
     }
 
     // LONG: unit state in HBM/L2, factors in LDS when they fit
+    if (report) {
+        report[EP_FAMILY] = VLGP_PATH_ESTEP_GENERIC; report[EP_LT] = LTl; report[EP_SMALL] = 0; report[EP_RG] = 64;
+        return VLGP_OK;
+    }
     const int nthr = 1024, nw = nthr / 64;
     int64_t long_d = common + 2LL * nw * 64 + ints;
     const int64_t need = 3 * us.rows * L;
@@ -521,7 +548,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     A.scratch = us.d_scratch;
     if (lc_total) A.lc_global = us.d_scratch + need;
     A.rg = 64;
-    ctx->last_estep_path = VLGP_PATH_ESTEP_GENERIC;
+    *path = VLGP_PATH_ESTEP_GENERIC;
     vlgp_prof_begin(ctx, VLGP_PROF_ESTEP_GENERIC);
     int rc = launch_l<false>(ctx, A, us.M, nthr, (size_t)long_d * 8);
     vlgp_prof_end(ctx, VLGP_PROF_ESTEP_GENERIC, (double)us.M * (A.n_iter > 0 ? A.n_iter : 1));

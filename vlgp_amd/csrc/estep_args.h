@@ -78,14 +78,16 @@ inline RankSummary estep_rank_summary(const vlgp_ctx* ctx, const UnitSet& us) {
     return S;
 }
 
+// Every launcher below takes `report` (see launch_estep, ctx.h): when set it decides as always, writes what it would launch
+// into report[EP_*], sets *handled and returns before its first allocation or launch.
 // estep_fast.hip: sets *handled = 1 and launches when the fast kernel applies
 // (T <= 64, every effective rank <= 32, L <= 8, LDS fits), else leaves 0.  rs: all zero when the mode needs no prior.
-int launch_estep_fast(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, const RankSummary& rs, int* handled);
+int launch_estep_fast(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, const RankSummary& rs, int* handled, int* report = nullptr);
 
 // estep_long.hip: long units (T > 64) with every wave of the workgroup on the per-latent phases;
 // declines (leaves *handled = 0) when rank > 50, L > 10 or the LDS budget does not fit.
-int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled);
+int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled, int* report = nullptr);
 
 // estep_split.hip: many window-sized units as a sequence of chip-wide launches (passes over rows, one wave per
 // (unit, latent) for the factor and mean phases); declines for small sets, T > 64, rank > 32 or L > 10.
-int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummary& rs, int* handled);
+int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummary& rs, int* handled, int* report = nullptr);

@@ -559,29 +559,51 @@ static int launch_fast_l(vlgp_ctx* ctx, const EstepArgs& A, int M, int nthr, siz
     return vlgp_fail(ctx, VLGP_ERR_STATE, "no fast E-step instantiation for %d latents at this rank", A.L);
 }
 
-int launch_estep_fast(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, const RankSummary& rs, int* handled) {
-    *handled = 0;
+// Whether the fast kernel takes the set, and its instantiation <LT, RP, RA> with the LDS it needs: decided before anything
+// touches the device (launch_estep_fast; vlgp_debug_estep_plan reports it)
+struct FastPlan {
+    bool take = false;
+    int LT = 0, RP = 0, RA = 0, nw = 0;
+    int64_t scr = 0, d = 0;  // doubles of the shared scratch region, of the whole LDS demand
+};
+static FastPlan plan_estep_fast(const vlgp_ctx* ctx, const UnitSet& us, const RankSummary& rs) {
+    FastPlan F;
     const int N = ctx->N, L = ctx->L;
-    if (ctx->sw.estep_generic) return VLGP_OK;
-    if (us.Tmax > 64 || L > 10) return VLGP_OK;
+    if (ctx->sw.estep_generic) return F;
+    if (us.Tmax > 64 || L > 10) return F;
     const int rmax = rs.rmax;
     const int64_t gsz = rs.g_even;
-    if (rmax > 32 || (L > 8 && rmax > 16)) return VLGP_OK;  // nine or ten latents: only the rank <= 16 instantiation
-    const int RP = rmax <= 16 ? 16 : 32;
-    const int LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
-    const int nw = L < 4 ? 4 : L;  // L <= 8
+    if (rmax > 32 || (L > 8 && rmax > 16)) return F;  // nine or ten latents: only the rank <= 16 instantiation
+    F.RP = rmax <= 16 ? 16 : 32;
+    F.LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
+    const int nw = F.nw = L < 4 ? 4 : L;  // L <= 8
     const int Tc = us.Tmax;
-    const int RA = rmax <= 16 ? 16 : (rmax <= 24 ? 24 : 32);
-    const int64_t PK = tri_packed_size(RA);
+    F.RA = rmax <= 16 ? 16 : (rmax <= 24 ? 24 : 32);
+    const int64_t PK = tri_packed_size(F.RA);
     int64_t scr = (int64_t)nw * Tc * L;                       // partial sums of the passes
     if (scr < (int64_t)nw * 256) scr = (int64_t)nw * 256;     // 16 x 16 MFMA staging tiles
     if (scr < (int64_t)nw * 128 + (int64_t)Tc * L) scr = (int64_t)nw * 128 + (int64_t)Tc * L;  // vec + u
-    scr = (scr + 1) & ~1LL;
-    int64_t d = 5LL * Tc * L + 1 + scr + L * PK + gsz + (2 * N + 3 * L + 3) / 2 + 2;
-    if (d * 8 > 160 * 1024) return VLGP_OK;
-    A.lds_gsz = (int)gsz;
-    A.lds_T = Tc;
-    A.lds_scr = (int)scr;
+    F.scr = scr = (scr + 1) & ~1LL;
+    F.d = 5LL * Tc * L + 1 + scr + L * PK + gsz + (2 * N + 3 * L + 3) / 2 + 2;
+    F.take = F.d * 8 <= 160 * 1024;
+    return F;
+}
+
+int launch_estep_fast(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, const RankSummary& rs, int* handled, int* report) {
+    *handled = 0;
+    const int N = ctx->N, L = ctx->L;
+    const FastPlan F = plan_estep_fast(ctx, us, rs);
+    if (!F.take) return VLGP_OK;
+    const int LT = F.LT, RA = F.RA, nw = F.nw;
+    const int64_t d = F.d;
+    if (report) {
+        report[EP_LT] = LT; report[EP_RP] = F.RP; report[EP_RA] = RA;
+        *handled = 1;
+        return VLGP_OK;
+    }
+    A.lds_gsz = (int)rs.g_even;
+    A.lds_T = us.Tmax;
+    A.lds_scr = (int)F.scr;
     if (!ctx->d_ecols) HIPCHK(ctx, hipMalloc(&ctx->d_ecols, sizeof(double) * ((size_t)N * 50 + 32)));
     A.cols_g = ctx->d_ecols;
     A.wconst_g = ctx->d_ecols + (int64_t)N * 34;

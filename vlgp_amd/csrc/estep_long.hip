@@ -545,7 +545,7 @@ int launch_long_t(vlgp_ctx* ctx, const EstepArgs& A, int M, size_t lds) {
 }  // namespace
 
 // Sets *handled = 1 and launches when the long-unit kernel applies (rank <= 50, L <= 10, LDS fits).
-int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled) {
+int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled, int* report) {
     *handled = 0;
     const int N = ctx->N, L = ctx->L;
     if (ctx->R > RPL || L > 10 || ctx->sw.estep_generic) return VLGP_OK;
@@ -554,6 +554,10 @@ int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled) {
     const int64_t ints = ((int64_t)N + 3 * L + 1) / 2 + 1;
     const size_t lds = (size_t)(doubles + ints) * 8;
     if (lds > 160 * 1024) return VLGP_OK;
+    if (report) {  // (vlgp_debug_estep_plan: the family only)
+        *handled = 1;
+        return VLGP_OK;
+    }
     const int64_t need = 3 * us.rows * L;
     const int64_t part = (int64_t)NWL * L * 64;
     if (us.scratch_len < need + part * us.M) {

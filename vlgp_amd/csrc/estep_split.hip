@@ -1677,10 +1677,13 @@ int run_pass_cs(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const double* cols) 
 
 // channel split: four waves per row group while a wave keeps >= 16 channels (measured at 200 k rows x 100
 // channels: 39.4 / 34.4 / 32.2 us for 1 / 2 / 4; at 131 k rows 35.9 / 24.8 / 24.6 us); the y pass is not split
+int pass_cs(int ntot) { return ntot >= 64 ? 4 : (ntot >= 32 ? 2 : 1); }
 template <int LT, int KIND>
 int run_pass_kind(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, const double* cols) {
-    if (A.ntot >= 64) return run_pass_cs<LT, KIND, 4>(ctx, ln, A, cols);
-    if (A.ntot >= 32) return run_pass_cs<LT, KIND, 2>(ctx, ln, A, cols);
+    switch (pass_cs(A.ntot)) {
+        case 4: return run_pass_cs<LT, KIND, 4>(ctx, ln, A, cols);
+        case 2: return run_pass_cs<LT, KIND, 2>(ctx, ln, A, cols);
+    }
     return run_pass_cs<LT, KIND, 1>(ctx, ln, A, cols);
 }
 
@@ -1699,8 +1702,10 @@ int run_pass(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int LT, int kind
 }
 
 // the y pass: coalesced form while a lane's channels fit in registers (N <= 128), else the lane-per-row pass
+int ya_nj(int N) { return N > 128 ? 0 : (N <= 64 ? 4 : 8); }  // channels per lane of the coalesced form; 0: lane-per-row
 int run_ya(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int LT, const double* cols, const double* ycoef) {
-    if (A.N > 128) return run_pass(ctx, ln, A, LT, SP_YA, cols);
+    const int nj = ya_nj(A.N);
+    if (nj == 0) return run_pass(ctx, ln, A, LT, SP_YA, cols);
     const int rows_per_wave = 64;
     const dim3 grid((unsigned)((A.rows + 4 * rows_per_wave - 1) / (4 * rows_per_wave))), blk(256);
     hipStream_t st = ln.st;
@@ -1712,7 +1717,7 @@ int run_ya(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int LT, const doub
         else hipLaunchKernelGGL((esplit_ya<LTV, NJV>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, A.ya,       \
                                 rows_per_wave, X);                                                                       \
     } while (0)
-    const bool small = A.N <= 64;
+    const bool small = nj == 4;
     if (LT == 3) { if (small) ESPLIT_YA(3, 4); else ESPLIT_YA(3, 8); }
     else if (LT == 5) { if (small) ESPLIT_YA(5, 4); else ESPLIT_YA(5, 8); }
     else if (LT == 8) { if (small) ESPLIT_YA(8, 4); else ESPLIT_YA(8, 8); }
@@ -1745,6 +1750,12 @@ int run_latent_class(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int maxr
     return VLGP_OK;
 }
 
+// the lane-per-task instantiation of a launch: compiled for ranks <= 13 unless a latent at 14 is in it
+int lane_rtop(const int* rk, int n) {
+    int rtop = 0;
+    for (int i = 0; i < n; ++i) rtop = rk[i] > rtop ? rk[i] : rtop;
+    return rtop <= 13 ? 13 : 14;
+}
 // one workgroup (four waves) per (latent, group of 64 units): estep_lane.h
 int run_latent_lane(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, bool mean) {
     const int groups = (A.M + 63) / 64;
@@ -1755,9 +1766,7 @@ int run_latent_lane(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, bool mean
         return vlgp_fail(ctx, VLGP_ERR_ARG, "lane-per-task E-step launch needs %zu bytes of LDS, the device has %d", lds, ctx->lds_max);
     const dim3 grid((unsigned)(groups * A.n_lat)), blk(256);
     hipStream_t st = ln.st;
-    int rtop = 0;
-    for (int i = 0; i < A.n_lat; ++i) rtop = A.shg_rk[i] > rtop ? A.shg_rk[i] : rtop;
-    auto fn = rtop <= 13 ? (!mean ? esplit_lane<0, 13> : (last ? esplit_lane<2, 13> : esplit_lane<1, 13>))
+    auto fn = lane_rtop(A.shg_rk, A.n_lat) == 13 ? (!mean ? esplit_lane<0, 13> : (last ? esplit_lane<2, 13> : esplit_lane<1, 13>))
                          : (!mean ? esplit_lane<0> : (last ? esplit_lane<2> : esplit_lane<1>));
     if (lds > 64 * 1024)
         HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1767,6 +1776,8 @@ int run_latent_lane(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, bool mean
     return VLGP_OK;
 }
 
+// the lane-per-task code of a mixed launch is compiled for ranks <= 13 only (plan_estep_split: rank 14 rides with the waves)
+constexpr int MIX_RTOP = 13;
 // the lane-per-task blocks of `Aln` and the wave-per-task blocks of `Alt` (class maxra: 20 / 24 / 32) as one grid (esplit_mix)
 int run_latent_mix(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& Aln, const SplitArgs& Alt, int maxra, bool mean) {
     const int n_lane = ((Aln.M + 63) / 64) * Aln.n_lat;
@@ -1782,10 +1793,10 @@ int run_latent_mix(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& Aln, const Sp
     hipStream_t st = ln.st;
     const int kind = !mean ? 0 : (last ? 2 : 1);
     for (int i = 0; i < Aln.n_lat; ++i)
-        if (Aln.shg_rk[i] > 13) return vlgp_fail(ctx, VLGP_ERR_STATE, "mixed E-step launch with a lane-per-task rank above 13");
+        if (Aln.shg_rk[i] > MIX_RTOP) return vlgp_fail(ctx, VLGP_ERR_STATE, "mixed E-step launch with a lane-per-task rank above 13");
 #define ESPLIT_MIX(KINDV, RA)                                                                                       \
     do {                                                                                                            \
-        auto fn = esplit_mix<KINDV, RA, 13>;                                                                          \
+        auto fn = esplit_mix<KINDV, RA, MIX_RTOP>;                                                                    \
         if (lds > 64 * 1024)                                                                                        \
             HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn),                                      \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
@@ -1827,13 +1838,23 @@ struct LatentClasses {
     bool mix = false;  // lane-per-task and wave-per-task latents in one launch (esplit_mix)
 };
 
+// the class of the hi launch: in a mixed launch the latents of rank <= 16 ride in it, at class 20 at least
+int hi_maxra(const LatentClasses& C) { return (C.mix && C.maxra_hi < 20) ? 20 : C.maxra_hi; }
+// the rank <= 16 launch stages G once per workgroup (one latent x four units) when the set has ONE prior
+bool lo_shares_g(const vlgp_ctx* ctx, const LatentClasses& C) {
+    return C.single_T > 0 && C.single && !ctx->sw.estep_no_shared_g;
+}
+// latents of the hi launch (in a mixed launch those of rank <= 16 ride in it), and whether the rank <= 16 launch runs
+int n_hi_launch(const LatentClasses& C) { return C.n_hi + (C.mix ? C.n_lo : 0); }
+bool lo_launch(const LatentClasses& C) { return C.n_lo > 0 && !C.mix; }
+
 int run_latent(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const LatentClasses& C, bool mean) {
     // lane-per-task latents AND others: one mixed launch (esplit_mix) instead of two or three dependent ones; the latents
     // of rank 15, 16 then ride in the class of the higher ones (VLGP_ESTEP_MIX=0: the separate launches)
     const bool mix = C.mix;
     SplitArgs Ahi = A;
-    const int n_hi = C.n_hi + (mix ? C.n_lo : 0);
-    const int maxra_hi = (mix && C.maxra_hi < 20) ? 20 : C.maxra_hi;
+    const int n_hi = n_hi_launch(C);
+    const int maxra_hi = hi_maxra(C);
     if (n_hi) {  // the long tasks first
         Ahi.n_lat = n_hi;
         for (int i = 0; i < C.n_hi; ++i) Ahi.lat[i] = C.hi[i];
@@ -1865,18 +1886,17 @@ int run_latent(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const LatentClasses& 
         A.clk = ctx->d_clk;
         A.clk_kind = ctx->sw.lane_clock;
         if (mix) {
-            ctx->last_estep_mix = 1;
             return run_latent_mix(ctx, ln, A, Ahi, maxra_hi, mean);
         }
         CHK(run_latent_lane(ctx, ln, A, mean));
     }
-    if (C.n_lo) {
+    if (lo_launch(C)) {  // (a mixed launch has returned above: C.mix needs lane-per-task latents)
         A.n_lat = C.n_lo;
         for (int i = 0; i < C.n_lo; ++i) A.lat[i] = C.lo[i];
         A.pkl = tri_packed_size(16);
         A.lds_g = C.lds_g_lo;
         A.shg = 0;
-        if (C.single_T > 0 && C.single && !ctx->sw.estep_no_shared_g) {
+        if (lo_shares_g(ctx, C)) {
             for (int i = 0; i < C.n_lo; ++i) {
                 A.shg_rk[i] = C.single->rl[C.lo[i]];
                 A.shg_gl[i] = C.single->d_compact + C.single->goff[C.lo[i]];
@@ -1899,6 +1919,7 @@ int run_latent(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const LatentClasses& 
 // What launch_estep_split decides before it touches the device: whether it takes the set (switches and size rules, DESIGN
 // 4.1) and with which kernels, classes, lanes and scratch layout (all from the set's own sizes: "path coupling").
 struct SplitPlan {
+    int decline_code = VLGP_ESPLIT_TAKEN;  // VLGP_ESPLIT_* of `decline` (vlgp_debug_estep_plan)
     const char* decline = nullptr;  // not taken, and why; a replicated set turns the reason into an error (nothing else runs it)
     bool lng = false;               // long units (T > 64): one workgroup per (unit, latent) task
     int LT = 0, REC = 0;            // compiled latent count of the passes, doubles per channel record
@@ -1919,31 +1940,31 @@ SplitPlan plan_estep_split(const vlgp_ctx* ctx, const UnitSet& us, const RankSum
     // a replicated set (vlgp_replicate_units) runs here or nowhere: only these row passes leave a channel out, so neither
     // the switches nor the size heuristics may send it to another kernel family -- a limit it exceeds is an error
     const bool rep = us.rep_src >= 0;
-#define SPLIT_DECLINE(cond, what) \
-    do { if (cond) { P.decline = what; return P; } } while (0)
-    SPLIT_DECLINE(!rep && sw.estep_split == 0, "VLGP_ESTEP_SPLIT=0");
-    SPLIT_DECLINE(!rep && sw.estep_generic, "VLGP_ESTEP_GENERIC");
-    SPLIT_DECLINE(L > 10, "L > 10");
-    SPLIT_DECLINE(N > 1024, "N > 1024");
+#define SPLIT_DECLINE(cond, code, what) \
+    do { if (cond) { P.decline_code = code; P.decline = what; return P; } } while (0)
+    SPLIT_DECLINE(!rep && sw.estep_split == 0, VLGP_ESPLIT_OFF, "VLGP_ESTEP_SPLIT=0");
+    SPLIT_DECLINE(!rep && sw.estep_generic, VLGP_ESPLIT_GENERIC, "VLGP_ESTEP_GENERIC");
+    SPLIT_DECLINE(L > 10, VLGP_ESPLIT_L, "L > 10");
+    SPLIT_DECLINE(N > 1024, VLGP_ESPLIT_N, "N > 1024");
     // long units (full-length trials): the same launch sequence with one workgroup per (unit, latent) task, once there
     // are enough tasks to fill the chip (VLGP_ESTEP_LSPLIT=0/1 never / always)
     const bool lng = P.lng = us.Tmax > 64;
     if (lng) {
-        SPLIT_DECLINE(!rep && sw.estep_lsplit == 0, "VLGP_ESTEP_LSPLIT=0");
-        SPLIT_DECLINE(ctx->R > LRP, "long units with prior rank R above the long-unit split limit");
-        SPLIT_DECLINE(!rep && sw.estep_lsplit != 1 && (int64_t)us.M * L < 128, "long units: fewer than 128 tasks");
+        SPLIT_DECLINE(!rep && sw.estep_lsplit == 0, VLGP_ESPLIT_LSPLIT_OFF, "VLGP_ESTEP_LSPLIT=0");
+        SPLIT_DECLINE(ctx->R > LRP, VLGP_ESPLIT_LONG_RANK, "long units with prior rank R above the long-unit split limit");
+        SPLIT_DECLINE(!rep && sw.estep_lsplit != 1 && (int64_t)us.M * L < 128, VLGP_ESPLIT_LONG_FEW, "long units: fewer than 128 tasks");
     }
     // the persistent kernel (one workgroup per unit, two or three per CU) wins while its workgroups are ONE generation
     // (measured at N = 100, L = 5: 500 units 0.89 ms persistent / 1.09 ms split; 1000 units 2.09 / 1.42 ms -- the second
     // generation costs as much as the first however few units it holds)
     SPLIT_DECLINE(!rep && !lng && sw.estep_split != 1 && (us.rows < 16LL * 1024 || us.M <= 2 * ctx->n_cu),
-                  "short units: one generation of persistent workgroups");
-    SPLIT_DECLINE(!lng && rs.rmax > 32, "short units at effective prior rank above 32");
+                  VLGP_ESPLIT_SMALL_SET, "short units: one generation of persistent workgroups");
+    SPLIT_DECLINE(!lng && rs.rmax > 32, VLGP_ESPLIT_RANK, "short units at effective prior rank above 32");
     const bool need_prior = (mode & (EM_FACTOR0 | EM_MEAN | EM_V)) != 0;
     const int maxra = P.maxra = rs.rmax <= 16 ? 16 : (rs.rmax <= 20 ? 20 : (rs.rmax <= 24 ? 24 : 32));
     P.LT = L <= 3 ? 3 : (L <= 5 ? 5 : (L <= 8 ? 8 : 10));
     P.REC = (2 * P.LT + 3 + 1) & ~1;
-    SPLIT_DECLINE(P.REC > 34, "channel records longer than 34 doubles");
+    SPLIT_DECLINE(P.REC > 34, VLGP_ESPLIT_REC, "channel records longer than 34 doubles");
 #undef SPLIT_DECLINE
     P.pkg = lng ? LPK : tri_packed_size(maxra);
     // lane-per-task launches (estep_lane.h): one prior for the whole set, T <= 64; VLGP_ESTEP_LANEPT=0 keeps the
@@ -2013,12 +2034,44 @@ SplitPlan plan_estep_split(const vlgp_ctx* ctx, const UnitSet& us, const RankSum
     return P;
 }
 
+// what launch_estep hears back: 1 split, 2 long split, 3 split with mixed launches (every mode that plans a mixed launch
+// runs one: C.mix needs lane-per-task latents, those a mode with a prior, and such a mode factors or sweeps)
+int split_handled(const SplitPlan& P) { return P.lng ? 2 : (P.C.mix ? 3 : 1); }
+
+// vlgp_debug_estep_plan: the plan as the report's slots, from what the launches read
+void report_split_plan(const vlgp_ctx* ctx, const RankSummary& rs, const SplitPlan& P, bool with_mean, int* out) {
+    const LatentClasses& C = P.C;
+    out[EP_LT] = P.LT; out[EP_REC] = P.REC; out[EP_MAXRA] = P.maxra; out[EP_USE_LANE] = P.use_lane;
+    out[EP_MIX] = C.mix;
+    // (long units run run_latent_long, not run_latent: no classes there)
+    out[EP_MAXRA_HI] = !P.lng && n_hi_launch(C) > 0 ? hi_maxra(C) : 0;
+    int rk[16];
+    for (int i = 0; i < C.n_ln; ++i) rk[i] = C.single->rl[C.ln[i]];
+    out[EP_RTOP] = C.n_ln == 0 ? 0 : (C.mix ? MIX_RTOP : lane_rtop(rk, C.n_ln));
+    out[EP_LO_SHG] = !P.lng && lo_launch(C) && lo_shares_g(ctx, C);
+    out[EP_N_LANES] = P.n_lanes;
+    for (int h = 0; h <= P.n_lanes; ++h) out[EP_CUT + h] = P.cut[h];
+    out[EP_CS] = pass_cs(ctx->N);
+    out[EP_NJ] = with_mean ? ya_nj(ctx->N) : -1;
+    for (int l = 0; l < ctx->L && l < 16; ++l) out[EP_RANK + l] = rs.rlat[l];
+    for (int i = 0; i < C.n_ln; ++i) out[EP_CLASS + C.ln[i]] = VLGP_ECLASS_LANE;
+    for (int i = 0; i < C.n_lo; ++i) out[EP_CLASS + C.lo[i]] = VLGP_ECLASS_LO;
+    for (int i = 0; i < C.n_hi; ++i) out[EP_CLASS + C.hi[i]] = VLGP_ECLASS_HI;
+}
+
 }  // namespace
 
-int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummary& rs, int* handled) {
+int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummary& rs, int* handled, int* report) {
     *handled = 0;
     const SplitPlan P = plan_estep_split(ctx, us, rs, E.mode, E.n_iter);
     const bool rep = us.rep_src >= 0;
+    if (report) {
+        report[EP_DECLINE] = P.decline_code;
+        if (P.decline) return VLGP_OK;
+        report_split_plan(ctx, rs, P, (E.mode & EM_MEAN) != 0, report);
+        *handled = split_handled(P);
+        return VLGP_OK;
+    }
     if (P.decline)
         return rep ? vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: the split E-step cannot run it (%s)", P.decline) : VLGP_OK;
     const int N = ctx->N, L = ctx->L, LT = P.LT, pkg = P.pkg, n_lanes = P.n_lanes, n_it = P.n_it;
@@ -2086,8 +2139,7 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     A.lds_g = 256; A.pkl = pkg; A.n_lat = 0;
     A.shg = 0; A.shg_cap = 0; A.shg_T = 0;
     A.do_v = 0; A.last = 0;
-    *handled = lng ? 2 : 1;
-    ctx->last_estep_mix = 0;
+    *handled = split_handled(P);
     HIPCHK(ctx, hipMemsetAsync(A.failg, 0, sizeof(int) * (size_t)us.M * L, ctx->stream));
 
     const int mode = E.mode;
@@ -2193,6 +2245,5 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
         if (hipGetLastError() != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "esplit_from_lm launch failed");
     }
     vlgp_prof_end(ctx, kind, (double)us.M * (E.n_iter > 0 ? E.n_iter : 1));
-    if (ctx->last_estep_mix && !lng) *handled = 3;
     return rc;
 }

@@ -499,6 +499,37 @@ class Engine:
         self._ck(self.lib.vlgp_debug_mstep_plan(self.h, C.c_int64(int(rows)), iptr(out)))
         return dict(zip(self.MSTEP_PLAN_KEYS, (int(v) for v in out)))
 
+    ESTEP_MODES = {"estep": 1 | 2 | 4, "update_w": 4, "update_v": 1 | 8}  # EM_FACTOR0 | EM_MEAN | EM_W | EM_V (csrc/ctx.h)
+    ESPLIT_DECLINES = ("taken", "VLGP_ESTEP_SPLIT=0", "VLGP_ESTEP_GENERIC", "L > 10", "N > 1024", "VLGP_ESTEP_LSPLIT=0",
+                       "long rank", "long: few tasks", "small set", "rank > 32", "records")  # in the order of _lib.ESPLIT
+    ECLASSES = tuple(k.lower() for k in _lib.ECLASS)
+
+    def estep_plan(self, set_id, n_iter, what="estep", vb=True):
+        """What ``estep`` / ``update_w`` / ``update_v`` would launch for the resident set (vlgp_debug_estep_plan: the
+        dispatch itself, reporting instead of launching).  A dict: ``family`` (one of _lib.ESTEP_PATHS), ``decline`` (why
+        the split E-step did not take the set, one of ESPLIT_DECLINES); for the split families LT, REC, maxra, use_lane,
+        mix, maxra_hi, rtop, lo_shared_g, n_lanes, cuts, CS, NJ, ranks and classes per latent; fast: LT, RP, RA; generic:
+        LT, small, rg."""
+        mode = self.ESTEP_MODES[what] | (8 if what == "estep" and vb else 0)
+        out = np.zeros(_lib.ESTEP_PLAN_LEN, dtype=np.int32)
+        self._ck(self.lib.vlgp_debug_estep_plan(self.h, int(set_id), mode, int(n_iter), iptr(out)))
+        o = [int(v) for v in out]
+        at = lambda name: o[_lib.EP[name]]
+        per_latent = lambda name: o[_lib.EP[name]:_lib.EP[name] + min(self.L, 16)]
+        family = _lib.ESTEP_PATHS[at("FAMILY")]
+        plan = {"family": family, "decline": self.ESPLIT_DECLINES[at("DECLINE")]}
+        if family in ("split", "split_mixed", "long_split"):
+            nl = at("N_LANES")
+            plan.update(LT=at("LT"), REC=at("REC"), maxra=at("MAXRA"), use_lane=at("USE_LANE"), mix=at("MIX"),
+                        maxra_hi=at("MAXRA_HI"), rtop=at("RTOP"), lo_shared_g=at("LO_SHG"), n_lanes=nl,
+                        cuts=o[_lib.EP["CUT"]:_lib.EP["CUT"] + nl + 1], CS=at("CS"), NJ=at("NJ"), ranks=per_latent("RANK"),
+                        classes=[self.ECLASSES[k] for k in per_latent("CLASS")])
+        elif family == "fast":
+            plan.update(LT=at("LT"), RP=at("RP"), RA=at("RA"))
+        elif family == "generic":
+            plan.update(LT=at("LT"), small=at("SMALL"), rg=at("RG"))
+        return plan
+
     def profile_get(self, kind):
         n, ms, units = C.c_int64(0), C.c_double(0), C.c_double(0)
         self._ck(self.lib.vlgp_profile_get(self.h, int(kind), C.byref(n), C.byref(ms), C.byref(units)))
