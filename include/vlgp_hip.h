@@ -149,6 +149,24 @@ int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums);
  * Waits for a pending M-step and norms pass; changes no unit state, no parameter and nothing vlgp_hstep_prepare built.
  * This handle's units only (no reduction over ranks); fixed-order reductions, no atomics: the same bits on every run. */
 int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms, int* n_failed);
+/* Forward prediction: carries the posterior of every (unit, latent) of a plain uploaded set past the unit's last row.
+ * With G (T, r) the compact prior factor the unit's length is bound to, mu, v, w the unit's columns and g the E-step's
+ * working gradient
+ * (g[t] = sum_n a[l, n] res[t, n]; res = y - trunc_exp(eta + 1/2 (a^2).v) Poisson, (y - eta) / noise Gaussian; the v term
+ * dropped when vb == 0):
+ *   H = I_r + G' diag(w) G = Lc Lc',   beta = H^-1 G' (g + w o mu)      (G beta is the next unclipped Newton iterate)
+ *   mu_ext = G_ext[:, :r] beta,   v_ext[t] = |Lc^-1 G_ext[t, :r]'|^2 + sum_{c >= r} G_ext[t, c]^2   (0 when vb == 0)
+ *   fit_terms = {|G beta - mu|^2, |mu|^2}
+ * lengths[n_lengths], strictly increasing, lists every unit length of the set; n_ext[k] >= 1 rows extend a unit of
+ * lengths[k]; G_ext holds the blocks (L, n_ext[k], R) back to back in the order of lengths: the rows of the factorisation
+ * whose first lengths[k] rows are the prior of that length.  mu_ext, v_ext (sum over the units of their n_ext, L),
+ * unit-major; fit_terms (M, L, 2) and n_failed may be NULL.  A pivot of H that is not positive and finite makes the task's
+ * mu_ext, v_ext and fit_terms NaN and is counted in *n_failed.  A cut or replicated set, parameters not set or a length
+ * without a prior: VLGP_ERR_STATE; a length that is not listed, n_ext < 1 or a null output: VLGP_ERR_ARG, the message
+ * naming the offender, nothing changed.  Waits for a pending M-step and norms pass; changes no unit state, no parameter
+ * and nothing vlgp_hstep_prepare built.  Fixed-order reductions, no atomics: the same bits on every run. */
+int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
+                  const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

@@ -114,6 +114,7 @@ _SIGNATURES = {
     "vlgp_debug_mstep_plan": (C.c_int, [_h, C.c_int64, _ip]),
     "vlgp_debug_estep_plan": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip]),
     "vlgp_replicate_groups": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
+    "vlgp_forecast": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

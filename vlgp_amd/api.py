@@ -5,6 +5,7 @@ caller's trial dicts are mutated in place and returned; mu, v, dmu are updated
 in place, w is replaced; numerical failures never raise.  The whole EM loop
 runs on the GPU between one upload and one download.
 """
+import contextlib
 import copy
 import logging
 
@@ -14,7 +15,7 @@ from . import engine as E
 from .preprocess import fill_params, fill_trials, get_config, get_params, initialize
 from .util import segment_starts
 
-__all__ = ["fit", "transform", "FitSession", "bind_priors"]
+__all__ = ["fit", "transform", "forecast", "FitSession", "bind_priors"]
 
 logger = logging.getLogger(__name__)
 
@@ -272,6 +273,72 @@ def transform(trials, params, config, device=0):
         E.infer(dev, params, config)
         dev.pull()
     return trials
+
+
+def _full_factors(eng, lengths, params):
+    """``{T: (L, T, R)}`` for the listed lengths: ``params["cholesky"][T]`` where present, the rest built on the device
+    from ``omega, sigma`` as ``bind_priors`` builds them.  Leaves the engine's prior table empty, ``params`` as it is."""
+    chol = params.get("cholesky") or {}
+    out = {T: np.asarray(chol[T], dtype=float) for T in lengths if T in chol}
+    missing = [T for T in lengths if T not in out]
+    if missing:
+        eng.build_prior(missing, params["omega"], params["sigma"])
+        for T in missing:
+            out[T] = eng.get_prior(T)
+        eng.clear_prior()
+    return out
+
+
+@contextlib.contextmanager
+def _extended(trials, held_in, n_ext, params, config, n_iter, device):
+    """What ``forecast`` and ``evaluation.forward_prediction`` share.  Trial ``i`` is held in up to row ``held_in[i]``
+    and extended by ``n_ext`` rows: the factor of length ``held_in[i] + n_ext`` gives its first rows as the prior of the
+    held-in length and its last ``n_ext`` as the extension rows; the latents are inferred on the held-in rows from a
+    zero start (``n_iter`` sweeps, default ``config["max_iter"]``, as ``evaluation.leave_group_out`` infers its own)
+    and carried forward by ``Engine.forecast``.  Yields ``(eng, mu_ext, v_ext, fit_terms, n_failed)`` with the held-in
+    rows still resident as set ``SET_TRIALS``; ``n_failed`` adds the E-step's failed updates and the failed tasks of
+    the extension."""
+    L = int(params["zdim"])
+    n_iter = int(config["max_iter"] if n_iter is None else n_iter)
+    vb = config["method"] == "VB"
+    units = [{"y": tr["y"][:T], "x": None if tr.get("x") is None else tr["x"][:T],
+              "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))} for tr, T in zip(trials, held_in)]
+    with E.Engine.for_params(params, device) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        full = _full_factors(eng, sorted({T + n_ext for T in held_in}), params)
+        for T, G in full.items():  # (distinct total lengths give distinct held-in lengths: nothing collides)
+            eng.set_prior(T - n_ext, G[:, :T - n_ext])
+        eng.upload(SET_TRIALS, units)
+        n_failed = eng.estep(SET_TRIALS, n_iter, config["dmu_bound"], vb)
+        mu_ext, v_ext, terms, bad = eng.forecast(SET_TRIALS, {T - n_ext: G[:, T - n_ext:] for T, G in full.items()}, vb=vb)
+        yield eng, mu_ext, v_ext, terms, int(n_failed) + int(bad)
+
+
+def forecast(trials, params, config, n_ahead, n_iter=None, device=0):
+    """Latents of new trials with fitted parameters, and their forecast ``n_ahead`` bins past the end of every trial
+    (``vlgp_amd.evaluation``'s module docstring defines the extension).
+
+    The prior of a trial of ``T`` bins is the first ``T`` rows of the factor of length ``T + n_ahead``
+    (``params["cholesky"][T + n_ahead]`` where present, otherwise built from ``omega, sigma`` on the device); its last
+    ``n_ahead`` rows carry the posterior forward.  Inference starts from zero and runs ``n_iter`` E-step iterations
+    (default ``config["max_iter"]``).  ``trials`` (``y``, and ``x`` with regressors) and ``params`` are not modified.
+
+    Returns a list with one dict per trial: ``mu``, ``v``, ``w`` (T, L) of the observed bins and ``mu_ahead``,
+    ``v_ahead`` (n_ahead, L).  No rates: there are no future regressors.  A (trial, latent) whose posterior could not be
+    factored has NaN in its ``mu_ahead``, ``v_ahead`` column."""
+    if isinstance(n_ahead, bool) or not isinstance(n_ahead, (int, np.integer)) or n_ahead < 1:
+        raise ValueError("n_ahead must be an integer >= 1, got %r" % (n_ahead,))
+    n_ahead = int(n_ahead)
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    with _extended(trials, lengths, n_ahead, params, config, n_iter, device) as (eng, mu_ext, v_ext, _, _):
+        state = eng.download(SET_TRIALS, ("mu", "v", "w"))
+    bounds = np.cumsum([0] + lengths)
+    out = []
+    for i in range(len(trials)):
+        rows, ahead = slice(bounds[i], bounds[i + 1]), slice(i * n_ahead, (i + 1) * n_ahead)
+        out.append({"mu": state["mu"][rows].copy(), "v": state["v"][rows].copy(), "w": state["w"][rows].copy(),
+                    "mu_ahead": mu_ext[ahead].copy(), "v_ahead": v_ext[ahead].copy()})
+    return out
 
 
 def sample_posterior(trial, params, nsamples, reg=1e-6, rng=None, device=0):

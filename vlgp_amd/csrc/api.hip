@@ -993,6 +993,83 @@ extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, doubl
     return VLGP_OK;
 }
 
+// ---- forward prediction ------------------------------------------------------------
+extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
+                             const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed) {
+    NEED_CTX(ctx);
+    CHK(vlgp_prior_collect(ctx));
+    CHK(join_m_reader(ctx));
+    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    UnitSet* us = vlgp_get_set(ctx, set, true);
+    if (!us) return VLGP_ERR_ARG;
+    NOT_REPLICATED(ctx, us, "vlgp_forecast");
+    if (us->parent >= 0) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_forecast refuses a cut set (set %d is cut from set %d)", set, us->parent);
+    if (n_lengths < 1 || !lengths || !n_ext || !G_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs lengths, n_ext and G_ext");
+    if (!mu_ext || !v_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs mu_ext and v_ext");
+    const int N = ctx->N, L = ctx->L, R = ctx->R, M = us->M;
+    std::vector<int64_t> blk((size_t)n_lengths + 1, 0);  // offsets of the (L, n_ext[k], R) blocks inside G_ext
+    for (int k = 0; k < n_lengths; ++k) {
+        if (k > 0 && lengths[k] <= lengths[k - 1])
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: lengths must be strictly increasing (lengths[%d] = %d)", k, lengths[k]);
+        if (n_ext[k] < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: n_ext[%d] = %d for length %d, need >= 1", k, n_ext[k], lengths[k]);
+        blk[(size_t)k + 1] = blk[(size_t)k] + (int64_t)L * n_ext[k] * R;
+    }
+    std::vector<int64_t> tab((size_t)2 * M + 1);  // ext_off (M + 1) | gx_off (M)
+    int64_t* ext_off = tab.data();
+    int64_t* gx_off = ext_off + M + 1;
+    ext_off[0] = 0;
+    for (int m = 0; m < M; ++m) {
+        const int T = (int)(us->off[m + 1] - us->off[m]);
+        const int* at = std::lower_bound(lengths, lengths + n_lengths, T);
+        if (at == lengths + n_lengths || *at != T)
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: unit %d has length %d, which is not listed", m, T);
+        ext_off[m + 1] = ext_off[m] + n_ext[at - lengths];
+        gx_off[m] = blk[(size_t)(at - lengths)];
+    }
+    if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
+    const int64_t tasks = (int64_t)M * L, n_out = ext_off[M] * L;
+    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: too many (unit, latent) pairs");
+    if (n_failed) *n_failed = 0;
+    if (!us->x_ones) CHK(vlgp_refresh_xb(ctx, *us));
+    CHK(vlgp_bind_priors(ctx, *us));
+    int rp = 1;
+    for (int k = 0; k < n_lengths; ++k) {  // the largest effective rank among the set's lengths sizes the task kernel's LDS
+        auto it = ctx->priors.find(lengths[k]);
+        if (it == ctx->priors.end()) continue;  // (listed, but no unit has it)
+        for (int l = 0; l < L; ++l) rp = std::max(rp, it->second.rl[l]);
+    }
+    // one device block of the call's own: z | G_ext | mu_ext | v_ext | terms | the two tables | flags
+    const int64_t o_g = us->rows * L, o_mu = o_g + blk[(size_t)n_lengths], o_v = o_mu + n_out, o_terms = o_v + n_out;
+    const int64_t o_tab = o_terms + 2 * tasks, o_flag = o_tab + (int64_t)tab.size(), need = o_flag + (tasks + 1) / 2;
+    double* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
+    int* d_flag = reinterpret_cast<int*>(d + o_flag);
+    int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
+    std::vector<int> flag((size_t)tasks);
+    int rc = VLGP_OK;
+    hipError_t e = hipMemcpyAsync(d + o_g, G_ext, sizeof(double) * (size_t)blk[(size_t)n_lengths], hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_forecast copy-in failed: %s", hipGetErrorString(e));
+    if (rc == VLGP_OK)
+        rc = launch_forecast(ctx, *us, vb, rp, d, d_tab, d_tab + M + 1, d + o_g, d + o_mu, d + o_v, d + o_terms, d_flag);
+    if (rc == VLGP_OK) {
+        e = hipMemcpyAsync(mu_ext, d + o_mu, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(v_ext, d + o_v, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && fit_terms)
+            e = hipMemcpyAsync(fit_terms, d + o_terms, sizeof(double) * 2 * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_forecast copy-out failed: %s", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    if (rc != VLGP_OK) return rc;
+    int bad = 0;
+    for (int64_t i = 0; i < tasks; ++i) bad += flag[(size_t)i] != 0;
+    if (n_failed) *n_failed = bad;
+    return VLGP_OK;
+}
+
 // ---- parameters ------------------------------------------------------------
 extern "C" int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise) {
     NEED_CTX(ctx);

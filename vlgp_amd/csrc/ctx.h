@@ -334,3 +334,9 @@ int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace
 int launch_elbo(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_part, double* d_sums, double* d_row_ell,
                 double* d_terms, int* d_flag);
+// forward prediction of a plain set (forecast.hip): z = g + w o mu per (row, latent) into d_z (rows, L), then per (unit,
+// latent) beta = (I + G'WG)^-1 G'z carried along the extension rows; d_ext_off (M + 1): first extension row of each unit,
+// d_gx_off (M): offset of the unit's (L, n_ext, R) block inside d_G_ext; d_terms (M, L, 2), d_flag (M, L)
+int launch_forecast(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_z, const int64_t* d_ext_off,
+                    const int64_t* d_gx_off, const double* d_G_ext, double* d_mu_ext, double* d_v_ext, double* d_terms,
+                    int* d_flag);

@@ -244,6 +244,30 @@ class Engine:
                                     C.byref(n)))
         return sums, terms, n.value, row_ell
 
+    def forecast(self, set_id, ext, vb=True):
+        """The posterior of a plain set carried past the last row of every unit (vlgp_forecast).  ``ext``:
+        ``{length: G_ext (L, n_ext, R)}`` for every unit length of the set, the rows that follow the bound prior factor
+        in the same factorisation.  Returns ``(mu_ext, v_ext, fit_terms, n_failed)``: mu_ext, v_ext
+        (sum over the units of their n_ext, L), unit-major; fit_terms (units, L, 2) = ``|G beta - mu|^2, |mu|^2``; the
+        number of (unit, latent) tasks whose factorisation failed (their outputs are NaN).  Changes no state."""
+        units, _, off = self.sets[set_id]
+        lengths = np.ascontiguousarray(sorted(int(T) for T in ext), dtype=np.int32)
+        blocks = [_f64(ext[int(T)]) for T in lengths]
+        for T, G in zip(lengths, blocks):
+            if G.ndim != 3 or G.shape[0] != self.L or G.shape[2] != self.R:
+                raise ValueError("extension rows for length %d must be (%d, n_ext, %d), got %r"
+                                 % (T, self.L, self.R, G.shape))
+        n_ext = np.ascontiguousarray([G.shape[1] for G in blocks], dtype=np.int32)
+        by_len = dict(zip(lengths.tolist(), n_ext.tolist()))
+        total = sum(by_len.get(int(T), 0) for T in np.diff(np.asarray(off)))  # (an unlisted length: the library says so)
+        G_all = _f64(np.concatenate([G.ravel() for G in blocks])) if blocks else np.zeros(0)
+        mu_ext, v_ext = np.empty((total, self.L)), np.empty((total, self.L))
+        terms = np.empty((units, self.L, 2))
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_forecast(self.h, int(set_id), int(bool(vb)), len(lengths), iptr(lengths), iptr(n_ext),
+                                        dptr(G_all), dptr(mu_ext), dptr(v_ext), dptr(terms), C.byref(n)))
+        return mu_ext, v_ext, terms, n.value
+
     def unit_ranks(self, set_id):
         """(units, L) effective rank of the prior factor each (unit, latent) of the set is bound to."""
         _, _, off = self.sets[set_id]

@@ -35,7 +35,33 @@ its all-zero columns dropped (``T x r``), ``w = w[:, l]``, ``mu = mu[:, l]``:
 - ``ELBO = sum E_q log p(y | x) - sum KL``.  Under MAP (``method != "VB"``: a point estimate, no entropy) ``elbo`` and
   ``kl`` are NaN and ``log_joint = sum log p(y | mu) - 1/2 sum beta'beta`` is reported instead.
 
-Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``): the results are the same bits on every run.
+Forward prediction (``forward_prediction``, ``vlgp_amd.forecast``): a posterior extended past its observed bins.  Take
+one unit and one latent ``l``.  ``G`` is the compact prior factor bound to the unit's length (``T_in x r``; compact: the
+leading non-zero columns, as everywhere in the engine), ``G_ext`` (``n_ext x R``) holds the rows of the same
+factorisation that belong to the unobserved bins, ``mu``, ``v``, ``w`` are the unit's stored posterior columns.
+
+- working gradient, the E-step's own residual: ``g[t] = sum_n a[l, n] res[t, n]``; Poisson
+  ``res = y - trunc_exp(eta + 1/2 (a ** 2) . v)``, Gaussian ``res = (y - eta) / noise``, ``eta = a . mu + (b x)``; the
+  ``v`` term is dropped under MAP.
+- weight-space posterior: ``x = G beta`` with ``beta ~ N(0, I_r)`` a priori; ``H = I_r + G' diag(w) G``, ``S = H^-1``,
+  ``beta_hat = S G' (g + w o mu)``.  ``G beta_hat`` is exactly the next unclipped Newton iterate of the E-step (push-through
+  identity ``(I + G G' W)^-1 G = G (I + G'WG)^-1``); at the E-step's fixed point ``beta_hat = G' g``.  Neither the
+  least-squares form ``argmin |G beta - mu|`` (top-row slices of a pivoted factor reach ``cond(G) = 5e8``) nor the bare
+  fixed-point form ``G' g`` (1e8 in relative size three sweeps from a cold start) is used.
+- extension: ``mu_ext = G_ext[:, :r] beta_hat``;
+  ``v_ext[t] = |Lc^-1 G_ext[t, :r]'|^2 + sum_{c >= r} G_ext[t, c]^2`` with ``Lc Lc' = H``.  A column that is zero on every
+  held-in row but not on the extension rows is a weight the data never saw: it keeps its prior variance of 1, which
+  is the second term.  Under MAP ``v_ext = 0``.
+- convergence report per (unit, latent): ``{|G beta_hat - mu|^2, |mu|^2}``; their ratio is ``off_fixed_point``.
+- forward-predicted rate of channel ``n`` at an extension row: the plug-in rate above, evaluated with ``mu_ext``,
+  ``v_ext`` and that row's own regressors.  With ``history > 0`` those regressors contain the held-out spikes, so the
+  prediction is ONE STEP AHEAD: bin ``t`` is predicted from the latents inferred on the held-in bins and the spikes up
+  to ``t - 1``.
+- ``bits_per_spike_past``: bits per spike against a constant rate at the channel's mean count over the HELD-IN rows --
+  what is known at prediction time -- NaN where that mean is 0 and for Gaussian channels.
+
+Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``): the results are the same
+bits on every run.
 """
 import contextlib
 import math
@@ -44,12 +70,12 @@ import numpy as np
 
 from . import engine as E
 from ._lib import ERR_STATE, VlgpError
-from .api import bind_priors
+from .api import _extended, bind_priors
 
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
-           "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms"]
+           "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction"]
 
-SET_TEST, SET_REPLICAS = 0, 2
+SET_TEST, SET_FORWARD, SET_REPLICAS = 0, 1, 2
 
 # Device memory the batched leave-one-out may hold in replicas at once.  A replica costs about ten doubles per
 # (row, latent): its mu, v, w, dmu and the split E-step's scratch (latent-major copies, residual projections, factors)
@@ -338,3 +364,57 @@ def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_it
     out.update(groups=groups, group_of=[k for k, g in enumerate(groups) for _ in g],
                co_bps=co_bits_per_spike(out["ll"], out["ll_null"], out["n_spikes"]))
     return out
+
+
+def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0):
+    """Forward prediction of held-out trials: the last ``n_forward`` bins of every trial predicted from its first bins
+    (module docstring for the definitions).
+
+    ``trials``: dicts with ``y`` (T, N) and, with regressors, ``x`` (T, xdim, N); ``n_forward``: an integer with
+    ``1 <= n_forward < min T``.  For every trial length ``T`` the full factor is ``params["cholesky"][T]`` where present,
+    otherwise built from ``omega, sigma`` on the device; its first ``T - n_forward`` rows are the prior of the held-in
+    rows, its last ``n_forward`` rows extend the posterior.  The latents are inferred on the held-in rows from a zero
+    start, ``n_iter`` E-step iterations (default ``config["max_iter"]``), as ``leave_group_out`` infers its own; the
+    forward rows are then scored by ``vlgp_loglik`` under ``mu_ahead, v_ahead``.  Neither ``params`` nor the trials are
+    modified.
+
+    Returns a dict: per trial ``mu_ahead``, ``v_ahead`` (n_forward, L) and ``rate`` (n_forward, N; Gaussian: means); per
+    channel ``ll``, ``ll_null``, ``n_spikes``, ``bits_per_spike`` (``bits_per_spike``'s null: the channel's mean count
+    over the forward rows, comparable with ``leave_group_out``) and ``ll_null_past``, ``bits_per_spike_past`` (null: the
+    mean count over the held-in rows); ``fp_bps`` and ``fp_bps_past``, pooled by ``co_bits_per_spike``'s rule;
+    ``off_fixed_point`` (trials, L); ``n_failed`` (failed E-step updates plus (trial, latent) extensions whose ``H`` had
+    a pivot that was not positive: their NaN reaches every number they enter)."""
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    if isinstance(n_forward, bool) or not isinstance(n_forward, (int, np.integer)):
+        raise ValueError("n_forward must be an integer, got %r" % (n_forward,))
+    if not lengths or not 1 <= n_forward < min(lengths):
+        raise ValueError("need 1 <= n_forward < the shortest trial (%s bins), got %d"
+                         % (min(lengths) if lengths else "no", n_forward))
+    nf = int(n_forward)
+    vb = config["method"] == "VB"
+    held_in = [T - nf for T in lengths]
+    with _extended(trials, held_in, nf, params, config, n_iter, device) as (eng, mu_ext, v_ext, terms, n_failed):
+        ahead = [{"y": tr["y"][T:], "x": None if tr.get("x") is None else tr["x"][T:],
+                  "mu": mu_ext[i * nf:(i + 1) * nf], "v": v_ext[i * nf:(i + 1) * nf], "w": None}
+                 for i, (tr, T) in enumerate(zip(trials, held_in))]
+        eng.upload(SET_FORWARD, ahead)
+        sums, rate = eng.loglik(SET_FORWARD, vb=vb, want_rate=True)
+        gauss = eng.gauss.copy()
+    rows = nf * len(trials)
+    ll, ll_null, ny, bps = bits_per_spike(sums, rows, gauss)
+    past = np.sum([np.sum(np.asarray(tr["y"][:T], dtype=float), axis=0) for tr, T in zip(trials, held_in)], axis=0) \
+        / float(sum(held_in))
+    known = ~gauss & (past > 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ll_null_past = np.where(known, ny * np.log(np.where(known, past, 1.0)) - rows * past - sums[:, 3], np.nan)
+        bps_past = np.where(known & (ny > 0), (ll - ll_null_past) / (ny * math.log(2.0)), np.nan)
+        off = terms[:, :, 0] / np.maximum(terms[:, :, 1], np.finfo(float).tiny)
+    return {
+        "mu_ahead": [mu_ext[i * nf:(i + 1) * nf].copy() for i in range(len(trials))],
+        "v_ahead": [v_ext[i * nf:(i + 1) * nf].copy() for i in range(len(trials))],
+        "rate": [rate[i * nf:(i + 1) * nf].copy() for i in range(len(trials))],
+        "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
+        "ll_null_past": ll_null_past, "bits_per_spike_past": bps_past,
+        "fp_bps": co_bits_per_spike(ll, ll_null, ny), "fp_bps_past": co_bits_per_spike(ll, ll_null_past, ny),
+        "off_fixed_point": off, "n_failed": int(n_failed),
+    }
