@@ -322,6 +322,23 @@ def test_singular_pair_is_counted_and_nan_not_a_fault(V):
     assert np.all(np.isfinite(sums))
 
 
+def test_map_sums_of_y_and_rate_are_the_bits_of_vlgp_loglik(V):
+    """vlgp_loglik and vlgp_elbo share the row model and the four-sum reduction (csrc/eval_wave.h).  With vb = False
+    both form eta by the same chain, the bound adds a variance term of 0.0 to it, and both reduce in the same order:
+    sum y and sum rate (Poisson) / sum eta (Gaussian) per channel are the same bits from either call."""
+    units, params, gauss = _problem([50, 80, 50], 14, 3, [2e-2, 5e-3, 1e-3], seed=11, n_gauss=3, vb=False)
+    with V.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"], gauss) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(SET, units)
+        for T, G in params["cholesky"].items():
+            eng.set_prior(T, G)
+        ll = eng.loglik(SET, vb=False)[0]
+        el = eng.elbo(SET, vb=False)[0]
+    assert gauss.sum() == 3 and np.all(np.isfinite(ll)) and np.all(np.isfinite(el))
+    for col in (1, 2):
+        assert ll[:, col].tobytes() == el[:, col].tobytes(), (col, ll[:, col] - el[:, col])
+
+
 def _rank_worker(rank, world, tmp, q):
     os.environ.update({"VLGP_COMM_TRANSPORT": "shm", "RANK": str(rank), "WORLD_SIZE": str(world),
                        "LOCAL_RANK": "0", "MASTER_PORT": "29998", "VLGP_RENDEZVOUS_DIR": tmp})

@@ -103,6 +103,13 @@ int vlgp_ensure_pinned(vlgp_ctx* ctx, int64_t n) {
     return VLGP_OK;
 }
 
+int vlgp_raise_lds(vlgp_ctx* ctx, const void* fn, int bytes) {
+    if (std::find(ctx->lds_attr_done.begin(), ctx->lds_attr_done.end(), fn) != ctx->lds_attr_done.end()) return VLGP_OK;
+    HIPCHK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    ctx->lds_attr_done.push_back(fn);
+    return VLGP_OK;
+}
+
 UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     if (set < 0 || set >= VLGP_MAX_SETS) {
         vlgp_fail(ctx, VLGP_ERR_ARG, "unit set index %d out of range [0, %d)", set, VLGP_MAX_SETS);
@@ -934,35 +941,51 @@ extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double*
 }
 
 // ---- variational lower bound -----------------------------------------------------
-// the waits of vlgp_join_m without its epoch bump: vlgp_elbo only reads, so what vlgp_hstep_prepare built stays valid
-static int join_m_reader(vlgp_ctx* ctx) {
+// what vlgp_elbo and vlgp_forecast do first: a plain set with parameters, xb and its priors bound, nothing pending.  The
+// waits of vlgp_join_m without its epoch bump: both calls only read, so what vlgp_hstep_prepare built stays valid
+static int open_posterior(vlgp_ctx* ctx, int set, const char* what, UnitSet** out) {
+    CHK(vlgp_prior_collect(ctx));
     CHK(wait_norms(ctx));
     if (ctx->m_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_m_done));
-    return VLGP_OK;
-}
-
-extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms,
-                         int* n_failed) {
-    NEED_CTX(ctx);
-    CHK(vlgp_prior_collect(ctx));
-    CHK(join_m_reader(ctx));
     if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
     HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
+    UnitSet* us = *out = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_elbo");
-    if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
-    if (n_failed) *n_failed = 0;
+    NOT_REPLICATED(ctx, us, what);
     if (!us->x_ones) CHK(vlgp_refresh_xb(ctx, *us));
-    CHK(vlgp_bind_priors(ctx, *us));
+    return vlgp_bind_priors(ctx, *us);
+}
+
+// the largest effective rank among the set's lengths: it sizes the LDS of the (unit, latent) kernels
+static int set_rank_max(vlgp_ctx* ctx, const UnitSet& us) {
     int rp = 1, T_seen = -1;
-    for (int m = 0; m < us->M; ++m) {  // the largest effective rank among the set's lengths sizes the KL kernel's LDS
-        const int T = (int)(us->off[m + 1] - us->off[m]);
+    for (int m = 0; m < us.M; ++m) {
+        const int T = (int)(us.off[m + 1] - us.off[m]);
         if (T == T_seen) continue;
         T_seen = T;
         const Prior& pr = ctx->priors.find(T)->second;  // (vlgp_bind_priors found every length)
         for (int l = 0; l < ctx->L; ++l) rp = std::max(rp, pr.rl[l]);
     }
+    return rp;
+}
+
+// the flags of the (unit, latent) tasks, behind everything queued on the stream; *n_failed = how many are set
+static hipError_t count_flags(vlgp_ctx* ctx, const int* d_flag, int64_t tasks, int* n_failed) {
+    std::vector<int> flag((size_t)tasks);
+    hipError_t e = hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && n_failed) *n_failed = (int)(tasks - std::count(flag.begin(), flag.end(), 0));
+    return e;
+}
+
+extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms,
+                         int* n_failed) {
+    NEED_CTX(ctx);
+    UnitSet* us = nullptr;
+    CHK(open_posterior(ctx, set, "vlgp_elbo", &us));
+    if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
+    if (n_failed) *n_failed = 0;
+    const int rp = set_rank_max(ctx, *us);
     const int N = ctx->N, L = ctx->L;
     const int64_t tasks = (int64_t)us->M * L;
     if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo: too many (unit, latent) pairs");
@@ -980,16 +1003,11 @@ extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, doubl
     double* d = ctx->d_elbo;
     int* d_flag = reinterpret_cast<int*>(d + o_flag);
     CHK(launch_elbo(ctx, *us, vb, rp, d, d + o_sums, row_ell ? d + o_rows : nullptr, d + o_terms, d_flag));
-    std::vector<int> flag((size_t)tasks);
     HIPCHK(ctx, hipMemcpyAsync(row_sums, d + o_sums, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(kl_terms, d + o_terms, sizeof(double) * 4 * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream));
     if (row_ell)
         HIPCHK(ctx, hipMemcpyAsync(row_ell, d + o_rows, sizeof(double) * (size_t)us->rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    int bad = 0;
-    for (int64_t i = 0; i < tasks; ++i) bad += flag[(size_t)i] != 0;
-    if (n_failed) *n_failed = bad;
+    HIPCHK(ctx, count_flags(ctx, d_flag, tasks, n_failed));
     return VLGP_OK;
 }
 
@@ -997,12 +1015,8 @@ extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, doubl
 extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
                              const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed) {
     NEED_CTX(ctx);
-    CHK(vlgp_prior_collect(ctx));
-    CHK(join_m_reader(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_forecast");
+    UnitSet* us = nullptr;
+    CHK(open_posterior(ctx, set, "vlgp_forecast", &us));
     if (us->parent >= 0) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_forecast refuses a cut set (set %d is cut from set %d)", set, us->parent);
     if (n_lengths < 1 || !lengths || !n_ext || !G_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs lengths, n_ext and G_ext");
     if (!mu_ext || !v_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs mu_ext and v_ext");
@@ -1026,18 +1040,10 @@ extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, cons
         ext_off[m + 1] = ext_off[m] + n_ext[at - lengths];
         gx_off[m] = blk[(size_t)(at - lengths)];
     }
-    if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
     const int64_t tasks = (int64_t)M * L, n_out = ext_off[M] * L;
     if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: too many (unit, latent) pairs");
     if (n_failed) *n_failed = 0;
-    if (!us->x_ones) CHK(vlgp_refresh_xb(ctx, *us));
-    CHK(vlgp_bind_priors(ctx, *us));
-    int rp = 1;
-    for (int k = 0; k < n_lengths; ++k) {  // the largest effective rank among the set's lengths sizes the task kernel's LDS
-        auto it = ctx->priors.find(lengths[k]);
-        if (it == ctx->priors.end()) continue;  // (listed, but no unit has it)
-        for (int l = 0; l < L; ++l) rp = std::max(rp, it->second.rl[l]);
-    }
+    const int rp = set_rank_max(ctx, *us);
     // one device block of the call's own: z | G_ext | mu_ext | v_ext | terms | the two tables | flags
     const int64_t o_g = us->rows * L, o_mu = o_g + blk[(size_t)n_lengths], o_v = o_mu + n_out, o_terms = o_v + n_out;
     const int64_t o_tab = o_terms + 2 * tasks, o_flag = o_tab + (int64_t)tab.size(), need = o_flag + (tasks + 1) / 2;
@@ -1045,7 +1051,6 @@ extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, cons
     HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
     int* d_flag = reinterpret_cast<int*>(d + o_flag);
     int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
-    std::vector<int> flag((size_t)tasks);
     int rc = VLGP_OK;
     hipError_t e = hipMemcpyAsync(d + o_g, G_ext, sizeof(double) * (size_t)blk[(size_t)n_lengths], hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, ctx->stream);
@@ -1057,17 +1062,12 @@ extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, cons
         if (e == hipSuccess) e = hipMemcpyAsync(v_ext, d + o_v, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && fit_terms)
             e = hipMemcpyAsync(fit_terms, d + o_terms, sizeof(double) * 2 * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = count_flags(ctx, d_flag, tasks, n_failed);
         if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_forecast copy-out failed: %s", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
-    if (rc != VLGP_OK) return rc;
-    int bad = 0;
-    for (int64_t i = 0; i < tasks; ++i) bad += flag[(size_t)i] != 0;
-    if (n_failed) *n_failed = bad;
-    return VLGP_OK;
+    return rc;
 }
 
 // ---- parameters ------------------------------------------------------------

@@ -267,6 +267,8 @@ int vlgp_fail(vlgp_ctx* ctx, int code, const char* fmt, ...);
 
 int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n_doubles);
 int vlgp_ensure_pinned(vlgp_ctx* ctx, int64_t n_doubles);
+// dynamic-LDS ceiling of kernel fn raised to `bytes`, once per handle: the attribute is per device, one handle = one device
+int vlgp_raise_lds(vlgp_ctx* ctx, const void* fn, int bytes);
 int vlgp_allreduce(vlgp_ctx* ctx, double* d_buf, int64_t n);  // in place, sum, on ctx->stream
 int vlgp_hx_allreduce(vlgp_ctx* ctx, double* h_vals, int n);   // host values, n <= 64, rank-order sum; needs ctx->hx
 int vlgp_allreduce_m(vlgp_ctx* ctx, double* d_buf, int64_t n);  // same on the M-step lane (comm_m, mstream)
@@ -329,6 +331,8 @@ int launch_gather(vlgp_ctx* ctx, UnitSet& src, UnitSet& dst, int window);
 // plug-in rates and per-channel log-likelihood sums of a set (evaluate.hip): d_rate (rows, N) for a plain set, (rows_src,
 // n_pairs) for a replicated one, or null; d_sums (slots, 4) with slots = N or n_pairs, written in a fixed order
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums);
+// d_sums (slots, 4) = the partials d_part (slots, n_blk, 4) of each slot added in workgroup order (evaluate.hip)
+int launch_sums_finish(vlgp_ctx* ctx, int slots, int n_blk, const double* d_part, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace

@@ -1076,15 +1076,7 @@ static inline int n_lr_or_all(bool lr, int n_lr, int n_eval) { return lr ? n_lr 
 template <int T, int RC, bool TABG = false, bool TABF = false>
 static int launch_round_lr(vlgp_ctx* ctx, const HRoundArgs& R, int grid, size_t lds_bytes) {
     constexpr int NW = LR_NW;
-    // the dynamic-LDS ceiling is a per-DEVICE attribute of the function: remembered per handle (one handle = one device),
-    // not per process (a second engine on another device never got it)
-    const void* fn = reinterpret_cast<const void*>(hstep_round_lr<T, NW, RC, TABG, TABF>);
-    bool have = false;
-    for (const void* f : ctx->lds_attr_done) have = have || f == fn;
-    if (!have) {
-        HIPCHK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - 512)));
-        ctx->lds_attr_done.push_back(fn);
-    }
+    CHK(vlgp_raise_lds(ctx, reinterpret_cast<const void*>(hstep_round_lr<T, NW, RC, TABG, TABF>), 160 * 1024 - 512));
     hipLaunchKernelGGL((hstep_round_lr<T, NW, RC, TABG, TABF>), dim3(grid), dim3(64 * NW), lds_bytes, ctx->stream, R);
     return VLGP_OK;
 }
