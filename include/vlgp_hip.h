@@ -123,6 +123,22 @@ int vlgp_free_units(vlgp_ctx* ctx, int set);
  * VLGP_ERR_STATE, never another kernel), vlgp_download_units, vlgp_free_units and vlgp_loglik; every other entry point
  * refuses it with VLGP_ERR_STATE.  The same as vlgp_replicate_groups (below) with one channel per group. */
 int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel);
+/* Speckled hold-out: replicas that leave single (row, channel) ENTRIES out -- the general form of vlgp_replicate_groups
+ * (declared at the end of this header), whose groups are masks that are constant along the rows.  held_out is
+ * (n_rep, rows_src, nw) words, nw = (N + 63) / 64: bit n & 63 of word n >> 6 is set when replica k leaves entry (row, n) of
+ * `src` out.  vlgp_estep on `dst` then runs for replica k the E-step with the likelihood terms of those entries removed:
+ * their working residual and curvature are 0, and with them their contributions to y.a, to w and to the Gaussian constant of
+ * w; everything else -- the regressors x as the caller gave them included -- is untouched.  A mask constant along the rows
+ * gives the bits of vlgp_replicate_groups.  A set bit at a position >= N is VLGP_ERR_ARG, the message naming the replica
+ * and the row, nothing changed; a replica with no bit set, a row with every bit set (there w == 0: the prior alone) and a
+ * channel held out on every row are legal.  src, dst, aliasing, lifetime and the entry points that accept the set are those
+ * of vlgp_replicate_groups.  Costs one mask word per (row, 64 channels) and, with a Gaussian channel on the handle, L
+ * doubles per row for the constant of w.
+ * vlgp_loglik on such a set: sums (n_rep, N, 4), slot (k, n) holding the four sums of channel n over exactly the rows where
+ * replica k holds (row, n) out (an empty slot: four zeros); rate (rows_src, N) or NULL, NaN where no replica holds the
+ * entry out, else written from the replica that does -- asking for rate when two replicas hold the same entry out is
+ * VLGP_ERR_ARG (decided when the set is made).  At most 65535 replicas. */
+int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint64_t* held_out);
 /* Plug-in rate and log-likelihood of the observations under the set's current posterior (mu, v):
  *   Poisson   rate = trunc_exp(a_n.mu_t + (b x)_tn + 1/2 (a_n^2).v_t)  (the E-step's rate; vb == 0 drops the v term)
  *             ll = y log rate - rate - lgamma(y + 1);   sums[n] = {sum ll, sum y, sum rate, sum lgamma(y + 1)}
@@ -132,7 +148,7 @@ int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* 
  * (replica, left-out channel) pair, in the order of the channel list the set was made with -- pair p is channel[p] under
  * the posterior of the replica that leaves it out, on the source rows: rate (rows_src, n_pairs) or NULL, sums
  * (n_pairs, 4).  A set made by vlgp_replicate_units has n_pairs == n_rep.  At most 65535 pairs per set (VLGP_ERR_ARG
- * beyond).  Sums cover this handle's units only (no reduction over ranks) and are bitwise reproducible (fixed-order
+ * beyond).  A set made by vlgp_replicate_masked: see there.  Sums cover this handle's units only (no reduction over ranks) and are bitwise reproducible (fixed-order
  * two-stage reduction, no atomics). */
 int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums);
 /* Terms of the variational lower bound of a plain set (uploaded or cut; a replicated set is VLGP_ERR_STATE) under its

@@ -7,7 +7,8 @@ from .engine import (DeviceTrials, Engine, VlgpError, constrain_latent, constrai
                      estep, hstep, infer, make_cholesky, mstep, update_v, update_w, vem)
 from .preprocess import get_config, get_params  # noqa: F401
 from . import evaluation  # noqa: F401,E402
+from .evaluation import impute  # noqa: F401,E402
 from . import model_selection  # noqa: F401,E402
 from .model_selection import cross_validate  # noqa: F401,E402
 
-__all__ = ["fit", "transform", "forecast", "Engine", "DeviceTrials", "VlgpError", "evaluation", "model_selection", "cross_validate"]
+__all__ = ["fit", "transform", "forecast", "Engine", "DeviceTrials", "VlgpError", "evaluation", "model_selection", "cross_validate", "impute"]

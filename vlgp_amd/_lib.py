@@ -64,6 +64,7 @@ _SIGNATURES = {
     "vlgp_stash_mu": (C.c_int, [_h, C.c_int, C.c_int]),
     "vlgp_free_units": (C.c_int, [_h, C.c_int]),
     "vlgp_replicate_units": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip]),
+    "vlgp_replicate_masked": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "vlgp_loglik": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
     "vlgp_elbo": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "vlgp_set_params": (C.c_int, [_h, _dp, _dp, _dp]),

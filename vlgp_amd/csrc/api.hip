@@ -818,6 +818,55 @@ extern "C" int vlgp_free_units(vlgp_ctx* ctx, int set) {
 }
 
 // ---- leave-group-out replicas and held-out likelihood --------------------------
+// what every replicate call checks of its two sets once its own arguments are sound
+static int replicas_check(vlgp_ctx* ctx, int src, int dst, int n_rep, const UnitSet* s, const UnitSet* d) {
+    if (s->rep_src >= 0 || s->parent >= 0 || s->alias || !s->stage_start.empty())
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)", src);
+    if (d->rep_users > 0)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", dst);
+    if ((int64_t)n_rep * s->M > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "too many replicated units");
+    return VLGP_OK;
+}
+
+// dst := n_rep replicas of src, replica-major: offsets, y and x aliased, mu, v, w, dmu its own, copies of the source's
+// (enqueued; the caller adds its tables and synchronises).  From `valid` on free_set releases whatever was allocated,
+// should a later step fail.
+static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s, UnitSet* d) {
+    for (auto& other : ctx->sets)
+        if (other.valid && other.alias && other.parent == dst) free_set(ctx, other);
+    free_set(ctx, *d);
+    const int Ms = s->M, L = ctx->L;
+    const int64_t rs = s->rows;
+    std::vector<int64_t> off((size_t)n_rep * Ms + 1);
+    for (int k = 0; k < n_rep; ++k)
+        for (int m = 0; m < Ms; ++m) off[(size_t)k * Ms + m] = k * rs + s->off[m];
+    off[(size_t)n_rep * Ms] = n_rep * rs;
+    CHK(set_offsets(ctx, *d, n_rep * Ms, off.data()));
+    d->rep_src = src;
+    d->n_rep = n_rep;
+    d->rows_src = rs;
+    d->rep_nw = (ctx->N + 63) / 64;
+    d->x_ones = s->x_ones;
+    d->y = s->y;  // aliased: a copy per replica would be rows x N doubles each
+    d->x = s->x;
+    s->rep_users++;
+    d->valid = true;
+    const size_t nb = (size_t)rs * L * sizeof(double);
+    CHK(dev_alloc(ctx, &d->mu, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, &d->v, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, &d->w, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, &d->dmu, n_rep * rs * L, false));
+    HIPCHK(ctx, hipMalloc(&d->d_rep_xa, sizeof(d->rep_xh)));
+    for (int k = 0; k < n_rep; ++k) {
+        const int64_t o = k * rs * L;
+        HIPCHK(ctx, hipMemcpyAsync(d->mu + o, s->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->v + o, s->v, nb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->w + o, s->w, nb, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d->dmu + o, s->dmu, nb, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return VLGP_OK;
+}
+
 extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* group_start,
                                      const int* channel) {
     NEED_CTX(ctx);
@@ -848,55 +897,62 @@ extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep,
         }
     }
     const int n_pairs = group_start[n_rep];
-    if (s->rep_src >= 0 || s->parent >= 0 || s->alias || !s->stage_start.empty())
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)", src);
-    if (d->rep_users > 0)
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", dst);
-    if ((int64_t)n_rep * s->M > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "too many replicated units");
-    for (auto& other : ctx->sets)
-        if (other.valid && other.alias && other.parent == dst) free_set(ctx, other);
-    free_set(ctx, *d);
-    const int Ms = s->M, L = ctx->L;
-    const int64_t rs = s->rows;
-    std::vector<int64_t> off((size_t)n_rep * Ms + 1);
-    for (int k = 0; k < n_rep; ++k)
-        for (int m = 0; m < Ms; ++m) off[(size_t)k * Ms + m] = k * rs + s->off[m];
-    off[(size_t)n_rep * Ms] = n_rep * rs;
-    CHK(set_offsets(ctx, *d, n_rep * Ms, off.data()));
-    d->rep_src = src;
-    d->n_rep = n_rep;
-    d->rows_src = rs;
+    CHK(replicas_check(ctx, src, dst, n_rep, s, d));
+    CHK(replicas_make(ctx, src, dst, n_rep, s, d));
     d->n_pairs = n_pairs;
-    d->rep_nw = nw;
     d->rep_ch.assign(channel, channel + n_pairs);
-    d->x_ones = s->x_ones;
-    d->y = s->y;  // aliased: a copy per replica would be rows x N doubles each
-    d->x = s->x;
-    s->rep_users++;
-    d->valid = true;  // (from here on free_set releases whatever was allocated, should a step below fail)
-    const size_t nb = (size_t)rs * L * sizeof(double);
-    CHK(dev_alloc(ctx, &d->mu, n_rep * rs * L, false));
-    CHK(dev_alloc(ctx, &d->v, n_rep * rs * L, false));
-    CHK(dev_alloc(ctx, &d->w, n_rep * rs * L, false));
-    CHK(dev_alloc(ctx, &d->dmu, n_rep * rs * L, false));
     HIPCHK(ctx, hipMalloc(&d->d_rep_ch, sizeof(int) * n_pairs));
     HIPCHK(ctx, hipMalloc(&d->d_rep_pair, sizeof(int) * n_pairs));
     HIPCHK(ctx, hipMalloc(&d->d_rep_mask, sizeof(unsigned long long) * mask.size()));
     HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * 16 * n_rep));
-    HIPCHK(ctx, hipMalloc(&d->d_rep_xa, sizeof(d->rep_xh)));
     HIPCHK(ctx, hipMemcpyAsync(d->d_rep_ch, channel, sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d->d_rep_pair, pair_rep.data(), sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d->d_rep_mask, mask.data(), sizeof(unsigned long long) * mask.size(), hipMemcpyHostToDevice,
                                ctx->stream));
-    for (int k = 0; k < n_rep; ++k) {
-        const int64_t o = k * rs * L;
-        HIPCHK(ctx, hipMemcpyAsync(d->mu + o, s->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d->v + o, s->v, nb, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d->w + o, s->w, nb, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d->dmu + o, s->dmu, nb, hipMemcpyDeviceToDevice, ctx->stream));
-    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the channel list is the caller's again, the host tables may go)
-    d->valid = true;
+    return VLGP_OK;
+}
+
+// Speckled hold-out: replica k leaves out the entries (row, n) whose bit is set in held_out[(k rows_src + row) nw + (n >> 6)].
+// The mask goes to the device as the caller packed it -- (n_rep rows_src, nw) is the row order of the replicated set.
+extern "C" int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint64_t* held_out) {
+    NEED_CTX(ctx);
+    ctx->hmom_us = nullptr;
+    CHK(vlgp_join_m(ctx));
+    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    UnitSet* s = vlgp_get_set(ctx, src, true);
+    UnitSet* d = vlgp_get_set(ctx, dst, false);
+    if (!s || !d) return VLGP_ERR_ARG;
+    if (src == dst || n_rep < 1 || !held_out) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad replicate arguments");
+    CHK(replicas_check(ctx, src, dst, n_rep, s, d));
+    // no bit at a channel >= N; whether two replicas hold the same entry out (vlgp_loglik then writes no rate)
+    const int N = ctx->N, nw = (N + 63) / 64;
+    const int64_t rs = s->rows;
+    const uint64_t beyond = (N & 63) ? ~0ull << (N & 63) : 0ull;  // bits of the last word past channel N - 1
+    std::vector<uint64_t> seen((size_t)rs * nw, 0ull);
+    bool overlap = false;
+    for (int k = 0; k < n_rep; ++k)
+        for (int64_t r = 0; r < rs; ++r) {
+            const uint64_t* mk = held_out + ((size_t)k * rs + r) * nw;
+            if (mk[nw - 1] & beyond)
+                return vlgp_fail(ctx, VLGP_ERR_ARG, "replica %d holds out a channel outside [0, %d) at row %lld", k, N,
+                                 (long long)r);
+            for (int q = 0; q < nw; ++q) {
+                uint64_t& sw = seen[(size_t)r * nw + q];
+                overlap = overlap || (sw & mk[q]) != 0;
+                sw |= mk[q];
+            }
+        }
+    CHK(replicas_make(ctx, src, dst, n_rep, s, d));
+    d->rep_by_row = true;
+    d->rep_overlap = overlap;
+    d->n_pairs = 0;
+    const size_t words = (size_t)n_rep * rs * nw;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "mask words are 64 bits");
+    HIPCHK(ctx, hipMalloc(&d->d_rep_mask, sizeof(uint64_t) * words));
+    if (ctx->n_gauss > 0) HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * (size_t)n_rep * rs * ctx->L));
+    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_mask, held_out, sizeof(uint64_t) * words, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the mask is the caller's again)
     return VLGP_OK;
 }
 
@@ -917,17 +973,24 @@ extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double*
     if (!sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik needs sums");
     if (us->parent >= 0 && !us->alias)
         return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on a copied cut: merge it and score the source set");
-    const bool rep = us->rep_src >= 0;
+    const bool rep = us->rep_src >= 0, by_row = rep && us->rep_by_row;
+    if (by_row && rate && us->rep_overlap)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: the masks of set %d overlap (an entry is held out by more than one "
+                         "replica): no rate, sums only", set);
     UnitSet& rows_of = rep ? ctx->sets[us->rep_src] : *us;  // the y / x rows
     if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
-    const int slots = rep ? us->n_pairs : ctx->N;
-    const int64_t n_rate = rep ? us->rows_src * us->n_pairs : us->rows * ctx->N;
+    const int slots = by_row ? us->n_rep * ctx->N : (rep ? us->n_pairs : ctx->N);
+    const int64_t n_rate = by_row ? us->rows_src * ctx->N : (rep ? us->rows_src * us->n_pairs : us->rows * ctx->N);
     const int64_t o_sums = rate ? n_rate : 0;
     double* d_rate = nullptr;
     double* d_out = nullptr;
     HIPCHK(ctx, hipMalloc(&d_out, sizeof(double) * (size_t)(o_sums + 4 * (int64_t)slots)));
     if (rate) d_rate = d_out;
-    int rc = launch_loglik(ctx, *us, vb, d_rate, d_out + o_sums);
+    int rc = VLGP_OK;
+    if (by_row && rate &&  // NaN (every byte 0xff) where no replica holds the entry out
+        hipMemsetAsync(d_rate, 0xff, sizeof(double) * (size_t)n_rate, ctx->stream) != hipSuccess)
+        rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_loglik: filling the rates failed");
+    if (rc == VLGP_OK) rc = launch_loglik(ctx, *us, vb, d_rate, d_out + o_sums);
     if (rc == VLGP_OK) {
         hipError_t e = hipMemcpyAsync(sums, d_out + o_sums, sizeof(double) * 4 * slots, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && rate)

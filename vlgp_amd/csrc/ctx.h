@@ -60,6 +60,12 @@ struct UnitSet {
     // E-step reads the groups as bit masks, rep_nw = (N + 63) / 64 words per replica, bit n & 63 of word n >> 6 set when
     // the replica leaves channel n out.  y and xb are the source's (aliased, never freed here); mu, v, w, dmu are the
     // replicas' own.  The source counts the replica sets that alias it (rep_users) and refuses re-upload / free.
+    // A masked set (vlgp_replicate_masked) is the general form, one mask per ROW: rep_by_row, d_rep_mask (n_rep rows_src,
+    // rep_nw) indexed by the replicated row, d_rep_wconst (n_rep rows_src, L) or null without a Gaussian channel, no pairs
+    // (n_pairs == 0); rep_overlap: some (row, channel) is held out by more than one replica (decided on the host when the
+    // set is made: vlgp_loglik then has no single replica to write that entry's rate from).
+    bool rep_by_row = false;
+    bool rep_overlap = false;
     int rep_src = -1;
     int n_rep = 0;
     int n_pairs = 0;
@@ -69,7 +75,7 @@ struct UnitSet {
     int* d_rep_ch = nullptr;          // (n_pairs) left-out channel of each pair
     int* d_rep_pair = nullptr;        // (n_pairs) replica of each pair
     unsigned long long* d_rep_mask = nullptr;  // (n_rep, rep_nw) membership masks
-    double* d_rep_wconst = nullptr;   // (n_rep, 16): Gaussian constant of w per replica (estep_split.hip)
+    double* d_rep_wconst = nullptr;   // (n_rep, 16): Gaussian constant of w per replica (estep_split.hip); masked: per row
     void* d_rep_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
     double rep_xh[8] = {};
     int rep_users = 0;

@@ -98,6 +98,14 @@ struct ExclArgs {
     const double* mu_lm;   // the row passes: unshifted latent-major mu -- a lane's row base is A.mu - mu_lm
 };  // (no field for nw: the kernels have N, and the struct -- an argument of every esplit_ya -- keeps its size)
 __host__ __device__ inline int excl_words(int N) { return (N + 63) >> 6; }
+// A masked set (vlgp_replicate_masked) is the general form of that table, one mask per ROW of the replicated set: `mask`
+// is (n_rep rows_src, nw), indexed by the absolute replicated row k rows_src + sr, and `wconst` is (n_rep rows_src, L), the
+// Gaussian constant of w of that row (null: the handle has no Gaussian channel, the constant is 0).  The bit test and
+// select sit where the per-replica mode has them, so a mask that is constant along the rows of a replica gives that
+// replica the bits of the group path.  This third mode is a template VALUE of the row passes, not a new parameter: their
+// first argument is LT | EX_BY_ROW (with EXCL true).  A parameter more, or another type for EXCL, would rename every
+// instantiation there is; this way each keeps its arguments, its symbol and its code.
+enum { EX_BY_ROW = 64 };  // (LT <= 10)
 
 // ---------------------------------------------------------------------------------------------------------
 // channel records, Poisson channels first: a[LT] | a^2 / 2 [LT] | b | c (1/noise or 1) | id (integer bits) | pad
@@ -185,6 +193,23 @@ esplit_excl_wconst(int N, int L, int n_rep, int nw, const double* __restrict__ a
     wconst[i] = s;
 }
 
+// the same per ROW of a masked set (vlgp_replicate_masked): wconst (rows, L), mask (rows, nw), rows = n_rep rows_src; the
+// chain of esplit_excl_wconst, so a mask constant along the rows of a replica gives every row that replica's constant
+__global__ void __launch_bounds__(256)
+esplit_row_wconst(int N, int L, int64_t rows, int nw, const double* __restrict__ a, const double* __restrict__ noise,
+                  const int* __restrict__ gauss, const unsigned long long* __restrict__ mask,
+                  double* __restrict__ wconst) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    const unsigned long long* mk = mask + row * nw;
+    for (int l = 0; l < L; ++l) {
+        double s = 0.0;
+        for (int n = 0; n < N; ++n)
+            if (gauss[n] && !((mk[n >> 6] >> (n & 63)) & 1ull)) s = fma(a[l * N + n] * a[l * N + n], 1.0 / noise[n], s);
+        wconst[row * L + l] = s;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // (rows, L) <-> (L, rows): the split kernels work on latent-major copies -- a wave whose lanes are rows (passes) or time
 // bins of one latent (latent kernels) then touches 8 contiguous bytes per lane instead of 8 of every 8 L (PMC: ~500
@@ -220,10 +245,13 @@ esplit_from_lm(int L, int64_t rows, const double* __restrict__ b0, const double*
 // time (128 contiguous bytes per row and load), four rows per wave and step; the per-channel coefficients of a lane's
 // channels stay in registers (N <= 16 NJ).  The lane-per-row form (esplit_pass<SP_YA>) reads 8 bytes of every 8 N:
 // 466 MB of HBM traffic for 160 MB of y at C3 (PMC), 108 us.
-template <int LT, int NJ, bool EXCL = false>
+template <int LTM, int NJ, bool EXCL = false>
 __global__ void __launch_bounds__(256)
 esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, const double* __restrict__ ycoef,
           double* __restrict__ ya, int rows_per_wave, ExclArgs X) {
+    constexpr int LT = LTM & (EX_BY_ROW - 1);
+    constexpr bool BY_ROW = (LTM & EX_BY_ROW) != 0;
+    static_assert(EXCL || !BY_ROW, "a mask per row is an exclusion mode");
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int r4 = lane >> 4, c16 = lane & 15;
     double cf[NJ][LT];
@@ -245,7 +273,8 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
             const int64_t ar = X.row_base + (in ? row : 0), k = ar / X.rows_src;
             yr = X.y + (ar - k * X.rows_src) * N;
 #pragma unroll
-            for (int q = 0; q < (NJ + 3) / 4; ++q) ex[q] = q < excl_words(N) ? X.mask[k * excl_words(N) + q] >> c16 : 0ull;
+            for (int q = 0; q < (NJ + 3) / 4; ++q)
+                ex[q] = q < excl_words(N) ? X.mask[(BY_ROW ? ar : k) * excl_words(N) + q] >> c16 : 0ull;
         }
         double acc[LT];
 #pragma unroll
@@ -274,9 +303,12 @@ esplit_ya(int N, int L, int64_t rows, int64_t ld, const double* __restrict__ y, 
 // CS: the channels of one row group are split over CS waves of the workgroup (a lone wave walking all N channels
 // is a chain of N dependent record loads + exponentials: measured 35 us at two waves per SIMD and 41 us at four --
 // latency, not throughput); the partial sums meet in LDS and are added in wave order (deterministic).
-template <int LT, int KIND, bool HASXB, int CS, bool EXCL = false>
+template <int LTM, int KIND, bool HASXB, int CS, bool EXCL = false>
 __global__ void __launch_bounds__(256)
 esplit_pass(SplitArgs A, const double* __restrict__ cols) {
+    constexpr int LT = LTM & (EX_BY_ROW - 1);
+    constexpr bool BY_ROW = (LTM & EX_BY_ROW) != 0;
+    static_assert(EXCL || !BY_ROW, "a mask per row is an exclusion mode");
     constexpr int REC = rec_len<LT>();
     constexpr int RPB = 256 / CS;  // rows per workgroup
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -305,6 +337,7 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
     // and the records of a list come in channel order, so the word changes at most every 64 records (never for
     // N <= 64); the replica is per lane -- a wave may straddle two -- and so is the word
     int rk = 0, exw = 0;
+    int64_t xrow = 0;  // BY_ROW: the lane's absolute replicated row
     unsigned long long ex = 0;
     const unsigned long long* exm = nullptr;
     ExclArgs X;
@@ -313,7 +346,8 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
         X.row_base = A.mu - X.mu_lm;
         const int64_t ar = X.row_base + rr, k = ar / X.rows_src, sr = ar - k * X.rows_src;
         rk = (int)k;
-        exm = X.mask + k * excl_words(N);
+        xrow = ar;
+        exm = X.mask + (BY_ROW ? ar : k) * excl_words(N);
         ex = exm[0];
         yrow = X.y + sr * N;
         xbrow = HASXB ? X.xb + sr * N : nullptr;
@@ -454,7 +488,8 @@ esplit_pass(SplitArgs A, const double* __restrict__ cols) {
                     if (A.sv) A.sv[(int64_t)l * A.ld + row] = fma(wv[l], mr[l], rav);
                 } else {
                     double wc;
-                    if constexpr (EXCL) wc = X.wconst[rk * 16 + l];
+                    if constexpr (BY_ROW) wc = X.wconst ? X.wconst[xrow * L + l] : 0.0;
+                    else if constexpr (EXCL) wc = X.wconst[rk * 16 + l];
                     else wc = A.wconst[l];
                     A.w[(int64_t)l * A.ld + row] = fma(2.0, acc[l], wc);  // (the records hold a^2 / 2)
                     if ((A.dmask >> l) & 1u) A.mu[(int64_t)l * A.ld + row] = mr[l];
@@ -1656,6 +1691,7 @@ struct Lane {
     hipStream_t st;
     const ExclArgs* excl;      // host copy (an argument of the y pass), or null: a plain set
     const ExclArgs* excl_dev;  // its device copy (the row passes read it through SplitArgs::excl)
+    bool by_row;               // the table holds one mask per row (EX_BY_ROW, vlgp_replicate_masked), not one per replica
 };
 
 // one row pass (KIND) with its channels split over CS waves per row group; a replicated set's launch reads the replica table
@@ -1663,7 +1699,11 @@ template <int LT, int KIND, int CS>
 int run_pass_cs(vlgp_ctx* ctx, const Lane& ln, SplitArgs A, const double* cols) {
     constexpr int RPB = 256 / CS;
     const dim3 grid((unsigned)((A.rows + RPB - 1) / RPB)), blk(256);
-    if (ln.excl) {
+    if (ln.excl && ln.by_row) {
+        A.excl = ln.excl_dev;
+        if (A.xb) hipLaunchKernelGGL((esplit_pass<LT | EX_BY_ROW, KIND, true, CS, true>), grid, blk, 0, ln.st, A, cols);
+        else hipLaunchKernelGGL((esplit_pass<LT | EX_BY_ROW, KIND, false, CS, true>), grid, blk, 0, ln.st, A, cols);
+    } else if (ln.excl) {
         A.excl = ln.excl_dev;
         if (A.xb) hipLaunchKernelGGL((esplit_pass<LT, KIND, true, CS, true>), grid, blk, 0, ln.st, A, cols);
         else hipLaunchKernelGGL((esplit_pass<LT, KIND, false, CS, true>), grid, blk, 0, ln.st, A, cols);
@@ -1712,7 +1752,9 @@ int run_ya(vlgp_ctx* ctx, const Lane& ln, const SplitArgs& A, int LT, const doub
     const ExclArgs X = ln.excl ? *ln.excl : ExclArgs{};
 #define ESPLIT_YA(LTV, NJV)                                                                                              \
     do {                                                                                                                 \
-        if (ln.excl) hipLaunchKernelGGL((esplit_ya<LTV, NJV, true>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, \
+        if (ln.excl && ln.by_row) hipLaunchKernelGGL((esplit_ya<LTV | EX_BY_ROW, NJV, true>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, \
+                                                     A.y, ycoef, A.ya, rows_per_wave, X);                                \
+        else if (ln.excl) hipLaunchKernelGGL((esplit_ya<LTV, NJV, true>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, \
                                         A.ya, rows_per_wave, X);                                                         \
         else hipLaunchKernelGGL((esplit_ya<LTV, NJV>), grid, blk, 0, st, A.N, A.L, A.rows, A.ld, A.y, ycoef, A.ya,       \
                                 rows_per_wave, X);                                                                       \
@@ -2103,8 +2145,12 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
         XA.rows_src = us.rows_src;
         XA.row_base = 0;
         XA.mu_lm = nullptr;  // (set below, with the latent-major copies)
-        hipLaunchKernelGGL(esplit_excl_wconst, dim3((unsigned)((us.n_rep * 16 + 255) / 256)), dim3(256), 0, ctx->stream, N,
-                           L, us.n_rep, us.rep_nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_mask, us.d_rep_wconst);
+        if (!us.rep_by_row)
+            hipLaunchKernelGGL(esplit_excl_wconst, dim3((unsigned)((us.n_rep * 16 + 255) / 256)), dim3(256), 0, ctx->stream, N,
+                               L, us.n_rep, us.rep_nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_mask, us.d_rep_wconst);
+        else if (us.d_rep_wconst)  // (null: no Gaussian channel, the row passes take the constant as 0)
+            hipLaunchKernelGGL(esplit_row_wconst, dim3((unsigned)((us.rows + 255) / 256)), dim3(256), 0, ctx->stream, N, L,
+                               us.rows, us.rep_nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_mask, us.d_rep_wconst);
         HIPCHK(ctx, hipGetLastError());
     }
 
@@ -2147,7 +2193,8 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     const int kind = lng ? VLGP_PROF_ESTEP_LONG
                          : (P.maxra <= 16 ? VLGP_PROF_ESTEP_RA16 : (P.maxra <= 24 ? VLGP_PROF_ESTEP_RA24 : VLGP_PROF_ESTEP_RA32));
     vlgp_prof_begin(ctx, kind);
-    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.d_rep_xa) : nullptr};
+    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.d_rep_xa) : nullptr,
+                   rep && us.rep_by_row};
     int rc = VLGP_OK;
     if (with_mean) rc = run_ya(ctx, main_lane, A, LT, cols, ycoef);
 

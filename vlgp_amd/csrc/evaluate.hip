@@ -62,6 +62,54 @@ __global__ void __launch_bounds__(256) ll_rows(LlArgs A) {
     }
 }
 
+// A masked set (vlgp_replicate_masked): blockIdx.y is the replica, a lane takes a source row and walks the channels in
+// plain order, evaluating those its replica holds out at that row under that replica's posterior.  Slot (k, n) sums over
+// exactly the rows where replica k holds (row, n) out -- the other lanes add zeros, in the same fixed order -- and
+// rate[row, n] is written by the replica that holds the entry out (the host has checked that there is at most one).
+struct LlMaskArgs {
+    RowModel m;
+    int n_blk, nw;
+    const unsigned long long* mask;  // (n_rep rows, nw)
+    double* rate;                    // (rows, N), filled with NaN beforehand, or null
+    double* part;                    // (n_rep N, n_blk, 4)
+};
+
+__global__ void __launch_bounds__(256) ll_rows_masked(LlMaskArgs A) {
+    __shared__ double red[2][4][4];
+    const RowModel& M = A.m;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in = r < M.rows;
+    const int64_t row = in ? r : 0;
+    const int k = blockIdx.y;
+    const int64_t mrow = (int64_t)k * M.rows + row;  // row of mu, v and of the mask in the replicated set
+    const unsigned long long* mk = A.mask + mrow * A.nw;
+    for (int n = 0; n < M.N; ++n) {
+        const bool out = in && ((mk[n >> 6] >> (n & 63)) & 1ull);
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        if (out) {
+            double eta = row_eta(M, row, mrow, n);
+            const double yv = M.y[row * M.N + n];
+            if (M.gauss[n]) {
+                const double nz = M.noise[n], d = yv - eta;
+                s[0] = -0.5 * log(2.0 * M_PI * nz) - d * d / (2.0 * nz);
+                s[2] = eta;
+                s[3] = yv * yv;
+                if (A.rate) A.rate[row * M.N + n] = eta;
+            } else {
+                eta = row_quad(M, mrow, n, eta);
+                const double lam = exp(clamp10(eta));
+                const double lg = lgamma(yv + 1.0);
+                s[0] = yv * log(lam) - lam - lg;
+                s[2] = lam;
+                s[3] = lg;
+                if (A.rate) A.rate[row * M.N + n] = lam;
+            }
+            s[1] = yv;
+        }
+        block_sums4(s, out, n, red, A.part + (((int64_t)k * M.N + n) * A.n_blk + blockIdx.x) * 4);
+    }
+}
+
 // sums[slot][j] = the slot's partials added in workgroup order
 __global__ void __launch_bounds__(256) ll_finish(int slots, int n_blk, const double* __restrict__ part,
                                                  double* __restrict__ sums) {
@@ -82,8 +130,27 @@ int launch_sums_finish(vlgp_ctx* ctx, int slots, int n_blk, const double* d_part
     return VLGP_OK;
 }
 
+static int launch_loglik_masked(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums) {
+    LlMaskArgs A;
+    A.m = fill_row_model(ctx, ctx->sets[us.rep_src], us, vb);
+    A.n_blk = (int)((A.m.rows + 255) / 256);
+    A.nw = us.rep_nw;
+    A.mask = us.d_rep_mask;
+    A.rate = d_rate;
+    const int64_t slots = (int64_t)us.n_rep * ctx->N;
+    if (A.m.rows < 1 || A.n_blk < 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on an empty set");
+    if (us.n_rep > 65535) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: at most 65535 replicas per masked set");
+    if (slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: too many (replica, channel) slots");
+    CHK(vlgp_ensure_work(ctx, slots * A.n_blk * 4 + 8));
+    A.part = ctx->d_work;
+    hipLaunchKernelGGL(ll_rows_masked, dim3((unsigned)A.n_blk, (unsigned)us.n_rep), dim3(256), 0, ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+    return launch_sums_finish(ctx, (int)slots, A.n_blk, ctx->d_work, d_sums);
+}
+
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums) {
     const bool rep = us.rep_src >= 0;
+    if (rep && us.rep_by_row) return launch_loglik_masked(ctx, us, vb, d_rate, d_sums);
     LlArgs A;
     A.m = fill_row_model(ctx, rep ? ctx->sets[us.rep_src] : us, us, vb);
     A.n_blk = (int)((A.m.rows + 255) / 256);

@@ -48,6 +48,25 @@ def _all_ones(x):
     return bool(np.all(x == 1.0))
 
 
+def pack_mask(mask):
+    """Bool array (..., N) -> uint64 words (..., (N + 63) // 64), bit ``n & 63`` of word ``n >> 6`` for channel ``n``: the
+    layout of vlgp_replicate_masked."""
+    mask = np.asarray(mask, dtype=bool)
+    N = mask.shape[-1]
+    nw = (N + 63) // 64
+    padded = np.zeros(mask.shape[:-1] + (nw * 64,), dtype=np.uint8)
+    padded[..., :N] = mask
+    by = np.packbits(padded, axis=-1, bitorder="little")  # byte j holds channels 8 j ... 8 j + 7, low bit first
+    return np.ascontiguousarray(by).view("<u8").reshape(mask.shape[:-1] + (nw,)).astype(np.uint64, copy=False)
+
+
+def unpack_mask(words, n_channels):
+    """The inverse of ``pack_mask``: uint64 words (..., nw) -> bool (..., n_channels)."""
+    words = np.ascontiguousarray(words, dtype="<u8")
+    bits = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")
+    return bits[..., :int(n_channels)].astype(bool)
+
+
 class Engine:
     """One GPU, one handle (include/vlgp_hip.h)."""
 
@@ -196,23 +215,35 @@ class Engine:
         self.sets.pop(set_id, None)
         self.replicas.pop(set_id, None)
 
-    def replicate(self, src, dst, channels=None, groups=None):
+    def replicate(self, src, dst, channels=None, groups=None, held_out=None):
         """Set ``dst`` := replicas of set ``src``, replica-major units, y / x aliased to ``src``
         (vlgp_replicate_groups).  ``groups``: one replica per list of channels, replica k leaving ``groups[k]`` out of
         its E-step; ``loglik`` then scores one slot per (replica, channel) pair, the groups concatenated in order.
-        ``channels``: one replica per entry -- the singleton groups ``[[c] for c in channels]``."""
-        if (channels is None) == (groups is None):
-            raise ValueError("replicate takes channels or groups")
+        ``channels``: one replica per entry -- the singleton groups ``[[c] for c in channels]``.
+        ``held_out``: a bool array (n_rep, rows, N), replica k leaving the single entries ``held_out[k]`` out
+        (vlgp_replicate_masked); ``loglik`` then scores one slot per (replica, channel)."""
+        if sum(arg is not None for arg in (channels, groups, held_out)) != 1:
+            raise ValueError("replicate takes channels, groups or held_out")
         self.state_epoch += 1
-        if groups is None:
-            groups = np.asarray(channels, dtype=np.int32).reshape(-1, 1)
-        groups = [np.asarray(g, dtype=np.int32).reshape(-1) for g in groups]
-        k = len(groups)
-        start = np.zeros(k + 1, dtype=np.int32)
-        np.cumsum([len(g) for g in groups], out=start[1:])
-        ch = np.ascontiguousarray(np.concatenate(groups) if k else np.zeros(0), dtype=np.int32)
-        self._ck(self.lib.vlgp_replicate_groups(self.h, int(src), int(dst), k, iptr(start), iptr(ch)))
         m, rows, off = self.sets[src]
+        if held_out is not None:
+            held_out = np.asarray(held_out)
+            if held_out.dtype != np.bool_ or held_out.ndim != 3 or held_out.shape[1:] != (rows, self.N):
+                raise ValueError("held_out must be a bool array (n_rep, %d, %d)" % (rows, self.N))
+            k = held_out.shape[0]
+            words = pack_mask(held_out)
+            self._ck(self.lib.vlgp_replicate_masked(self.h, int(src), int(dst), k,
+                                                    words.ctypes.data_as(C.POINTER(C.c_uint64))))
+            ch = None
+        else:
+            if groups is None:
+                groups = np.asarray(channels, dtype=np.int32).reshape(-1, 1)
+            groups = [np.asarray(g, dtype=np.int32).reshape(-1) for g in groups]
+            k = len(groups)
+            start = np.zeros(k + 1, dtype=np.int32)
+            np.cumsum([len(g) for g in groups], out=start[1:])
+            ch = np.ascontiguousarray(np.concatenate(groups) if k else np.zeros(0), dtype=np.int32)
+            self._ck(self.lib.vlgp_replicate_groups(self.h, int(src), int(dst), k, iptr(start), iptr(ch)))
         roff = np.concatenate([r * rows + off[:-1] for r in range(k)] + [np.array([k * rows], dtype=np.int64)])
         self.sets[dst] = (k * m, k * rows, roff)
         self.replicas[dst] = (k, ch)
@@ -220,13 +251,19 @@ class Engine:
     def loglik(self, set_id, vb=True, want_rate=False):
         """Plug-in rates and per-channel log-likelihood sums of a set (vlgp_loglik): ``(sums, rate)``, sums
         (slots, 4) and rate (rows, slots) or None; slots = N for a plain set, the (replica, left-out channel) pairs in
-        the order of the channel list for a replicated one (rows: the source set's)."""
+        the order of the channel list for a replicated one (rows: the source set's).  A set replicated with
+        ``held_out``: sums (n_rep, N, 4) over the entries each replica holds out, rate (rows of the source, N), NaN
+        where no replica holds the entry out."""
         _, rows, _ = self.sets[set_id]
         rep = self.replicas.get(set_id)
-        slots = self.N if rep is None else len(rep[1])
         rows_out = rows if rep is None else rows // max(rep[0], 1)
-        sums = np.empty((slots, 4))
-        rate = np.empty((rows_out, slots)) if want_rate else None
+        if rep is not None and rep[1] is None:
+            sums = np.empty((rep[0], self.N, 4))
+            rate = np.empty((rows_out, self.N)) if want_rate else None
+        else:
+            slots = self.N if rep is None else len(rep[1])
+            sums = np.empty((slots, 4))
+            rate = np.empty((rows_out, slots)) if want_rate else None
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
         return sums, rate
 

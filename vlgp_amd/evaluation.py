@@ -15,6 +15,18 @@ Definitions (the tests hold the code to them).  For channel ``n`` at row ``t`` o
 - leave-group-out (co-smoothing) for a set ``g`` of channels: the same with ``a[:, g] = 0`` -- one inference for the
   whole set -- and every channel of ``g`` predicted from those latents with its original loading.  Singleton groups are
   leave-one-out, bit for bit.
+- leave-entries-out (speckled hold-out) for a set ``S`` of single (row, channel) entries: the E-step with the likelihood
+  terms of the entries of ``S`` removed -- their working residual ``res[t, n]`` and curvature ``U[t, n]`` are 0, and with
+  them their contributions to ``y . a``, to ``w`` and to the Gaussian constant of ``w`` -- from ``mu = v = w = 0``,
+  ``n_iter`` iterations; every entry of ``S`` is then predicted from those latents with its channel's loading.  Nothing
+  else changes: the regressors ``x`` enter as the caller gave them, so with ``history > 0`` they hold the held-out counts
+  of earlier bins, as in leave-one-out.  A set that is constant along the rows is leave-group-out, bit for bit.  A row
+  with every entry held out has ``w = 0``: its latents come from the prior and the neighbouring rows alone.
+- ``entry_folds``: ``np.random.default_rng(seed).permutation(rows * N).reshape(rows, N) % n_folds`` -- every entry in
+  exactly one fold, fold sizes differing by at most one.  ``leave_entries_out`` runs one replica per fold.
+- speckled bits per spike of a Poisson channel: as below, with the sums over the channel's held-out entries (all folds)
+  and ``LL_null`` a constant rate at the channel's mean count over those entries; ``speckled_bps`` pools the channels
+  as ``co_bps`` does.
 - bits per spike of a Poisson channel: ``(LL_model - LL_null) / (sum y * ln 2)``, ``LL_null`` the log-likelihood of a
   constant rate at the channel's mean count over the evaluated rows (the ``lgamma`` terms cancel).  Gaussian channels,
   and channels without a spike, get NaN.
@@ -73,7 +85,8 @@ from ._lib import ERR_STATE, VlgpError
 from .api import _extended, bind_priors
 
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
-           "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction"]
+           "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
+           "entry_scores", "leave_entries_out", "impute"]
 
 SET_TEST, SET_FORWARD, SET_REPLICAS = 0, 1, 2
 
@@ -91,9 +104,14 @@ def plan_chunks(channels, max_replicas):
     return [channels[i:i + step] for i in range(0, len(channels), step)]
 
 
-def default_max_replicas(rows, n_latents, budget=REPLICA_BUDGET_BYTES):
-    """Replicas of a ``rows``-row test set that fit ``budget`` bytes (at least one)."""
-    per = _DOUBLES_PER_ROW_LATENT * 8 * max(int(rows), 1) * max(int(n_latents), 1)
+def default_max_replicas(rows, n_latents, budget=REPLICA_BUDGET_BYTES, mask_channels=0, gauss=False):
+    """Replicas of a ``rows``-row test set that fit ``budget`` bytes (at least one).  ``mask_channels``: the channel count
+    of a replica with per-entry masks (``Engine.replicate(held_out=...)``), which adds one 64-bit word per row and 64
+    channels and, with a Gaussian channel (``gauss``), the per-row constant of ``w``: one double per (row, latent)."""
+    rows, n_latents = max(int(rows), 1), max(int(n_latents), 1)
+    per = _DOUBLES_PER_ROW_LATENT * 8 * rows * n_latents
+    if mask_channels:
+        per += 8 * rows * ((int(mask_channels) + 63) // 64) + (8 * rows * n_latents if gauss else 0)
     return max(int(budget // per), 1)
 
 
@@ -364,6 +382,152 @@ def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_it
     out.update(groups=groups, group_of=[k for k, g in enumerate(groups) for _ in g],
                co_bps=co_bits_per_spike(out["ll"], out["ll_null"], out["n_spikes"]))
     return out
+
+
+def entry_folds(rows, n_channels, n_folds, seed=0):
+    """A (rows, n_channels) integer array of fold indices, every entry in exactly one fold and fold sizes differing by
+    at most one: ``np.random.default_rng(seed).permutation(rows * n_channels).reshape(rows, n_channels) % n_folds``.  A
+    deterministic function of its arguments."""
+    rows, n_channels, n_folds = int(rows), int(n_channels), int(n_folds)
+    if rows < 1 or n_channels < 1 or not 1 <= n_folds <= rows * n_channels:
+        raise ValueError("need rows, n_channels >= 1 and 1 <= n_folds <= rows * n_channels, got %d folds for %d x %d entries"
+                         % (n_folds, rows, n_channels))
+    return np.random.default_rng(seed).permutation(rows * n_channels).reshape(rows, n_channels) % n_folds
+
+
+def entry_scores(sums, n_entries, gauss=None):
+    """Scores of a speckled hold-out from the masked ``vlgp_loglik`` sums (pure host code).  ``sums`` (n_folds, N, 4):
+    per (fold, channel) ``sum ll, sum y, sum rate, sum lgamma(y + 1)`` over the entries that fold holds out;
+    ``n_entries`` (N): held-out entries per channel, all folds.  Returns a dict: per channel ``ll``, ``ll_null`` (a
+    constant rate at the channel's mean count over its held-out entries), ``n_spikes``, ``n_entries``,
+    ``bits_per_spike`` (NaN for Gaussian channels and channels without a held-out spike); ``ll_per_fold`` (n_folds, N);
+    ``speckled_bps``, pooled by ``co_bits_per_spike``'s rule.  The folds are added in fold order."""
+    sums = np.asarray(sums, dtype=float)
+    if sums.ndim != 3 or sums.shape[2] != 4:
+        raise ValueError("sums must be (n_folds, N, 4)")
+    n_entries = np.asarray(n_entries, dtype=float)
+    if n_entries.shape != (sums.shape[1],):
+        raise ValueError("n_entries must hold one count per channel")
+    gauss = np.zeros(sums.shape[1], dtype=bool) if gauss is None else np.asarray(gauss, dtype=bool)
+    tot = np.zeros(sums.shape[1:])
+    for k in range(sums.shape[0]):
+        tot += sums[k]
+    ll, ny, lg = tot[:, 0], tot[:, 1], tot[:, 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ybar = np.where(n_entries > 0, ny / np.where(n_entries > 0, n_entries, 1.0), 0.0)
+        ll_null = np.where(ny > 0, ny * np.log(np.where(ny > 0, ybar, 1.0)), 0.0) - n_entries * ybar - lg
+        bps = (ll - ll_null) / (ny * math.log(2.0))
+    bps = np.where(gauss | ~(ny > 0), np.nan, bps)
+    ll_null = np.where(gauss, np.nan, ll_null)
+    return {"ll": ll, "ll_null": ll_null, "n_spikes": ny, "n_entries": n_entries.astype(np.int64),
+            "bits_per_spike": bps, "ll_per_fold": sums[:, :, 0].copy(),
+            "speckled_bps": co_bits_per_spike(ll, ll_null, ny)}
+
+
+def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device, posterior=False):
+    """One replica per mask of ``held_out`` (bool (n_rep, rows, N)) from a zero start, ``max_replicas`` at a time:
+    ``(sums (n_rep, N, 4), rate (rows, N), n_failed, posterior)``, the posterior (mu, v, w of every replica, (n_rep, rows,
+    L) each) only on request.  The masks of one call are pairwise disjoint, so the rate of every entry has one source."""
+    L = int(params["zdim"])
+    n_iter = int(config["max_iter"] if n_iter is None else n_iter)
+    vb = config["method"] == "VB"
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    rows, N = int(sum(lengths)), int(params["ydim"])
+    units = [{"y": tr["y"], "x": tr.get("x"), "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))}
+             for tr, T in zip(trials, lengths)]
+    n_rep = held_out.shape[0]
+    sums = np.empty((n_rep, N, 4))
+    rate = np.full((rows, N), np.nan)
+    post = {k: np.empty((n_rep, rows, L)) for k in ("mu", "v", "w")} if posterior else None
+    n_failed = 0
+    with _resident(trials, params, units, device) as eng:
+        cap = max_replicas
+        if cap is None:
+            cap = default_max_replicas(rows, L, mask_channels=N, gauss=bool(eng.gauss.any()))
+        cap = max(int(cap), 1)
+        for k0 in range(0, n_rep, cap):
+            chunk = held_out[k0:k0 + cap]
+            eng.replicate(SET_TEST, SET_REPLICAS, held_out=chunk)
+            n_failed += eng.estep(SET_REPLICAS, n_iter, config["dmu_bound"], vb)
+            s, r = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
+            if posterior:
+                got = eng.download(SET_REPLICAS, ("mu", "v", "w"))
+                for key in post:
+                    post[key][k0:k0 + len(chunk)] = got[key].reshape(len(chunk), rows, L)
+            eng.free_units(SET_REPLICAS)
+            sums[k0:k0 + len(chunk)] = s
+            mine = chunk.any(axis=0)
+            rate[mine] = r[mine]
+        gauss = eng.gauss.copy()
+    return sums, rate, int(n_failed), post, gauss
+
+
+def _per_trial_entries(arrays, trials, what, dtype):
+    N = int(trials[0]["y"].shape[1])
+    if len(arrays) != len(trials):
+        raise ValueError("%s needs one array per trial" % what)
+    out = []
+    for arr, tr in zip(arrays, trials):
+        arr = np.asarray(arr)
+        if arr.shape != (tr["y"].shape[0], N) or not (arr.dtype == np.bool_ if dtype is bool
+                                                      else np.issubdtype(arr.dtype, np.integer)):
+            raise ValueError("%s: every trial needs a (T, %d) %s array" % (what, N, "bool" if dtype is bool else "integer"))
+        out.append(arr)
+    return out
+
+
+def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_iter=None, max_replicas=None, device=0):
+    """Speckled hold-out on held-out trials: single (row, channel) entries left out of the inference and predicted
+    (module docstring for the definitions).
+
+    ``trials``: as ``leave_group_out``.  ``folds``: a list per trial of (T, N) integer arrays, the fold every entry is
+    held out in, ``-1`` for an entry that is never held out; the folds run from 0 to the largest index given
+    (``n_folds`` and ``seed`` are then not read).  Default: ``entry_folds`` over the concatenated rows, cut per trial.
+    One replica of the test set per fold (``vlgp_replicate_masked``) from a zero start, ``n_iter`` E-step iterations
+    (default ``config["max_iter"]``), ``max_replicas`` at a time (default: what ``REPLICA_BUDGET_BYTES`` holds; the
+    chunking changes no bit).  There is no sequential path: a configuration the split E-step refuses (e.g. L > 10)
+    raises ``VlgpError`` with the device's reason.
+
+    Returns a dict: ``folds``; ``rate``, per trial (T, N), NaN where never held out (Gaussian: means); per channel
+    ``ll``, ``ll_null``, ``n_spikes``, ``n_entries``, ``bits_per_spike``; ``ll_per_fold`` (n_folds, N);
+    ``speckled_bps``; ``n_failed``."""
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    rows, N = int(sum(lengths)), int(params["ydim"])
+    bounds = np.cumsum([0] + lengths)
+    if folds is None:
+        F = entry_folds(rows, N, n_folds, seed)
+        n_folds = int(n_folds)
+    else:
+        F = np.concatenate(_per_trial_entries(folds, trials, "folds", int), axis=0)
+        if F.min() < -1:
+            raise ValueError("fold indices are >= 0, or -1 for an entry that is never held out")
+        n_folds = int(F.max()) + 1
+        if n_folds < 1:
+            raise ValueError("folds hold no entry out")
+    held = np.stack([F == k for k in range(n_folds)])
+    sums, rate, n_failed, _, gauss = _entries_out(trials, params, config, held, n_iter, max_replicas, device)
+    out = entry_scores(sums, (F >= 0).sum(axis=0), gauss)
+    out.update(folds=[F[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))],
+               rate=[rate[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))], n_failed=n_failed)
+    return out
+
+
+def impute(trials, params, config, missing, n_iter=None, device=0):
+    """Inference on trials with holes: ``missing`` is a list per trial of (T, N) bool arrays, True where the
+    observation is absent (an artifact-blanked bin, a channel dead for part of a trial; the value stored in ``y``
+    there is not read by the inference).  One E-step from a zero start with those entries' likelihood terms removed
+    (module docstring: leave-entries-out with the one fold ``missing``), ``n_iter`` iterations (default
+    ``config["max_iter"]``).
+
+    Returns a dict of per-trial lists: ``mu``, ``v``, ``w`` (T, L) and ``rate`` (T, N), the model's prediction at the
+    missing entries (Gaussian: means) and NaN elsewhere; and ``n_failed``."""
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    bounds = np.cumsum([0] + lengths)
+    held = np.concatenate(_per_trial_entries(missing, trials, "missing", bool), axis=0)[None]
+    _, rate, n_failed, post, _ = _entries_out(trials, params, config, held, n_iter, 1, device, posterior=True)
+    cut = lambda arr: [arr[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))]  # noqa: E731
+    return {"mu": cut(post["mu"][0]), "v": cut(post["v"][0]), "w": cut(post["w"][0]), "rate": cut(rate),
+            "n_failed": n_failed}
 
 
 def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0):

@@ -4,11 +4,15 @@
 held-out trials with ``evaluation.leave_group_out``: the latents of a test trial are inferred from all channels but a
 fold, that fold is predicted, and the prediction is scored in bits per spike.  Trial folds and channel folds are drawn
 once and shared by every candidate, so the candidates are compared on paired folds.  One process, one GPU.
+
+With ``score="speckled_bps"`` the held-out trials are scored by ``evaluation.leave_entries_out`` instead: folds of single
+(bin, channel) entries are left out of the inference and predicted (the reference's ``gmap_speckled_cv`` scheme).  The fit
+itself sees whole training trials, never a mask: the trials are held out, the speckle is applied to the test trials.
 """
 import numpy as np
 
 from .api import fit
-from .evaluation import channel_folds, leave_group_out
+from .evaluation import channel_folds, leave_entries_out, leave_group_out
 
 __all__ = ["cross_validate", "trial_folds"]
 
@@ -57,7 +61,7 @@ def best_candidate(n_factors_list, mean_co_bps):
 
 
 def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, seed=0, n_iter=None, device=0,
-                   **fit_kwargs):
+                   score="co_bps", **fit_kwargs):
     """Score every ``n_factors`` of ``n_factors_list`` by co-smoothing bits per spike on held-out trials.
 
     For every trial fold and candidate: ``fit`` on fresh copies of the other trials (``fit_kwargs`` are ``fit``'s),
@@ -70,7 +74,14 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
     Returns a dict: ``n_factors``; ``trial_folds`` (test-trial indices per fold); ``channel_folds``; ``co_bps``
     (candidates, trial folds); ``bits_per_spike`` (candidates, trial folds, N), per channel in plain order;
     ``n_failed`` (candidates, trial folds); ``mean_co_bps`` (candidates); ``best``; ``errors``, a list of
-    ``(n_factors, fold, text)``."""
+    ``(n_factors, fold, text)``.
+
+    ``score="speckled_bps"`` scores every trial fold with ``leave_entries_out(n_folds=n_channel_folds, seed=seed)``
+    instead (the entry folds depend on the fold's row count alone, so the candidates still share them).  The dict then
+    holds ``speckled_bps`` and ``mean_speckled_bps`` where the default has ``co_bps`` and ``mean_co_bps``, ``score``, and
+    no ``channel_folds``; ``best`` follows ``mean_speckled_bps``."""
+    if score not in ("co_bps", "speckled_bps"):
+        raise ValueError("score must be 'co_bps' or 'speckled_bps', got %r" % (score,))
     if "comm" in fit_kwargs:
         raise ValueError("cross_validate runs on one process: it takes no comm")
     n_factors_list = [int(n) for n in n_factors_list]
@@ -78,8 +89,9 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
         raise ValueError("n_factors_list must hold positive integers")
     N = int(trials[0]["y"].shape[1])
     t_folds = trial_folds(len(trials), n_trial_folds, seed)
-    c_folds = channel_folds(N, n_channel_folds, seed)
-    order = np.argsort([c for g in c_folds for c in g])  # channel-list order -> plain channel order
+    speckled = score == "speckled_bps"
+    c_folds = None if speckled else channel_folds(N, n_channel_folds, seed)
+    order = np.arange(N) if speckled else np.argsort([c for g in c_folds for c in g])  # channel-list -> plain order
     shape = (len(n_factors_list), len(t_folds))
     co_bps = np.full(shape, np.nan)
     bps = np.full(shape + (N,), np.nan)
@@ -91,15 +103,23 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
         for c, n in enumerate(n_factors_list):
             try:
                 fitted = _seeded_fit(seed, _fresh(trials, train_idx), n, device=device, verbose=False, **fit_kwargs)
-                got = leave_group_out(_fresh(trials, test_idx), fitted["params"], fitted["config"], groups=c_folds,
-                                      n_iter=n_iter, device=device)
+                if speckled:
+                    got = leave_entries_out(_fresh(trials, test_idx), fitted["params"], fitted["config"],
+                                            n_folds=n_channel_folds, seed=seed, n_iter=n_iter, device=device)
+                else:
+                    got = leave_group_out(_fresh(trials, test_idx), fitted["params"], fitted["config"], groups=c_folds,
+                                          n_iter=n_iter, device=device)
             except Exception as err:  # (the sweep goes on: one candidate's failure is a result, not the end)
                 errors.append((n, f, "%s: %s" % (type(err).__name__, err)))
                 continue
-            co_bps[c, f] = got["co_bps"]
+            co_bps[c, f] = got[score]
             bps[c, f] = got["bits_per_spike"][order]
             n_failed[c, f] = got["n_failed"]
     mean = np.array([np.mean(row) for row in co_bps])  # (NaN as soon as one fold of the candidate failed)
+    if speckled:
+        return {"n_factors": n_factors_list, "trial_folds": t_folds, "score": score, "speckled_bps": co_bps,
+                "bits_per_spike": bps, "n_failed": n_failed, "mean_speckled_bps": mean,
+                "best": best_candidate(n_factors_list, mean), "errors": errors}
     return {"n_factors": n_factors_list, "trial_folds": t_folds, "channel_folds": c_folds, "co_bps": co_bps,
             "bits_per_spike": bps, "n_failed": n_failed, "mean_co_bps": mean,
             "best": best_candidate(n_factors_list, mean), "errors": errors}
