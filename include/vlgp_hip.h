@@ -137,7 +137,22 @@ int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* 
  * vlgp_loglik on such a set: sums (n_rep, N, 4), slot (k, n) holding the four sums of channel n over exactly the rows where
  * replica k holds (row, n) out (an empty slot: four zeros); rate (rows_src, N) or NULL, NaN where no replica holds the
  * entry out, else written from the replica that does -- asking for rate when two replicas hold the same entry out is
- * VLGP_ERR_ARG (decided when the set is made).  At most 65535 replicas. */
+ * VLGP_ERR_ARG (decided when the set is made).  At most 65535 replicas.
+ *
+ * ONE replica (n_rep == 1) makes a masked fit set: the rows and units of `src`, a set bit meaning "this entry of y is
+ * missing".  Besides the entry points above it takes the ones a fit runs: vlgp_update_w and vlgp_update_v (w of a row
+ * sums over its observed channels, through the split E-step's by-row passes), vlgp_norms, vlgp_norms_begin,
+ * vlgp_norms_end, vlgp_apply_latent_map, vlgp_latent_moments, vlgp_hstep_prepare, vlgp_hstep_begin,
+ * vlgp_hstep_objective, vlgp_hstep_end (all of them read mu, v, w, dmu alone) and vlgp_mstep, vlgp_mstep_begin,
+ * vlgp_mstep_end: the M-step of every channel over its observed rows only -- mu'y, x'y, every gradient and Hessian sum
+ * and the noise variance (mean and variance over the channel's own observed rows; the number of observed rows per
+ * channel is counted when the set is made).  What y holds at a missing entry, NaN included, reaches no sum; with no bit
+ * set a, b, da, db are those of `src`, bit for bit, and noise is that of its two-pass form.  A channel with no observed
+ * row keeps a, b, noise and is not counted in *n_failed.  The masked M-step is VLGP_ERR_STATE, the message naming the
+ * reason, with a Gaussian channel on the handle, on the loop-based kernels (P > 8, VLGP_MSTEP_GENERIC), beyond 10
+ * latents and with more than one rank.  vlgp_elbo, vlgp_forecast, vlgp_project_units, cuts, merges, stashes and
+ * overlaps refuse a masked fit set like every replicated set; a group-replica set and a masked set of several
+ * replicas are refused by all of the above exactly as before. */
 int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint64_t* held_out);
 /* Plug-in rate and log-likelihood of the observations under the set's current posterior (mu, v):
  *   Poisson   rate = trunc_exp(a_n.mu_t + (b x)_tn + 1/2 (a_n^2).v_t)  (the E-step's rate; vb == 0 drops the v term)
@@ -204,7 +219,7 @@ int vlgp_clear_prior(vlgp_ctx* ctx);
 int vlgp_get_prior(vlgp_ctx* ctx, int T, double* G, int* rank_out);
 
 /* ---- E-step ----------------------------------------------------------- */
-/* core.update_w (vlgp/core.py:419-442) */
+/* core.update_w (vlgp/core.py:419-442).  This and vlgp_update_v take a masked fit set (vlgp_replicate_masked). */
 int vlgp_update_w(vlgp_ctx* ctx, int set);
 /* core.update_v (vlgp/core.py:445-471); vb == 0 is the reference's early
  * return for method != "VB". */
@@ -220,7 +235,8 @@ int vlgp_estep_wait(vlgp_ctx* ctx);
 /* ---- M-step ----------------------------------------------------------- */
 /* core.mstep (vlgp/core.py:129-249) over the concatenation of all units of
  * the set.  With a communicator attached the sufficient statistics are
- * all-reduced over ranks once per Newton iteration. */
+ * all-reduced over ranks once per Newton iteration.  A masked fit set (vlgp_replicate_masked, one replica): every
+ * channel over its observed rows only; see there for its limits.  Other replicated sets: VLGP_ERR_STATE. */
 int vlgp_mstep(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, double eps,
                double learning_rate, double da_bound, double db_bound, int* n_failed);
 
@@ -252,7 +268,8 @@ int vlgp_hstep_objective(vlgp_ctx* ctx, int set, int window, double dt, int n_ev
  * sum_i mu_i mu_i' that the quadratic terms of every evaluation share are then built
  * once (by the first objective call) instead of on every call.  The caller must not
  * modify the set between begin and end.  Optional: without it every
- * vlgp_hstep_objective call is self-contained. */
+ * vlgp_hstep_objective call is self-contained.  The H-step reads mu and w alone: all four calls take a masked fit set
+ * (vlgp_replicate_masked) as any set. */
 int vlgp_hstep_begin(vlgp_ctx* ctx, int set, int window);
 int vlgp_hstep_end(vlgp_ctx* ctx);
 /* Optional, before vlgp_hstep_begin: enqueue what the bracket builds from the units alone (those second moments and
@@ -265,7 +282,8 @@ int vlgp_hstep_prepare(vlgp_ctx* ctx, int set, int window);
 /* ---- constraints / norms --------------------------------------------- */
 /* mu <- (mu - shift) @ map for every unit (map (L, L) row-major, shift (L) or
  * NULL).  Covers core.constrain_loading (vlgp/core.py:392-416: map = s I, or
- * the SVD factor) and core.constrain_latent (vlgp/core.py:366-389). */
+ * the SVD factor) and core.constrain_latent (vlgp/core.py:366-389).  This, the norms and vlgp_latent_moments below
+ * read mu, v, dmu alone and take a masked fit set (vlgp_replicate_masked). */
 int vlgp_apply_latent_map(vlgp_ctx* ctx, int set, const double* map, const double* shift);
 /* out[0] = sum mu^2, out[1] = sum dmu^2 over the set (and over ranks):
  * the convergence test of core.vem (vlgp/core.py:300-305,350-354). */

@@ -20,6 +20,8 @@ __all__ = ["fit", "transform", "forecast", "FitSession", "bind_priors"]
 logger = logging.getLogger(__name__)
 
 SET_TRIALS, SET_SEGMENTS = 0, 1
+# a fit with missing observations works on masked fit sets (one-replica vlgp_replicate_masked) of the two above
+SET_TRIALS_MASKED, SET_SEGMENTS_MASKED = 2, 3
 
 
 def _echo(msg):
@@ -88,9 +90,13 @@ class FitSession:
     ``fit`` is ``FitSession(...).run().finish()``.
     """
 
-    def __init__(self, trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, **kwargs):
+    def __init__(self, trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, missing=None, **kwargs):
         self.echo = _echo if verbose else None
         self.track_elbo = bool(track_elbo)
+        self.missing = None
+        if missing is not None:
+            self._init_masked(trials, n_factors, device, comm, missing, kwargs)
+            return
         echo = self.echo
         self.trials = trials
         self.config = config = get_config(**kwargs)
@@ -158,6 +164,144 @@ class FitSession:
             self.close()
             raise
 
+    def _init_masked(self, trials, n_factors, device, comm, missing, kwargs):
+        """The same phases for trials with missing observations (``fit``'s ``missing``): the initialisation on private
+        copies of y with the holes filled by the channel's observed mean, then everything on masked fit sets."""
+        from .evaluation import _per_trial_entries
+
+        echo = self.echo
+        lik = kwargs.get("lik", "poisson")
+        if any(k == "gaussian" for k in (lik if isinstance(lik, list) else [lik])):
+            raise ValueError("fit(missing=...) takes Poisson channels only: a Gaussian channel's update needs "
+                             "per-channel masked Gram matrices")
+        if kwargs.get("history", 0) > 0:
+            raise ValueError("fit(missing=...) takes no history: the regressors would be built from missing counts")
+        if comm is not None and comm.world > 1:
+            raise ValueError("fit(missing=...) runs on one rank: it takes no comm with world > 1")
+        if self.track_elbo:
+            raise ValueError("fit(missing=...) takes no track_elbo: the bound of a masked set is not computed")
+        self.trials = trials
+        self.config = config = get_config(**kwargs)
+        if config["constrain_loading"] == "svd":
+            raise ValueError("fit(missing=...) takes no constrain_loading='svd': it rests on segments being views of trials")
+        missing = [np.array(m, dtype=bool) for m in _per_trial_entries(missing, trials, "missing", bool)]
+        window = config["window"]
+        if window and any(tr["y"].shape[0] % window for tr in trials):
+            raise ValueError("fit(missing=...) needs trial lengths that are multiples of window=%d: overlapping "
+                             "segments share rows, which a masked set cannot" % window)
+        n_obs = sum((~m).sum(axis=0) for m in missing)
+        if np.any(n_obs == 0):
+            raise ValueError("channel(s) %s have no observed entry" % np.flatnonzero(n_obs == 0).tolist())
+        # private copies of y, the holes filled with the channel's mean over its observed entries: the initialisation
+        # (factor analysis, initial latents, b = log mean y) works on them, and they are what the device holds -- the
+        # masked row passes of the E-step leave an entry out by a zero coefficient, under which a NaN in the caller's y
+        # would survive.  The fill value reaches no result after the initialisation; the caller's values at missing entries
+        # are never read.
+        y_sum = sum(np.where(m, 0.0, tr["y"]).sum(axis=0) for tr, m in zip(trials, missing))
+        y_mean = y_sum / n_obs
+        work = [dict(tr, y=np.where(m, y_mean[None, :], tr["y"]).astype(float)) for tr, m in zip(trials, missing)]
+        logger.info("\n".join("{} : {}".format(k, v) for k, v in config.items()))
+        kwargs["omega_bound"] = config["omega_bound"]
+        self.params = params = get_params(trials, n_factors, **kwargs)
+        self.comm = comm
+        self.eng = None
+        self.runtime = E.new_runtime()
+        self.materialize_x = bool(kwargs.get("materialize_x", True))
+        self.missing = missing
+
+        if echo:
+            echo("Initializing")
+        eng = E.Engine.for_params(params, device)
+        self.eng = eng
+        try:
+            initialize(work, params, config)
+            fill_trials(work)
+            for tr, wk in zip(trials, work):  # the caller's dicts get what initialize leaves; their y stays theirs
+                tr.update({k: v for k, v in wk.items() if k != "y"})
+            if echo:
+                echo("Initialized")
+            fill_params(params)
+            for key in ("a", "b", "noise", "omega", "sigma"):
+                params[key] = np.array(params[key], dtype=float)
+            eng.set_params(params["a"], params["b"], params["noise"])
+            self._y_dev = [wk["y"] for wk in work]
+            eng.upload(SET_TRIALS, [dict(tr, y=yd) for tr, yd in zip(trials, self._y_dev)])
+            self._mask_rows = np.concatenate(missing, axis=0)
+            eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=self._mask_rows[None])
+            self.dev_trials = E.DeviceTrials(trials, eng, SET_TRIALS_MASKED)
+            E.make_cholesky(self.dev_trials, params, config)
+            E.update_w(self.dev_trials, params, config)
+            E.update_v(self.dev_trials, params, config)
+            if window:
+                # the segments as a plain set of their own (a host cut: y, x, mu, v, w), and its masked fit set.  Trial
+                # lengths are multiples of the window: the segments' rows, in order, are the trials' rows.
+                self.dev_trials.pull(("mu", "v", "w"))
+                segs = []
+                for tr, yd in zip(trials, self._y_dev):
+                    for s0 in range(0, tr["y"].shape[0], window):
+                        segs.append({k: (yd if k == "y" else tr[k])[s0:s0 + window] for k in ("y", "x", "mu", "w", "v")})
+                block = np.zeros((len(segs), window, params["zdim"]))
+                for i, sg in enumerate(segs):
+                    sg["dmu"] = block[i]
+                eng.upload(SET_SEGMENTS, segs)
+                eng.replicate(SET_SEGMENTS, SET_SEGMENTS_MASKED, held_out=self._mask_rows[None])
+                self.segs = E.DeviceTrials(segs, eng, SET_SEGMENTS_MASKED)
+                E.make_cholesky(self.segs, params, config)
+                fill_trials(self.segs)
+            else:
+                self.segs = self.dev_trials
+            snapshot = {k: v for k, v in params.items() if k != "cholesky"}
+            chol = params["cholesky"]
+            if isinstance(chol, E._LazyPrior):
+                chol = chol.materialize() if window else E._InitialPrior(chol._lengths, params["omega"], params["sigma"],
+                                                                         params["rank"])
+            snapshot["cholesky"] = chol
+            params["initial"] = copy.deepcopy(snapshot)
+            E._push_params(eng, params)
+        except Exception:
+            self.close()
+            raise
+
+    def _finish_masked(self):
+        eng, params, config, echo = self.eng, self.params, self.config, self.echo
+        try:
+            if self.segs is not self.dev_trials:
+                # the segments' posterior back into the trials (same rows, same order), then the trials' masked fit
+                # set again from it
+                got = eng.download(SET_SEGMENTS_MASKED, ("mu", "v", "w"))
+                row = 0
+                for tr in self.trials:
+                    T = tr["y"].shape[0]
+                    for k in ("mu", "v"):
+                        tr[k][...] = got[k][row:row + T]
+                    tr["w"] = got["w"][row:row + T].copy()
+                    row += T
+                eng.free_units(SET_SEGMENTS_MASKED)
+                eng.free_units(SET_TRIALS_MASKED)
+                eng.upload(SET_TRIALS, [dict(tr, y=yd) for tr, yd in zip(self.trials, self._y_dev)])
+                eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=self._mask_rows[None])
+                self.dev_trials = E.DeviceTrials(self.trials, eng, SET_TRIALS_MASKED)
+            E.make_cholesky(self.dev_trials, params, config)
+            E.update_w(self.dev_trials, params, config)
+            E.update_v(self.dev_trials, params, config)
+            if echo:
+                echo("Inferring")
+            E.infer(self.dev_trials, params, config, echo=echo)
+            self.dev_trials.pull()
+            for tr, m in zip(self.trials, self.missing):
+                tr["missing"] = m
+                x = tr.get("x")
+                if self.materialize_x and isinstance(x, np.ndarray) and not x.flags.writeable and x.size and \
+                        all(st == 0 for st in x.strides):
+                    tr["x"] = np.ones(x.shape)
+            if isinstance(params["cholesky"], E._LazyPrior):
+                params["cholesky"] = params["cholesky"].materialize()
+            if echo:
+                echo("Done")
+        finally:
+            self.close()
+        return {"trials": self.trials, "params": params, "config": config}
+
     def _replicate_params(self):
         """Every rank must start from the same a, b, noise: keep rank 0's."""
         p, eng = self.params, self.eng
@@ -183,6 +327,8 @@ class FitSession:
         return self
 
     def finish(self):
+        if self.missing is not None:
+            return self._finish_masked()
         eng, params, config, echo = self.eng, self.params, self.config, self.echo
         try:
             if self.segs is not self.dev_trials:
@@ -221,7 +367,7 @@ class FitSession:
             self.eng = None
 
 
-def fit(trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, **kwargs):
+def fit(trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, missing=None, **kwargs):
     """Variational-EM fit of vLGP on one MI355X (or one rank of several).
 
     Same arguments as the reference: ``lik``, ``history``, ``a``, ``b``,
@@ -236,10 +382,18 @@ def fit(trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, 
     gets the variational lower bound after every E-step, ``"elbo_ell"`` / ``"elbo_kl"`` its two parts, and
     ``"elbo_final"`` the bound of the full-length trials after the final inference; all summed over the ranks.  The
     per-iteration trace is the objective of the SEGMENT set the EM loop works on -- segments of a trial whose length
-    is not a multiple of the window overlap -- not of the trials; see ``vlgp_amd.evaluation.elbo``).
+    is not a multiple of the window overlap -- not of the trials; see ``vlgp_amd.evaluation.elbo``),
+    ``missing`` (default None: today's fit.  A list per trial of (T, N) bool arrays, True where the observation is
+    absent, as ``evaluation.impute`` takes it: those entries' likelihood terms are left out of the E-step, the M-step and
+    the initialisation, and what ``y`` holds there is never read.  Poisson channels, no ``history``, one rank, no
+    ``track_elbo``, no ``constrain_loading="svd"``, trial lengths multiples of ``window``; each is a ``ValueError``
+    otherwise.  Every returned trial carries its ``missing`` array.  INTEGRATION.md, "Fit with missing observations").
     """
+    if missing is None:
+        return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, track_elbo=track_elbo,
+                          **kwargs).run().finish()
     return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, track_elbo=track_elbo,
-                      **kwargs).run().finish()
+                      missing=missing, **kwargs).run().finish()
 
 
 def bind_priors(eng, trials, params):

@@ -131,6 +131,15 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
             return vlgp_fail(ctx, VLGP_ERR_STATE, "%s refuses a replicated set (leave-one-out replicas of set %d: "    \
                              "E-step, download, loglik and free only)", what, (us)->rep_src);                        \
     } while (0)
+// ... but a MASKED FIT SET -- vlgp_replicate_masked with one replica: the source's rows, units and y / x, its own mu, v, w,
+// dmu, one mask bit per entry of y -- is a set the fit runs on.  The entry points that read mu, v, w, dmu alone (norms,
+// latent map, moments, H-step) take it as any set; update_w / update_v go through the split E-step's masked row passes;
+// the M-step has masked kernels (mstep.hip).  Group replicas and masked sets of several replicas stay refused as above.
+static inline bool masked_fit_set(const UnitSet* us) { return us->rep_src >= 0 && us->rep_by_row && us->n_rep == 1; }
+#define NOT_REPLICATED_BUT_FIT(ctx, us, what)                \
+    do {                                                     \
+        if (!masked_fit_set(us)) NOT_REPLICATED(ctx, us, what); \
+    } while (0)
 
 // ---- profiling -----------------------------------------------------------
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st) {
@@ -498,7 +507,7 @@ static void free_set(vlgp_ctx* ctx, UnitSet& us) {
     (void)hipStreamSynchronize(ctx->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     if (us.rep_src >= 0) {  // replicas: y, x, xb are the source's
-        fr(us.mu); fr(us.v); fr(us.w); fr(us.d_rep_ch); fr(us.d_rep_pair); fr(us.d_rep_mask); fr(us.d_rep_wconst);
+        fr(us.mu); fr(us.v); fr(us.w); fr(us.d_rep_ch); fr(us.d_rep_pair); fr(us.d_rep_mask); fr(us.d_rep_wconst); fr(us.d_rep_nobs);
         fr(us.d_rep_xa);
         ctx->sets[us.rep_src].rep_users--;
         us.d_xb = nullptr;
@@ -952,6 +961,15 @@ extern "C" int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep,
     HIPCHK(ctx, hipMalloc(&d->d_rep_mask, sizeof(uint64_t) * words));
     if (ctx->n_gauss > 0) HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * (size_t)n_rep * rs * ctx->L));
     HIPCHK(ctx, hipMemcpyAsync(d->d_rep_mask, held_out, sizeof(uint64_t) * words, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<double> nobs;  // one replica: a masked fit set, whose M-step divides by the observed rows of each channel
+    if (n_rep == 1) {
+        nobs.assign((size_t)N, (double)rs);
+        for (int64_t r = 0; r < rs; ++r)
+            for (int n = 0; n < N; ++n)
+                if ((held_out[(size_t)r * nw + (n >> 6)] >> (n & 63)) & 1ull) nobs[n] -= 1.0;
+        HIPCHK(ctx, hipMalloc(&d->d_rep_nobs, sizeof(double) * (size_t)N));
+        HIPCHK(ctx, hipMemcpyAsync(d->d_rep_nobs, nobs.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the mask is the caller's again)
     return VLGP_OK;
 }
@@ -1382,7 +1400,7 @@ extern "C" int vlgp_update_w(vlgp_ctx* ctx, int set) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_update_w");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_update_w");
     return launch_estep(ctx, *us, EM_W, 0, 0.0, 0);
 }
 
@@ -1394,7 +1412,7 @@ extern "C" int vlgp_update_v(vlgp_ctx* ctx, int set, int vb, int* n_failed) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_update_v");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_update_v");
     if (n_failed) *n_failed = 0;
     if (!vb) return VLGP_OK;
     CHK(begin_count(ctx));
@@ -1522,7 +1540,7 @@ extern "C" int vlgp_mstep_begin(vlgp_ctx* ctx, int set, int n_iter, int use_hess
     if (ctx->m_pending) return vlgp_fail(ctx, VLGP_ERR_STATE, "an M-step is already in flight (call vlgp_mstep_end)");
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_mstep_begin");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_mstep_begin");
     if (!(da_bound > 0) || !(db_bound > 0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "da_bound/db_bound must be positive");
     // fork: the M-step lane starts after everything already queued on the main stream
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -1586,7 +1604,7 @@ extern "C" int vlgp_hstep_objective(vlgp_ctx* ctx, int set, int window, double d
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_hstep_objective");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_hstep_objective");
     if (n_eval < 1 || !latent || !logp || !ll || !dll) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad hstep arguments");
     return launch_hstep(ctx, *us, window, dt, n_eval, latent, logp, ll, dll);
 }
@@ -1596,7 +1614,7 @@ extern "C" int vlgp_hstep_prepare(vlgp_ctx* ctx, int set, int window) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_hstep_prepare");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_hstep_prepare");
     ctx->hprep = false;
     if (ctx->hmom_bracket || window < 1) return VLGP_OK;
     // On the MAIN stream, behind everything queued so far -- the call may come while the E-step still runs (the host
@@ -1613,7 +1631,7 @@ extern "C" int vlgp_hstep_begin(vlgp_ctx* ctx, int set, int window) {
     NEED_CTX(ctx);
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_hstep_begin");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_hstep_begin");
     ctx->hmom_bracket = true;
     // the first objective call inside the bracket builds the moments and the w copy -- unless vlgp_hstep_prepare did,
     // for this set and window, and no entry point that may change the units ran since
@@ -1646,7 +1664,7 @@ extern "C" int vlgp_apply_latent_map(vlgp_ctx* ctx, int set, const double* map, 
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us || !map) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad latent map arguments");
-    NOT_REPLICATED(ctx, us, "vlgp_apply_latent_map");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_apply_latent_map");
     const int L = ctx->L;
     // staged through a pinned and a device buffer of its own, reused after the event behind the last kernel that read
     // them: nothing waits here (this is the first call of every EM iteration, constrain_loading)
@@ -1688,7 +1706,7 @@ extern "C" int vlgp_norms(vlgp_ctx* ctx, int set, double out[2]) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_norms");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_norms");
     if (ctx->world == 1) {  // one rank: the kernel of the two-halves form (the same sums, bit for bit)
         CHK(vlgp_norms_begin(ctx, set));
         return vlgp_norms_end(ctx, out);
@@ -1708,7 +1726,7 @@ extern "C" int vlgp_norms_begin(vlgp_ctx* ctx, int set) {
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_norms_begin");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_norms_begin");
     CHK(wait_norms(ctx));  // (a pass never collected: dropped)
     ctx->x_pending = 0;
     ctx->x_set = set;
@@ -1748,7 +1766,7 @@ extern "C" int vlgp_latent_moments(vlgp_ctx* ctx, int set, double* sum1, double*
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_latent_moments");
+    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_latent_moments");
     std::vector<double> m;
     CHK(moments_host(ctx, *us, m));
     const int L = ctx->L, t = L * (L + 1) / 2;

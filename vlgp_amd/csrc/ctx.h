@@ -76,6 +76,7 @@ struct UnitSet {
     int* d_rep_pair = nullptr;        // (n_pairs) replica of each pair
     unsigned long long* d_rep_mask = nullptr;  // (n_rep, rep_nw) membership masks
     double* d_rep_wconst = nullptr;   // (n_rep, 16): Gaussian constant of w per replica (estep_split.hip); masked: per row
+    double* d_rep_nobs = nullptr;     // masked fit set (masked, n_rep == 1): (N) observed rows per channel (M-step noise)
     void* d_rep_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
     double rep_xh[8] = {};
     int rep_users = 0;

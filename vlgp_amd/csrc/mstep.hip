@@ -29,6 +29,10 @@
 #endif
 
 enum { K_PREP = 0, K_NEWTON = 1, K_NOISE1 = 2, K_NOISE2 = 3 };
+// A masked fit set (vlgp_replicate_masked with one replica): KIND | K_MASKED is the same pass with the missing entries of
+// y left out of every sum.  A value of the existing parameter, like EX_BY_ROW of the E-step's row passes: a parameter
+// more would rename every kernel of the family.
+enum { K_MASKED = 4 };
 
 struct MArgs {
     int N, L, P;
@@ -42,14 +46,26 @@ struct MArgs {
     const double* v;
     const double* a;
     const double* b;
-    const int* gauss;
-    const double* mean;  // NOISE2: per-channel mean of (y - eta)
+    // The two pointers a masked launch (KIND | K_MASKED) needs share the slots of two it does not read: the struct keeps
+    // its size, so the kernel arguments of every unmasked instantiation -- and with them the offsets of the hidden
+    // arguments behind them in its code -- stay what they were.
+    union {
+        const int* gauss;
+        // masked (no Gaussian channel on the handle): (rows, (N + 63) / 64) words, bit n & 63 of word n >> 6 of a row
+        // set where y[row, n] is missing
+        const unsigned long long* mask;
+    };
+    union {
+        const double* mean;  // NOISE2: per-channel mean of (y - eta)
+        const double* nobs;  // masked NEWTON: (N) observed rows per channel
+    };
     double* partial;     // (G, K, N)
 };
 
 __host__ __device__ constexpr int tri(int n) { return n * (n + 1) / 2; }
-template <int LT, int PT, int KIND>
+template <int LT, int PT, int KINDM>
 __host__ __device__ constexpr int nacc() {
+    constexpr int KIND = KINDM & (K_MASKED - 1);
     return KIND == K_PREP ? LT + PT + PT * LT + tri(PT) + (PT <= 2 ? 2 + PT : 0)
          : KIND == K_NEWTON ? 2 * LT + tri(LT) + PT + tri(PT)
          : 1;
@@ -75,11 +91,16 @@ static inline int nstat_rt(int L, int P, int kind) {
 // 256 registers but no second row in flight either, 36 -> 43 ms.  A 512-thread workgroup is two waves per SIMD whatever
 // the register count up to 256; more occupancy needs <= 128 registers, i.e. the accumulators of a channel split over lanes.)
 #define MS_GS 8
-template <int LT, int PT, int KIND, bool EXACT>
+// MASKED: the statistics of a Poisson channel are linear in y (K_PREP), in the rate (K_NEWTON) or in the residual
+// (K_NOISE1 / K_NOISE2): a missing entry puts 0 there by a select -- never a product with 0, what y holds at a missing
+// entry (NaN, anything) reaches no sum -- and with no bit set the sums are the unmasked kernel's, bit for bit.
+template <int LT, int PT, int KINDM, bool EXACT>
 // four waves per SIMD (128 VGPRs) up to five latents; the 2 L + L (L + 1) / 2 accumulators of more latents
 // need the registers more than the occupancy
 __global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_accum(MArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int KIND = KINDM & (K_MASKED - 1);
+    constexpr bool MASKED = (KINDM & K_MASKED) != 0;
     constexpr int NA = nacc<LT, PT, KIND>();
     constexpr int NBUF = 1;
     const int N = A.N, CT = A.CT, S = A.S;
@@ -107,7 +128,19 @@ __global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_
     for (int j = 0; j < PT; ++j) bl[j] = (active && j < P) ? A.b[j * N + n] : 0.0;
 #pragma unroll
     for (int k = 0; k < NA; ++k) acc[k] = 0.0;
-    const bool gch = active ? A.gauss[n] != 0 : false;
+    const bool gch = (active && !MASKED) ? A.gauss[n] != 0 : false;
+    const int nw = (N + 63) >> 6;
+    if constexpr (MASKED && KIND == K_NEWTON) {
+        // a channel with no observed row: every sum is 0, and so would be its Newton systems.  One workgroup's first
+        // slice starts the diagonals of both Hessians at 1: the solve finds H = (1 + eps) I, g = 0 and steps by 0,
+        // instead of counting a failed factorisation when eps == 0.
+        if (active && s == 0 && blockIdx.x == 0 && A.nobs[n] == 0.0) {
+#pragma unroll
+            for (int i = 0; i < LT; ++i) acc[LT + tri(i) + i] = 1.0;
+#pragma unroll
+            for (int i = 0; i < PT; ++i) acc[2 * LT + tri(LT) + PT + tri(i) + i] = 1.0;
+        }
+    }
     const double shift = (KIND == K_NOISE2 && active) ? A.mean[n] : 0.0;
 
     const int64_t c0 = (int64_t)blockIdx.x * A.rows_per_wg;
@@ -143,8 +176,14 @@ __global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_
                 mr[l] = (EXACT || l < L) ? mu_t[rr * L + l] : 0.0;
                 vr[l] = (EXACT || l < L) ? v_t[rr * L + l] : 0.0;
             }
+            // MASKED: is y[row, n] observed?  (the lane's half of the mask word: one register for the load, a 32-bit
+            // shift; asked where the answer is used, after the registers of the rate's chain are free again)
+            auto observed = [&]() -> bool {
+                return ((reinterpret_cast<const unsigned*>(A.mask)[row * (2 * nw) + (n >> 5)] >> (n & 31)) & 1u) == 0u;
+            };
             if constexpr (KIND == K_PREP) {
-                const double yv = A.y[row * N + n];
+                double yv = A.y[row * N + n];
+                if constexpr (MASKED) yv = observed() ? yv : 0.0;
                 int k = 0;
 #pragma unroll
                 for (int l = 0; l < LT; ++l) { acc[k] = fma(mr[l], yv, acc[k]); ++k; }
@@ -176,7 +215,8 @@ __global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_
                     double ex = eta;
 #pragma unroll
                     for (int l = 0; l < LT; ++l) ex = fma(vr[l], al2[l], ex);
-                    const double rate = trunc_exp_tab64(ex, etab);
+                    double rate = trunc_exp_tab64(ex, etab);
+                    if constexpr (MASKED) rate = observed() ? rate : 0.0;
                     double mt[LT], q[LT];
 #pragma unroll
                     for (int l = 0; l < LT; ++l) {
@@ -199,7 +239,8 @@ __global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_
 #pragma unroll
                         for (int j = 0; j <= i; ++j) { acc[k] = fma(xv[i] * xv[j], rate, acc[k]); ++k; }
                 } else {
-                    const double dres = A.y[row * N + n] - eta - shift;
+                    double dres = A.y[row * N + n] - eta - shift;
+                    if constexpr (MASKED) dres = observed() ? dres : 0.0;
                     if constexpr (KIND == K_NOISE1) acc[0] += dres;
                     else acc[0] = fma(dres, dres, acc[0]);
                 }
@@ -853,6 +894,16 @@ __global__ void noise_final_kernel(int N, double count, const double* s2, double
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n < N) noise[n] = s2[n] / count;
 }
+// the same for a masked fit set: every channel divides by its own number of observed rows; a channel without one has a
+// mean of 0 (its masked residuals are all 0) and keeps its noise
+__global__ void noise_mean_nobs_kernel(int N, const double* nobs, const double* s1, double* mean) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n < N) mean[n] = nobs[n] > 0.0 ? s1[n] / nobs[n] : 0.0;
+}
+__global__ void noise_final_nobs_kernel(int N, const double* nobs, const double* s2, double* noise) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n < N && nobs[n] > 0.0) noise[n] = s2[n] / nobs[n];
+}
 // noise = var(y - eta) per channel (core.py:177) from sums the M-step holds anyway -- no pass over y:
 //   sum (y - eta) = 1'y - a'(1'mu) - b'(1'x),   sum (y - eta)^2 = y'y - 2 (a'(mu'y) + b'(x'y)) + a'(mu'mu) a + 2 b'(x'mu) a + b'(x'x) b.
 // The differences cancel where the fit is close (a Gaussian channel at high signal-to-noise): taken only for sets without
@@ -967,6 +1018,21 @@ static bool noise_by_passes(const vlgp_ctx* ctx) { return ctx->n_gauss > 0 || ct
 template <int LT, int PT>
 static void launch_accum_k(hipStream_t st, int kind, const Geometry& g, const MArgs& A) {
     dim3 grid(g.G, g.tiles), blk(g.nthr);
+    if (kind & K_MASKED) {  // a masked fit set (launch_mstep admits it up to ten latents)
+        if constexpr (LT <= 10) {
+            if (kind == (K_NEWTON | K_MASKED) && accum_exact(LT, PT, A.L, A.P, A.x == nullptr)) {
+                hipLaunchKernelGGL((mstep_accum<LT, PT, K_NEWTON | K_MASKED, true>), grid, blk, g.lds, st, A);
+                return;
+            }
+            switch (kind) {
+                case K_PREP | K_MASKED: hipLaunchKernelGGL((mstep_accum<LT, PT, K_PREP | K_MASKED, false>), grid, blk, g.lds, st, A); break;
+                case K_NEWTON | K_MASKED: hipLaunchKernelGGL((mstep_accum<LT, PT, K_NEWTON | K_MASKED, false>), grid, blk, g.lds, st, A); break;
+                case K_NOISE1 | K_MASKED: hipLaunchKernelGGL((mstep_accum<LT, PT, K_NOISE1 | K_MASKED, false>), grid, blk, g.lds, st, A); break;
+                default: hipLaunchKernelGGL((mstep_accum<LT, PT, K_NOISE2 | K_MASKED, false>), grid, blk, g.lds, st, A); break;
+            }
+        }
+        return;
+    }
     if (kind == K_NEWTON && accum_exact(LT, PT, A.L, A.P, A.x == nullptr)) {  // the hot launch, specialised
         hipLaunchKernelGGL((mstep_accum<LT, PT, K_NEWTON, true>), grid, blk, g.lds, st, A);
         return;
@@ -1083,6 +1149,20 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
                  double da_bound, double db_bound) {
     const int N = ctx->N, L = ctx->L, P = ctx->P;
     const bool gen = mstep_generic(ctx, L, P);  // beyond the compiled sizes: loop-based kernels, solves in global memory
+    // a masked fit set (api.hip lets no other replicated set in): the compiled Poisson kernels on one rank, or an error
+    const bool masked = us.rep_src >= 0;
+    if (masked) {
+        if (ctx->n_gauss > 0)
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: the handle has Gaussian channels (their least-squares "
+                             "update needs per-channel masked Gram matrices)");
+        if (gen)
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: the loop-based M-step kernels (P > 8 or "
+                             "VLGP_MSTEP_GENERIC) take no mask");
+        if (L > 10) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: more than 10 latents (L > 10)");
+        if (ctx->world > 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: more than one rank");
+        if (!us.d_rep_mask || !us.d_rep_nobs) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: the set has no mask");
+    }
+    const int km = masked ? K_MASKED : 0;
     const Geometry g = plan(ctx, us.rows);
     const int Kp = nstat_rt(L, P, K_PREP), Kn = nstat_rt(L, P, K_NEWTON);
     const int Kl = tri(L) + 3 * L + 1;
@@ -1104,12 +1184,14 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
 
     // Single rank, no per-launch timing: record the whole sequence once and replay it (see ctx.h).
     const bool use_graph = ctx->world == 1 && !ctx->prof_on && !ctx->sw.no_mgraph;
-    const bool noise_passes = noise_by_passes(ctx);
+    // (masked: the moments route assumes one row count and one Gram of mu for all channels)
+    const bool noise_passes = masked || noise_by_passes(ctx);
     std::vector<double> key;
     if (use_graph) {
         auto pk = [&](const void* p_) { key.push_back((double)(uintptr_t)p_); };
         pk(us.y); pk(us.x_ones ? nullptr : us.x); pk(us.mu); pk(us.v); pk(us.w); pk(us.dmu); pk(W); pk(ctx->d_a); pk(ctx->d_b);
         pk(ctx->d_noise); pk(ctx->d_da); pk(ctx->d_db); pk(ctx->d_fail_m); pk(ctx->d_gauss);
+        pk(masked ? us.d_rep_mask : nullptr); pk(masked ? us.d_rep_nobs : nullptr); key.push_back((double)masked);
         for (double v_ : {(double)us.rows, (double)N, (double)L, (double)P, (double)ctx->n_gauss, (double)n_iter,
                           (double)use_hessian, eps, lr, da_bound, db_bound, (double)noise_passes, (double)gen, ctx->sw.mstep_wg_per_cu})
             key.push_back(v_);
@@ -1130,6 +1212,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
     A.N = N; A.L = L; A.P = P; A.rows = us.rows; A.rows_per_wg = g.rows_per_wg; A.CT = g.CT; A.S = g.S;
     A.y = us.y; A.x = us.x_ones ? nullptr : us.x; A.mu = us.mu; A.v = us.v;
     A.a = ctx->d_a; A.b = ctx->d_b; A.gauss = ctx->d_gauss; A.mean = d_mean; A.partial = d_part;
+    if (masked) A.mask = us.d_rep_mask;  // (in the slot of gauss: the Newton launch gets nobs in the slot of mean)
 
     auto reduce_to = [&](int K, double* dst) -> int {
         const int64_t n = (int64_t)K * N;
@@ -1140,7 +1223,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
     };
 
     // sweep-invariant moments
-    CHK(launch_accum(ctx, K_PREP, g, A, d_cache));
+    CHK(launch_accum(ctx, K_PREP | km, g, A, d_cache));
     CHK(reduce_to(Kp, d_prep));
     CHK(latent_moments(ctx, us, d_part, d_lat, true));
     double total_rows = (double)us.rows;
@@ -1174,20 +1257,24 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
                                    d_prep, d_lat, ctx->d_a, ctx->d_b, ctx->d_noise);
                 HIPCHK(ctx, hipGetLastError());
             } else {
-            CHK(launch_accum(ctx, K_NOISE1, g, A, d_cache));
+            CHK(launch_accum(ctx, K_NOISE1 | km, g, A, d_cache));
             CHK(reduce_to(1, d_s1));
-            hipLaunchKernelGGL(noise_mean_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N,
+            if (masked) hipLaunchKernelGGL(noise_mean_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.d_rep_nobs, d_s1, d_mean);
+            else hipLaunchKernelGGL(noise_mean_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N,
                                total_rows, d_s1, d_mean);
-            CHK(launch_accum(ctx, K_NOISE2, g, A, d_cache));
+            CHK(launch_accum(ctx, K_NOISE2 | km, g, A, d_cache));
             CHK(reduce_to(1, d_s1));
-            hipLaunchKernelGGL(noise_final_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N,
+            if (masked) hipLaunchKernelGGL(noise_final_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.d_rep_nobs, d_s1, ctx->d_noise);
+            else hipLaunchKernelGGL(noise_final_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N,
                                total_rows, d_s1, ctx->d_noise);
             HIPCHK(ctx, hipGetLastError());
             }
         }
         if (any_poisson) {
             vlgp_prof_begin(ctx, VLGP_PROF_MSTEP, st);
-            int rc = launch_accum(ctx, K_NEWTON, g, A, d_cache);
+            MArgs An = A;
+            if (masked) An.nobs = us.d_rep_nobs;  // (the Newton launch reads no mean)
+            int rc = launch_accum(ctx, K_NEWTON | km, g, An, d_cache);
             vlgp_prof_end(ctx, VLGP_PROF_MSTEP, (double)us.rows, st);
             CHK(rc);
             if (ctx->world == 1) {  // no all-reduce between the sum and the solves: one launch for both

@@ -142,6 +142,14 @@ def _resident(trials, params, units, device, priors=True):
         yield eng
 
 
+def _no_missing(trials, what):
+    """A fit with missing observations (``fit(..., missing=)``) leaves the mask in every trial: a score over every (row,
+    channel) would count whatever ``y`` holds at the missing entries."""
+    if any(tr.get("missing") is not None for tr in trials):
+        raise ValueError("%s: the trials carry 'missing' (a fit with missing observations); scoring every entry would "
+                         "count the values stored at the missing ones" % what)
+
+
 def loglik(fit, per_channel=False, device=0):
     """Log-likelihood of a fit's own trials under their own posterior (``mu``, ``v``): a float, or the per-channel
     sums with ``per_channel=True``.
@@ -151,6 +159,7 @@ def loglik(fit, per_channel=False, device=0):
     rate (module docstring), the Poisson term includes ``-lgamma(y + 1)``, Gaussian channels are scored with their
     noise variance, and the sum runs over every (row, channel) of every trial."""
     trials, params, config = fit["trials"], fit["params"], fit.get("config") or {}
+    _no_missing(trials, "loglik")
     vb = config.get("method", "VB") == "VB"
     L = params["zdim"]
     units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "v": tr.get("v", np.zeros((tr["y"].shape[0], L))),
@@ -216,6 +225,7 @@ def elbo(fit, per_trial=False, device=0):
     the device leaves the expected log-likelihood of every row (channels summed in order) in the same launch and the
     rows of a trial are added on the host -- no second reduction kernel, no call per trial."""
     trials, params, config = fit["trials"], fit["params"], fit.get("config") or {}
+    _no_missing(trials, "elbo")
     vb = config.get("method", "VB") == "VB"
     L = params["zdim"]
 

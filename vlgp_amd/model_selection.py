@@ -67,7 +67,8 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
     For every trial fold and candidate: ``fit`` on fresh copies of the other trials (``fit_kwargs`` are ``fit``'s),
     then ``leave_group_out`` on copies of the fold with the fit's parameters and the shared channel folds (``n_iter``
     E-step iterations, default the fit's ``max_iter``).  Every fit starts with ``np.random.seed(seed)`` (the state of
-    the caller's generator is restored), so a second call returns the same bits.  The caller's trial dicts are not
+    the caller's generator is restored), so a second call returns the same bits.  A ``missing`` among ``fit_kwargs`` (one
+    mask per trial of ``trials``) is cut to the training trials of every fold; the held-out trials are scored as they are.  The caller's trial dicts are not
     written and their posteriors are not read.  A candidate whose fit or evaluation raises is recorded as NaN for that
     fold, the exception text goes into ``errors`` and the sweep continues.
 
@@ -100,9 +101,13 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
     for f, test_idx in enumerate(t_folds):
         held = set(test_idx)
         train_idx = [i for i in range(len(trials)) if i not in held]
+        if fit_kwargs.get("missing") is not None:  # fit's per-trial mask follows the training trials
+            fold_kwargs = dict(fit_kwargs, missing=[fit_kwargs["missing"][i] for i in train_idx])
+        else:
+            fold_kwargs = fit_kwargs
         for c, n in enumerate(n_factors_list):
             try:
-                fitted = _seeded_fit(seed, _fresh(trials, train_idx), n, device=device, verbose=False, **fit_kwargs)
+                fitted = _seeded_fit(seed, _fresh(trials, train_idx), n, device=device, verbose=False, **fold_kwargs)
                 if speckled:
                     got = leave_entries_out(_fresh(trials, test_idx), fitted["params"], fitted["config"],
                                             n_folds=n_channel_folds, seed=seed, n_iter=n_iter, device=device)
