@@ -77,8 +77,9 @@ def test_fit_with_missing_refuses_a_channel_never_observed():
 
 
 def test_missing_none_is_todays_call_path(monkeypatch):
-    """No mask: FitSession never enters the masked initialisation and reaches the engine by the plain path."""
-    from vlgp_amd import api
+    """No mask: FitSession runs no masked-only step -- neither the masked argument check nor the mask normalisation, and
+    no ``Engine.replicate``, without which a session cannot make a masked set -- and reaches the engine."""
+    from vlgp_amd import api, util
 
     class Reached(Exception):
         pass
@@ -86,17 +87,53 @@ def test_missing_none_is_todays_call_path(monkeypatch):
     def plain_engine(params, device=0):
         raise Reached()
 
-    def masked_init(self, *args, **kwargs):
-        raise AssertionError("missing=None took the masked path")
+    def masked_only(*args, **kwargs):
+        raise AssertionError("missing=None took a masked-only step")
 
     monkeypatch.setattr(api.E.Engine, "for_params", staticmethod(plain_engine))
-    monkeypatch.setattr(api.FitSession, "_init_masked", masked_init)
+    monkeypatch.setattr(api, "_masked_inputs", masked_only)
+    monkeypatch.setattr(util, "_per_trial_entries", masked_only)
+    monkeypatch.setattr(api, "_per_trial_entries", masked_only)
+    monkeypatch.setattr(api.E.Engine, "replicate", masked_only)
     trials, _ = small()
     with pytest.raises(Reached):
         api.fit(trials, 2, verbose=False)
     with pytest.raises(Reached):
         api.fit(trials, 2, verbose=False, missing=None)
     assert api.FitSession.finish is not None and "missing" not in trials[0]
+    assert all("missing" not in tr for tr in trials)
+
+
+def test_segment_dicts_are_trial_major_views_of_the_trials_and_of_the_y_given():
+    """The function the device cut (``_segments``) and the masked fit's host cut share: views of the trial arrays, y
+    sliced from the y handed in, trial-major order, every dmu a view of one block."""
+    from vlgp_amd.api import _segment_dicts
+
+    window, N, L = 40, 4, 2
+    rng = np.random.default_rng(3)
+    trials = [{"y": rng.poisson(1.0, (T, N)).astype(float), "x": np.ones((T, 1, N)), "mu": rng.standard_normal((T, L)),
+               "w": rng.random((T, L)), "v": rng.random((T, L))} for T in (40, 80, 40)]
+    ys = [tr["y"] + 100.0 for tr in trials]  # another y than the trials' own
+    segs = _segment_dicts(trials, ys, [range(0, tr["y"].shape[0], window) for tr in trials], window)
+    assert len(segs) == 4 and all(list(sg) == ["y", "x", "mu", "w", "v", "dmu"] for sg in segs)
+    owner, start = [0, 1, 1, 2], [0, 0, 40, 0]
+    for sg, i, s0 in zip(segs, owner, start):
+        for k in ("x", "mu", "w", "v"):
+            assert sg[k].shape[0] == window and np.shares_memory(sg[k], trials[i][k])
+            assert np.array_equal(sg[k], trials[i][k][s0:s0 + window])
+        assert np.shares_memory(sg["y"], ys[i]) and not np.shares_memory(sg["y"], trials[i]["y"])
+        for j in set(range(3)) - {i}:
+            assert not np.shares_memory(sg["mu"], trials[j]["mu"])
+    segs[2]["mu"][...] = 7.0  # a view: writes go through to rows 40 ... 79 of the second trial
+    assert np.all(trials[1]["mu"][40:] == 7.0) and not np.any(trials[1]["mu"][:40] == 7.0)
+    assert np.array_equal(np.concatenate([sg["y"] for sg in segs]), np.concatenate(ys))
+    assert np.array_equal(np.concatenate([sg["mu"] for sg in segs]), np.concatenate([tr["mu"] for tr in trials]))
+    block = segs[0]["dmu"].base
+    assert block.shape == (4, window, L) and not block.any()
+    assert all(sg["dmu"].base is block and np.shares_memory(sg["dmu"], block[i]) and sg["dmu"].shape == (window, L)
+               for i, sg in enumerate(segs))
+    segs[3]["dmu"][...] = 1.0
+    assert block[3].all() and not block[:3].any()
 
 
 @pytest.mark.parametrize("what", ["loglik", "elbo"])

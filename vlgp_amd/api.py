@@ -13,7 +13,7 @@ import numpy as np
 
 from . import engine as E
 from .preprocess import fill_params, fill_trials, get_config, get_params, initialize
-from .util import segment_starts
+from .util import _per_trial_entries, segment_starts
 
 __all__ = ["fit", "transform", "forecast", "FitSession", "bind_priors"]
 
@@ -28,26 +28,37 @@ def _echo(msg):
     print(msg, flush=True)
 
 
+def _segment_dicts(trials, ys, starts, window):
+    """The window-sized segments of the dict interface (util.cut_trials), trial-major: host-side NumPy views of every
+    trial's x, mu, w, v and of ``ys[i]`` -- the y to slice trial ``i``'s from, which need not be ``tr["y"]`` -- at the start
+    rows ``starts[i]``."""
+    segs = []
+    for tr, y, trial_starts in zip(trials, ys, starts):
+        for s in trial_starts:
+            sl = slice(int(s), int(s) + window)
+            segs.append({k: (y if k == "y" else tr[k])[sl] for k in ("y", "x", "mu", "w", "v")})
+    # the per-segment dmu buffers fill_trials would otherwise allocate one by one (4000 at C3): views of one block
+    if segs:
+        block = np.zeros((len(segs), window, segs[0]["mu"].shape[1]))
+        for i, sg in enumerate(segs):
+            sg["dmu"] = block[i]
+    return segs
+
+
 def _segments(trials, window, eng):
     """Cut the resident trials into window-sized segments (util.cut_trials):
     host-side NumPy views for the dict interface, one device cut for the data."""
-    starts, segs, row0 = [], [], 0
+    per_trial, starts, row0 = [], [], 0
     for tr in trials:
         T = tr["y"].shape[0]
         if T < window:
             # the reference would cut a shorter segment here and then fail in gp.optimize (np.stack of
             # unequal segments); the device cut needs equal lengths, so say it up front
             raise ValueError("trial of %d bins is shorter than window=%d; pass a smaller window" % (T, window))
-        for s in segment_starts(T, window):
-            sl = slice(int(s), int(s) + window)
-            segs.append({k: tr[k][sl] for k in ("y", "x", "mu", "w", "v")})
-            starts.append(row0 + int(s))
+        per_trial.append([int(s) for s in segment_starts(T, window)])
+        starts.extend(row0 + s for s in per_trial[-1])
         row0 += T
-    # the per-segment dmu buffers fill_trials would otherwise allocate one by one (4000 at C3): views of one block
-    if segs:
-        block = np.zeros((len(segs), window, segs[0]["mu"].shape[1]))
-        for i, sg in enumerate(segs):
-            sg["dmu"] = block[i]
+    segs = _segment_dicts(trials, [tr["y"] for tr in trials], per_trial, window)
     starts = np.asarray(starts, dtype=np.int64)
     # Overlapping neighbours (a trial length that is not a multiple of the window, vlgp/util.py:482-496): in the reference
     # they are views of the same rows, visited one after the other.  The device keeps independent copies, stored
@@ -78,6 +89,48 @@ def _segments(trials, window, eng):
     return E.DeviceTrials(segs, eng, SET_SEGMENTS, parent_set=SET_TRIALS, unit_of=unit_of)
 
 
+def _masked_inputs(trials, missing, comm, track_elbo, config, kwargs):
+    """What ``fit(..., missing=)`` refuses, before an engine exists and before a trial dict is touched.  Returns the
+    mask per trial and the private copies of y the fit works on."""
+    lik = kwargs.get("lik", "poisson")
+    if any(k == "gaussian" for k in (lik if isinstance(lik, list) else [lik])):
+        raise ValueError("fit(missing=...) takes Poisson channels only: a Gaussian channel's update needs "
+                         "per-channel masked Gram matrices")
+    if kwargs.get("history", 0) > 0:
+        raise ValueError("fit(missing=...) takes no history: the regressors would be built from missing counts")
+    if comm is not None and comm.world > 1:
+        raise ValueError("fit(missing=...) runs on one rank: it takes no comm with world > 1")
+    if track_elbo:
+        raise ValueError("fit(missing=...) takes no track_elbo: the bound of a masked set is not computed")
+    if config["constrain_loading"] == "svd":
+        raise ValueError("fit(missing=...) takes no constrain_loading='svd': it rests on segments being views of trials")
+    missing = [np.array(m, dtype=bool) for m in _per_trial_entries(missing, trials, "missing", bool)]
+    window = config["window"]
+    if window and any(tr["y"].shape[0] % window for tr in trials):
+        raise ValueError("fit(missing=...) needs trial lengths that are multiples of window=%d: overlapping "
+                         "segments share rows, which a masked set cannot" % window)
+    n_obs = sum((~m).sum(axis=0) for m in missing)
+    if np.any(n_obs == 0):
+        raise ValueError("channel(s) %s have no observed entry" % np.flatnonzero(n_obs == 0).tolist())
+    # private copies of y, the holes filled with the channel's mean over its observed entries: the initialisation
+    # (factor analysis, initial latents, b = log mean y) works on them, and they are what the device holds -- the
+    # masked row passes of the E-step leave an entry out by a zero coefficient, under which a NaN in the caller's y
+    # would survive.  The fill value reaches no result after the initialisation; the caller's values at missing entries
+    # are never read.
+    y_sum = sum(np.where(m, 0.0, tr["y"]).sum(axis=0) for tr, m in zip(trials, missing))
+    y_mean = y_sum / n_obs
+    return missing, [np.where(m, y_mean[None, :], tr["y"]).astype(float) for tr, m in zip(trials, missing)]
+
+
+def _ones_for_broadcast_x(trials):
+    """The reference leaves a writable np.ones((T, xdim, N)) in every trial that came without regressors: make it of the
+    zero-stride view the fit worked on."""
+    for tr in trials:
+        x = tr.get("x")
+        if isinstance(x, np.ndarray) and not x.flags.writeable and x.size and all(st == 0 for st in x.strides):
+            tr["x"] = np.ones(x.shape)
+
+
 class FitSession:
     """The three phases of api.fit as separate calls.
 
@@ -88,18 +141,20 @@ class FitSession:
 
     ``bench.py`` drives ``em_iteration`` directly to time single EM iterations;
     ``fit`` is ``FitSession(...).run().finish()``.
+
+    ``missing`` (``fit``'s docstring) varies six steps and nothing else: the argument checks, ``_initialize``,
+    ``_resident_trials``, ``_cut_segments``, ``_segments_to_trials`` and ``_after_inference``.
     """
 
     def __init__(self, trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, missing=None, **kwargs):
-        self.echo = _echo if verbose else None
+        self.echo = echo = _echo if verbose else None
         self.track_elbo = bool(track_elbo)
-        self.missing = None
-        if missing is not None:
-            self._init_masked(trials, n_factors, device, comm, missing, kwargs)
-            return
-        echo = self.echo
         self.trials = trials
         self.config = config = get_config(**kwargs)
+        self.missing = None
+        if missing is not None:
+            self.missing, self._y_filled = _masked_inputs(trials, missing, comm, self.track_elbo, config, kwargs)
+            self._mask_rows = np.concatenate(self.missing, axis=0)
         logger.info("\n".join("{} : {}".format(k, v) for k, v in config.items()))
         kwargs["omega_bound"] = config["omega_bound"]
         self.params = params = get_params(trials, n_factors, **kwargs)
@@ -118,17 +173,7 @@ class FitSession:
             multi = comm is not None and comm.world > 1
             if multi:
                 comm.attach(eng)
-            # sharded fit: the subsample, the factor analysis and b = log mean y are pooled over the ranks
-            plan = initialize(trials, params, config, defer_latent=True, pool=eng if multi else None)
-            fill_trials(trials)
-            eng.upload(SET_TRIALS, trials)
-            if plan is not None:
-                # the two full passes over y of preprocess.initialize, on the device: mu = transform(y), b = log mean y
-                colsum = eng.project_latent(SET_TRIALS, plan["proj"], plan["shift"])
-                if plan["need_b"]:
-                    if multi:
-                        eng.allreduce_host(colsum)
-                    params["b"] = np.log(np.maximum(colsum[None, :] / plan["rows"], config["eps"]))
+            self._initialize(multi)
             if echo:
                 echo("Initialized")
             fill_params(params)
@@ -137,170 +182,116 @@ class FitSession:
             if multi:
                 self._replicate_params()
             eng.set_params(params["a"], params["b"], params["noise"])
-            self.dev_trials = E.DeviceTrials(trials, eng, SET_TRIALS)
-            E.make_cholesky(self.dev_trials, params, config)
-            E.update_w(self.dev_trials, params, config)
-            E.update_v(self.dev_trials, params, config)
-            window = config["window"]
-            if window:
-                self.segs = _segments(trials, window, eng)
+            self.dev_trials = self._resident_trials()
+            self._prior_w_v()
+            if config["window"]:
+                self.segs = self._cut_segments(config["window"])
                 E.make_cholesky(self.segs, params, config)
                 fill_trials(self.segs)
             else:
                 self.segs = self.dev_trials
-            # params["initial"] = deepcopy(params) (api.py:60): every key, the segment-length factors included.  The
-            # resident factor is downloaded for it when a window is set (one (L, window, rank) array); without a
-            # window it is every full-length factor: those are rebuilt on the host when somebody reads them
-            snapshot = {k: v for k, v in params.items() if k != "cholesky"}
-            chol = params["cholesky"]
-            if isinstance(chol, E._LazyPrior):
-                # no window: the full-length factors of the initial omega, factored on first access (engine._InitialPrior)
-                chol = chol.materialize() if window else E._InitialPrior(chol._lengths, params["omega"], params["sigma"],
-                                                                         params["rank"])
-            snapshot["cholesky"] = chol
-            params["initial"] = copy.deepcopy(snapshot)
+            self._snapshot_initial()
             E._push_params(eng, params)
         except Exception:
             self.close()
             raise
 
-    def _init_masked(self, trials, n_factors, device, comm, missing, kwargs):
-        """The same phases for trials with missing observations (``fit``'s ``missing``): the initialisation on private
-        copies of y with the holes filled by the channel's observed mean, then everything on masked fit sets."""
-        from .evaluation import _per_trial_entries
-
-        echo = self.echo
-        lik = kwargs.get("lik", "poisson")
-        if any(k == "gaussian" for k in (lik if isinstance(lik, list) else [lik])):
-            raise ValueError("fit(missing=...) takes Poisson channels only: a Gaussian channel's update needs "
-                             "per-channel masked Gram matrices")
-        if kwargs.get("history", 0) > 0:
-            raise ValueError("fit(missing=...) takes no history: the regressors would be built from missing counts")
-        if comm is not None and comm.world > 1:
-            raise ValueError("fit(missing=...) runs on one rank: it takes no comm with world > 1")
-        if self.track_elbo:
-            raise ValueError("fit(missing=...) takes no track_elbo: the bound of a masked set is not computed")
-        self.trials = trials
-        self.config = config = get_config(**kwargs)
-        if config["constrain_loading"] == "svd":
-            raise ValueError("fit(missing=...) takes no constrain_loading='svd': it rests on segments being views of trials")
-        missing = [np.array(m, dtype=bool) for m in _per_trial_entries(missing, trials, "missing", bool)]
-        window = config["window"]
-        if window and any(tr["y"].shape[0] % window for tr in trials):
-            raise ValueError("fit(missing=...) needs trial lengths that are multiples of window=%d: overlapping "
-                             "segments share rows, which a masked set cannot" % window)
-        n_obs = sum((~m).sum(axis=0) for m in missing)
-        if np.any(n_obs == 0):
-            raise ValueError("channel(s) %s have no observed entry" % np.flatnonzero(n_obs == 0).tolist())
-        # private copies of y, the holes filled with the channel's mean over its observed entries: the initialisation
-        # (factor analysis, initial latents, b = log mean y) works on them, and they are what the device holds -- the
-        # masked row passes of the E-step leave an entry out by a zero coefficient, under which a NaN in the caller's y
-        # would survive.  The fill value reaches no result after the initialisation; the caller's values at missing entries
-        # are never read.
-        y_sum = sum(np.where(m, 0.0, tr["y"]).sum(axis=0) for tr, m in zip(trials, missing))
-        y_mean = y_sum / n_obs
-        work = [dict(tr, y=np.where(m, y_mean[None, :], tr["y"]).astype(float)) for tr, m in zip(trials, missing)]
-        logger.info("\n".join("{} : {}".format(k, v) for k, v in config.items()))
-        kwargs["omega_bound"] = config["omega_bound"]
-        self.params = params = get_params(trials, n_factors, **kwargs)
-        self.comm = comm
-        self.eng = None
-        self.runtime = E.new_runtime()
-        self.materialize_x = bool(kwargs.get("materialize_x", True))
-        self.missing = missing
-
-        if echo:
-            echo("Initializing")
-        eng = E.Engine.for_params(params, device)
-        self.eng = eng
-        try:
+    def _initialize(self, multi):
+        """preprocess.initialize and what it leaves in the trials.  Plain: the trials go to the device here, which does
+        the two full passes over y.  Masked: on the filled copies of y, all on the host; nothing is uploaded yet."""
+        trials, params, config, eng = self.trials, self.params, self.config, self.eng
+        if self.missing is not None:
+            work = [dict(tr, y=y) for tr, y in zip(trials, self._y_filled)]
             initialize(work, params, config)
             fill_trials(work)
             for tr, wk in zip(trials, work):  # the caller's dicts get what initialize leaves; their y stays theirs
                 tr.update({k: v for k, v in wk.items() if k != "y"})
-            if echo:
-                echo("Initialized")
-            fill_params(params)
-            for key in ("a", "b", "noise", "omega", "sigma"):
-                params[key] = np.array(params[key], dtype=float)
-            eng.set_params(params["a"], params["b"], params["noise"])
-            self._y_dev = [wk["y"] for wk in work]
-            eng.upload(SET_TRIALS, [dict(tr, y=yd) for tr, yd in zip(trials, self._y_dev)])
-            self._mask_rows = np.concatenate(missing, axis=0)
-            eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=self._mask_rows[None])
-            self.dev_trials = E.DeviceTrials(trials, eng, SET_TRIALS_MASKED)
-            E.make_cholesky(self.dev_trials, params, config)
-            E.update_w(self.dev_trials, params, config)
-            E.update_v(self.dev_trials, params, config)
-            if window:
-                # the segments as a plain set of their own (a host cut: y, x, mu, v, w), and its masked fit set.  Trial
-                # lengths are multiples of the window: the segments' rows, in order, are the trials' rows.
-                self.dev_trials.pull(("mu", "v", "w"))
-                segs = []
-                for tr, yd in zip(trials, self._y_dev):
-                    for s0 in range(0, tr["y"].shape[0], window):
-                        segs.append({k: (yd if k == "y" else tr[k])[s0:s0 + window] for k in ("y", "x", "mu", "w", "v")})
-                block = np.zeros((len(segs), window, params["zdim"]))
-                for i, sg in enumerate(segs):
-                    sg["dmu"] = block[i]
-                eng.upload(SET_SEGMENTS, segs)
-                eng.replicate(SET_SEGMENTS, SET_SEGMENTS_MASKED, held_out=self._mask_rows[None])
-                self.segs = E.DeviceTrials(segs, eng, SET_SEGMENTS_MASKED)
-                E.make_cholesky(self.segs, params, config)
-                fill_trials(self.segs)
-            else:
-                self.segs = self.dev_trials
-            snapshot = {k: v for k, v in params.items() if k != "cholesky"}
-            chol = params["cholesky"]
-            if isinstance(chol, E._LazyPrior):
-                chol = chol.materialize() if window else E._InitialPrior(chol._lengths, params["omega"], params["sigma"],
-                                                                         params["rank"])
-            snapshot["cholesky"] = chol
-            params["initial"] = copy.deepcopy(snapshot)
-            E._push_params(eng, params)
-        except Exception:
-            self.close()
-            raise
+            return
+        # sharded fit: the subsample, the factor analysis and b = log mean y are pooled over the ranks
+        plan = initialize(trials, params, config, defer_latent=True, pool=eng if multi else None)
+        fill_trials(trials)
+        eng.upload(SET_TRIALS, trials)
+        if plan is not None:
+            # the two full passes over y of preprocess.initialize, on the device: mu = transform(y), b = log mean y
+            colsum = eng.project_latent(SET_TRIALS, plan["proj"], plan["shift"])
+            if plan["need_b"]:
+                if multi:
+                    eng.allreduce_host(colsum)
+                params["b"] = np.log(np.maximum(colsum[None, :] / plan["rows"], config["eps"]))
 
-    def _finish_masked(self):
-        eng, params, config, echo = self.eng, self.params, self.config, self.echo
-        try:
-            if self.segs is not self.dev_trials:
-                # the segments' posterior back into the trials (same rows, same order), then the trials' masked fit
-                # set again from it
-                got = eng.download(SET_SEGMENTS_MASKED, ("mu", "v", "w"))
-                row = 0
-                for tr in self.trials:
-                    T = tr["y"].shape[0]
-                    for k in ("mu", "v"):
-                        tr[k][...] = got[k][row:row + T]
-                    tr["w"] = got["w"][row:row + T].copy()
-                    row += T
-                eng.free_units(SET_SEGMENTS_MASKED)
-                eng.free_units(SET_TRIALS_MASKED)
-                eng.upload(SET_TRIALS, [dict(tr, y=yd) for tr, yd in zip(self.trials, self._y_dev)])
-                eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=self._mask_rows[None])
-                self.dev_trials = E.DeviceTrials(self.trials, eng, SET_TRIALS_MASKED)
-            E.make_cholesky(self.dev_trials, params, config)
-            E.update_w(self.dev_trials, params, config)
-            E.update_v(self.dev_trials, params, config)
-            if echo:
-                echo("Inferring")
-            E.infer(self.dev_trials, params, config, echo=echo)
-            self.dev_trials.pull()
+    def _resident_trials(self):
+        """The set of the full-length trials.  Plain: ``SET_TRIALS`` as ``_initialize`` uploaded it.  Masked: the trials
+        as they are now with the filled y, and their masked fit set (one replica: the same rows, one mask bit per entry)."""
+        if self.missing is None:
+            return E.DeviceTrials(self.trials, self.eng, SET_TRIALS)
+        self.eng.upload(SET_TRIALS, [dict(tr, y=y) for tr, y in zip(self.trials, self._y_filled)])
+        self.eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=self._mask_rows[None])
+        return E.DeviceTrials(self.trials, self.eng, SET_TRIALS_MASKED)
+
+    def _cut_segments(self, window):
+        """The set the EM loop works on.  Plain: a device cut of ``SET_TRIALS``, overlaps included.  Masked: a plain set of
+        its own (a host cut: y, x, mu, v, w) and its masked fit set; trial lengths are multiples of the window, so the
+        segments' rows, in order, are the trials' rows."""
+        if self.missing is None:
+            return _segments(self.trials, window, self.eng)
+        self.dev_trials.pull(("mu", "v", "w"))
+        segs = _segment_dicts(self.trials, self._y_filled, [range(0, y.shape[0], window) for y in self._y_filled], window)
+        self.eng.upload(SET_SEGMENTS, segs)
+        self.eng.replicate(SET_SEGMENTS, SET_SEGMENTS_MASKED, held_out=self._mask_rows[None])
+        return E.DeviceTrials(segs, self.eng, SET_SEGMENTS_MASKED)
+
+    def _segments_to_trials(self):
+        """The segments' posterior back into the full-length trials.  Plain: a device merge.  Masked: through the host
+        (same rows, same order), then the trials' masked fit set again from it."""
+        eng = self.eng
+        if self.missing is None:
+            eng.merge(SET_SEGMENTS)
+            if self.segs.detached:  # constrain_loading "svd": the trials kept their pre-rotation mu (core.py:407-408)
+                eng.stash_mu(SET_TRIALS, restore=True)
+            return
+        got = eng.download(SET_SEGMENTS_MASKED, ("mu", "v", "w"))
+        row = 0
+        for tr in self.trials:
+            T = tr["y"].shape[0]
+            for k in ("mu", "v"):
+                tr[k][...] = got[k][row:row + T]
+            tr["w"] = got["w"][row:row + T].copy()
+            row += T
+        eng.free_units(SET_SEGMENTS_MASKED)
+        eng.free_units(SET_TRIALS_MASKED)
+        self.dev_trials = self._resident_trials()
+
+    def _after_inference(self):
+        """Plain: the bound of the full-length trials, when tracked.  Masked: every trial carries its mask."""
+        if self.missing is not None:
             for tr, m in zip(self.trials, self.missing):
                 tr["missing"] = m
-                x = tr.get("x")
-                if self.materialize_x and isinstance(x, np.ndarray) and not x.flags.writeable and x.size and \
-                        all(st == 0 for st in x.strides):
-                    tr["x"] = np.ones(x.shape)
-            if isinstance(params["cholesky"], E._LazyPrior):
-                params["cholesky"] = params["cholesky"].materialize()
-            if echo:
-                echo("Done")
-        finally:
-            self.close()
-        return {"trials": self.trials, "params": params, "config": config}
+        elif self.track_elbo:  # the bound of the full-length trials under the final posterior, summed over the ranks
+            final = E._elbo_totals(self.eng, SET_TRIALS, self.config["method"] == "VB")
+            if self.eng.world > 1:
+                self.eng.allreduce_host(final)
+            self.runtime["elbo_final"] = float(final[0])
+            self.config["runtime"] = self.runtime
+
+    def _prior_w_v(self):
+        """Prior factor, w and v of the full-length trials under the current parameters."""
+        E.make_cholesky(self.dev_trials, self.params, self.config)
+        E.update_w(self.dev_trials, self.params, self.config)
+        E.update_v(self.dev_trials, self.params, self.config)
+
+    def _snapshot_initial(self):
+        # params["initial"] = deepcopy(params) (api.py:60): every key, the segment-length factors included.  The
+        # resident factor is downloaded for it when a window is set (one (L, window, rank) array); without a
+        # window it is every full-length factor: those are rebuilt on the host when somebody reads them
+        params = self.params
+        snapshot = {k: v for k, v in params.items() if k != "cholesky"}
+        chol = params["cholesky"]
+        if isinstance(chol, E._LazyPrior):
+            # no window: the full-length factors of the initial omega, factored on first access (engine._InitialPrior)
+            chol = chol.materialize() if self.config["window"] else E._InitialPrior(
+                chol._lengths, params["omega"], params["sigma"], params["rank"])
+        snapshot["cholesky"] = chol
+        params["initial"] = copy.deepcopy(snapshot)
 
     def _replicate_params(self):
         """Every rank must start from the same a, b, noise: keep rank 0's."""
@@ -327,32 +318,18 @@ class FitSession:
         return self
 
     def finish(self):
-        if self.missing is not None:
-            return self._finish_masked()
-        eng, params, config, echo = self.eng, self.params, self.config, self.echo
+        params, config, echo = self.params, self.config, self.echo
         try:
             if self.segs is not self.dev_trials:
-                eng.merge(SET_SEGMENTS)
-                if self.segs.detached:  # constrain_loading "svd": the trials kept their pre-rotation mu (core.py:407-408)
-                    eng.stash_mu(SET_TRIALS, restore=True)
-            E.make_cholesky(self.dev_trials, params, config)
-            E.update_w(self.dev_trials, params, config)
-            E.update_v(self.dev_trials, params, config)
+                self._segments_to_trials()
+            self._prior_w_v()
             if echo:
                 echo("Inferring")
             E.infer(self.dev_trials, params, config, echo=echo)
-            if self.track_elbo:  # the bound of the full-length trials under the final posterior, summed over the ranks
-                final = E._elbo_totals(eng, SET_TRIALS, config["method"] == "VB")
-                if eng.world > 1:
-                    eng.allreduce_host(final)
-                self.runtime["elbo_final"] = float(final[0])
-                config["runtime"] = self.runtime
+            self._after_inference()
             self.dev_trials.pull()
             if self.materialize_x:
-                for tr in self.trials:
-                    x = tr.get("x")
-                    if isinstance(x, np.ndarray) and not x.flags.writeable and x.size and all(st == 0 for st in x.strides):
-                        tr["x"] = np.ones(x.shape)
+                _ones_for_broadcast_x(self.trials)
             if isinstance(params["cholesky"], E._LazyPrior):
                 params["cholesky"] = params["cholesky"].materialize()
             if echo:
@@ -389,9 +366,6 @@ def fit(trials, n_factors, device=0, comm=None, verbose=True, track_elbo=False, 
     ``track_elbo``, no ``constrain_loading="svd"``, trial lengths multiples of ``window``; each is a ``ValueError``
     otherwise.  Every returned trial carries its ``missing`` array.  INTEGRATION.md, "Fit with missing observations").
     """
-    if missing is None:
-        return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, track_elbo=track_elbo,
-                          **kwargs).run().finish()
     return FitSession(trials, n_factors, device=device, comm=comm, verbose=verbose, track_elbo=track_elbo,
                       missing=missing, **kwargs).run().finish()
 

@@ -83,6 +83,7 @@ import numpy as np
 from . import engine as E
 from ._lib import ERR_STATE, VlgpError
 from .api import _extended, bind_priors
+from .util import _per_trial_entries
 
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
            "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
@@ -140,6 +141,30 @@ def _resident(trials, params, units, device, priors=True):
         if priors:
             bind_priors(eng, trials, dict(params))  # (a copy: the caller's params["cholesky"] stays as it is)
         yield eng
+
+
+def _zero_start(trials, L):
+    """The units of a held-out inference: the trials' y and x with ``mu = v = w = 0``."""
+    return [{"y": tr["y"], "x": tr.get("x"), **{k: np.zeros((tr["y"].shape[0], L)) for k in ("mu", "v", "w")}}
+            for tr in trials]
+
+
+def _replica_chunk(eng, n_iter, dmu_bound, vb, posterior=False, **which):
+    """One chunk of replicas of ``SET_TEST`` (``which``: ``Engine.replicate``'s ``groups=`` or ``held_out=``): made,
+    inferred, scored and freed.  Returns ``(sums, rate, n_failed, posterior)``, the posterior (``mu, v, w`` of the
+    replicas' rows) only on request."""
+    eng.replicate(SET_TEST, SET_REPLICAS, **which)
+    n_failed = eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
+    sums, rate = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
+    post = eng.download(SET_REPLICAS, ("mu", "v", "w")) if posterior else None
+    eng.free_units(SET_REPLICAS)
+    return sums, rate, n_failed, post
+
+
+def _per_trial(arr, lengths):
+    """A (rows, ...) array cut into one copy per trial."""
+    bounds = np.cumsum([0] + list(lengths))
+    return [arr[bounds[i]:bounds[i + 1]].copy() for i in range(len(lengths))]
 
 
 def _no_missing(trials, what):
@@ -263,8 +288,7 @@ def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, devic
     noise = np.array(params["noise"], dtype=float)
     lengths = [int(tr["y"].shape[0]) for tr in trials]
     rows = int(sum(lengths))
-    units = [{"y": tr["y"], "x": tr.get("x"), "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))}
-             for tr, T in zip(trials, lengths)]
+    units = _zero_start(trials, L)
     rate = np.empty((rows, len(channels)))
     sums = np.empty((len(channels), 4))
     n_failed = 0
@@ -276,12 +300,9 @@ def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, devic
             try:
                 for chunk in plan_chunks(groups, cap):
                     n = sum(len(g) for g in chunk)
-                    eng.replicate(SET_TEST, SET_REPLICAS, groups=chunk)
-                    n_failed += eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
-                    s, r = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
-                    eng.free_units(SET_REPLICAS)
-                    sums[done:done + n] = s
-                    rate[:, done:done + n] = r
+                    sums[done:done + n], rate[:, done:done + n], bad, _ = \
+                        _replica_chunk(eng, n_iter, dmu_bound, vb, groups=chunk)
+                    n_failed += bad
                     done += n
             except VlgpError as err:
                 if path == "batched" or not _is_refusal(err):
@@ -303,10 +324,9 @@ def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, devic
                 rate[:, done:done + len(g)] = r[:, g]
                 done += len(g)
     ll, ll_null, ny, bps = bits_per_spike(sums, rows, eng.gauss[channels])
-    bounds = np.cumsum([0] + lengths)
     return {
         "channels": channels,
-        "rate": [rate[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))],
+        "rate": _per_trial(rate, lengths),
         "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
         "n_failed": int(n_failed), "path": used,
     }
@@ -443,8 +463,7 @@ def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device,
     vb = config["method"] == "VB"
     lengths = [int(tr["y"].shape[0]) for tr in trials]
     rows, N = int(sum(lengths)), int(params["ydim"])
-    units = [{"y": tr["y"], "x": tr.get("x"), "mu": np.zeros((T, L)), "v": np.zeros((T, L)), "w": np.zeros((T, L))}
-             for tr, T in zip(trials, lengths)]
+    units = _zero_start(trials, L)
     n_rep = held_out.shape[0]
     sums = np.empty((n_rep, N, 4))
     rate = np.full((rows, N), np.nan)
@@ -457,33 +476,16 @@ def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device,
         cap = max(int(cap), 1)
         for k0 in range(0, n_rep, cap):
             chunk = held_out[k0:k0 + cap]
-            eng.replicate(SET_TEST, SET_REPLICAS, held_out=chunk)
-            n_failed += eng.estep(SET_REPLICAS, n_iter, config["dmu_bound"], vb)
-            s, r = eng.loglik(SET_REPLICAS, vb=vb, want_rate=True)
+            s, r, bad, got = _replica_chunk(eng, n_iter, config["dmu_bound"], vb, posterior=posterior, held_out=chunk)
+            n_failed += bad
             if posterior:
-                got = eng.download(SET_REPLICAS, ("mu", "v", "w"))
                 for key in post:
                     post[key][k0:k0 + len(chunk)] = got[key].reshape(len(chunk), rows, L)
-            eng.free_units(SET_REPLICAS)
             sums[k0:k0 + len(chunk)] = s
             mine = chunk.any(axis=0)
             rate[mine] = r[mine]
         gauss = eng.gauss.copy()
     return sums, rate, int(n_failed), post, gauss
-
-
-def _per_trial_entries(arrays, trials, what, dtype):
-    N = int(trials[0]["y"].shape[1])
-    if len(arrays) != len(trials):
-        raise ValueError("%s needs one array per trial" % what)
-    out = []
-    for arr, tr in zip(arrays, trials):
-        arr = np.asarray(arr)
-        if arr.shape != (tr["y"].shape[0], N) or not (arr.dtype == np.bool_ if dtype is bool
-                                                      else np.issubdtype(arr.dtype, np.integer)):
-            raise ValueError("%s: every trial needs a (T, %d) %s array" % (what, N, "bool" if dtype is bool else "integer"))
-        out.append(arr)
-    return out
 
 
 def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_iter=None, max_replicas=None, device=0):
@@ -503,7 +505,6 @@ def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_i
     ``speckled_bps``; ``n_failed``."""
     lengths = [int(tr["y"].shape[0]) for tr in trials]
     rows, N = int(sum(lengths)), int(params["ydim"])
-    bounds = np.cumsum([0] + lengths)
     if folds is None:
         F = entry_folds(rows, N, n_folds, seed)
         n_folds = int(n_folds)
@@ -517,8 +518,7 @@ def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_i
     held = np.stack([F == k for k in range(n_folds)])
     sums, rate, n_failed, _, gauss = _entries_out(trials, params, config, held, n_iter, max_replicas, device)
     out = entry_scores(sums, (F >= 0).sum(axis=0), gauss)
-    out.update(folds=[F[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))],
-               rate=[rate[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))], n_failed=n_failed)
+    out.update(folds=_per_trial(F, lengths), rate=_per_trial(rate, lengths), n_failed=n_failed)
     return out
 
 
@@ -532,12 +532,10 @@ def impute(trials, params, config, missing, n_iter=None, device=0):
     Returns a dict of per-trial lists: ``mu``, ``v``, ``w`` (T, L) and ``rate`` (T, N), the model's prediction at the
     missing entries (Gaussian: means) and NaN elsewhere; and ``n_failed``."""
     lengths = [int(tr["y"].shape[0]) for tr in trials]
-    bounds = np.cumsum([0] + lengths)
     held = np.concatenate(_per_trial_entries(missing, trials, "missing", bool), axis=0)[None]
     _, rate, n_failed, post, _ = _entries_out(trials, params, config, held, n_iter, 1, device, posterior=True)
-    cut = lambda arr: [arr[bounds[i]:bounds[i + 1]].copy() for i in range(len(trials))]  # noqa: E731
-    return {"mu": cut(post["mu"][0]), "v": cut(post["v"][0]), "w": cut(post["w"][0]), "rate": cut(rate),
-            "n_failed": n_failed}
+    return {"mu": _per_trial(post["mu"][0], lengths), "v": _per_trial(post["v"][0], lengths),
+            "w": _per_trial(post["w"][0], lengths), "rate": _per_trial(rate, lengths), "n_failed": n_failed}
 
 
 def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0):
@@ -574,6 +572,7 @@ def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0)
         eng.upload(SET_FORWARD, ahead)
         sums, rate = eng.loglik(SET_FORWARD, vb=vb, want_rate=True)
         gauss = eng.gauss.copy()
+    ahead_rows = [nf] * len(trials)
     rows = nf * len(trials)
     ll, ll_null, ny, bps = bits_per_spike(sums, rows, gauss)
     past = np.sum([np.sum(np.asarray(tr["y"][:T], dtype=float), axis=0) for tr, T in zip(trials, held_in)], axis=0) \
@@ -584,9 +583,8 @@ def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0)
         bps_past = np.where(known & (ny > 0), (ll - ll_null_past) / (ny * math.log(2.0)), np.nan)
         off = terms[:, :, 0] / np.maximum(terms[:, :, 1], np.finfo(float).tiny)
     return {
-        "mu_ahead": [mu_ext[i * nf:(i + 1) * nf].copy() for i in range(len(trials))],
-        "v_ahead": [v_ext[i * nf:(i + 1) * nf].copy() for i in range(len(trials))],
-        "rate": [rate[i * nf:(i + 1) * nf].copy() for i in range(len(trials))],
+        "mu_ahead": _per_trial(mu_ext, ahead_rows), "v_ahead": _per_trial(v_ext, ahead_rows),
+        "rate": _per_trial(rate, ahead_rows),
         "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
         "ll_null_past": ll_null_past, "bits_per_spike_past": bps_past,
         "fp_bps": co_bits_per_spike(ll, ll_null, ny), "fp_bps_past": co_bits_per_spike(ll, ll_null_past, ny),

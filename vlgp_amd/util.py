@@ -42,6 +42,22 @@ def cut_trials(trials, params, config):
     return np.array(segs, dtype=object)
 
 
+def _per_trial_entries(arrays, trials, what, dtype):
+    """``arrays`` as a list with one (T, N) array of ``dtype`` (bool, or int for any integer type) per trial, or a
+    ValueError that names ``what``."""
+    N = int(trials[0]["y"].shape[1])
+    if len(arrays) != len(trials):
+        raise ValueError("%s needs one array per trial" % what)
+    out = []
+    for arr, tr in zip(arrays, trials):
+        arr = np.asarray(arr)
+        if arr.shape != (tr["y"].shape[0], N) or not (arr.dtype == np.bool_ if dtype is bool
+                                                      else np.issubdtype(arr.dtype, np.integer)):
+            raise ValueError("%s: every trial needs a (T, %d) %s array" % (what, N, "bool" if dtype is bool else "integer"))
+        out.append(arr)
+    return out
+
+
 def save(result, path, ext="npy"):
     """Store a ``fit`` result (vlgp/util.py:181-190): one pickled object in ``.npy``, or the
     top-level keys as arrays in ``.npz``."""
