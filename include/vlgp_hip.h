@@ -118,10 +118,13 @@ int vlgp_free_units(vlgp_ctx* ctx, int set);
  * channel[k] out of its E-step: vlgp_estep on `dst` runs what it would run with a[:, channel[k]] = 0 for replica k,
  * bit for bit.  y and x (and x.b) are ALIASED to `src`; mu, v, w, dmu start as copies of src's.  `src` must be a plain
  * uploaded set (not a cut, no overlap stages).  While a replica set exists, vlgp_upload_units and vlgp_free_units on
- * `src` return VLGP_ERR_STATE.  A replicated set takes vlgp_estep (split E-step only: a configuration that kernel
- * family cannot run -- L > 10, N > 1024, long units at R above its limit, short units at effective rank > 32 -- is
- * VLGP_ERR_STATE, never another kernel), vlgp_download_units, vlgp_free_units and vlgp_loglik; every other entry point
- * refuses it with VLGP_ERR_STATE.  The same as vlgp_replicate_groups (below) with one channel per group. */
+ * `src` return VLGP_ERR_STATE, and so does a cut or a replicate call whose destination is `src`.
+ * WHICH ENTRY POINT TAKES WHICH KIND OF SET is one table, DESIGN.md 4.6 (csrc/api.hip holds it as data).  In short: a
+ * replicated set takes vlgp_estep (split E-step only: a configuration that kernel family cannot run -- L > 10, N > 1024,
+ * long units at R above its limit, short units at effective rank > 32 -- is VLGP_ERR_STATE, never another kernel),
+ * vlgp_download_units, vlgp_upload_units, vlgp_free_units and vlgp_loglik; a masked set of ONE replica
+ * (vlgp_replicate_masked) also takes the entry points a fit runs; every other entry point refuses a replicated set
+ * with VLGP_ERR_STATE.  The same as vlgp_replicate_groups (below) with one channel per group. */
 int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* channel);
 /* Speckled hold-out: replicas that leave single (row, channel) ENTRIES out -- the general form of vlgp_replicate_groups
  * (declared at the end of this header), whose groups are masks that are constant along the rows.  held_out is
@@ -152,7 +155,7 @@ int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* 
  * reason, with a Gaussian channel on the handle, on the loop-based kernels (P > 8, VLGP_MSTEP_GENERIC), beyond 10
  * latents and with more than one rank.  vlgp_elbo, vlgp_forecast, vlgp_project_units, cuts, merges, stashes and
  * overlaps refuse a masked fit set like every replicated set; a group-replica set and a masked set of several
- * replicas are refused by all of the above exactly as before. */
+ * replicas are refused by all of the above (the whole table: DESIGN.md 4.6). */
 int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint64_t* held_out);
 /* Plug-in rate and log-likelihood of the observations under the set's current posterior (mu, v):
  *   Poisson   rate = trunc_exp(a_n.mu_t + (b x)_tn + 1/2 (a_n^2).v_t)  (the E-step's rate; vb == 0 drops the v term)
@@ -166,7 +169,7 @@ int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint
  * beyond).  A set made by vlgp_replicate_masked: see there.  Sums cover this handle's units only (no reduction over ranks) and are bitwise reproducible (fixed-order
  * two-stage reduction, no atomics). */
 int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums);
-/* Terms of the variational lower bound of a plain set (uploaded or cut; a replicated set is VLGP_ERR_STATE) under its
+/* Terms of the variational lower bound of a set that is not replicated (VLGP_ERR_STATE otherwise) under its
  * current posterior (mu, v, w), the current parameters and the prior factors the set's lengths are bound to.
  *   row_sums (N, 4): per channel, with eta = a_n.mu_t + (b x)_tn and s = 1/2 (a_n^2).v_t (s = 0 when vb == 0),
  *     Poisson   {sum E_q log p, sum y, sum rate, sum y s},  E_q log p = y eta - trunc_exp(eta + s) - lgamma(y + 1)
@@ -192,7 +195,7 @@ int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell,
  * lengths[k]; G_ext holds the blocks (L, n_ext[k], R) back to back in the order of lengths: the rows of the factorisation
  * whose first lengths[k] rows are the prior of that length.  mu_ext, v_ext (sum over the units of their n_ext, L),
  * unit-major; fit_terms (M, L, 2) and n_failed may be NULL.  A pivot of H that is not positive and finite makes the task's
- * mu_ext, v_ext and fit_terms NaN and is counted in *n_failed.  A cut or replicated set, parameters not set or a length
+ * mu_ext, v_ext and fit_terms NaN and is counted in *n_failed.  A cut or replicated set (DESIGN.md 4.6), parameters not set or a length
  * without a prior: VLGP_ERR_STATE; a length that is not listed, n_ext < 1 or a null output: VLGP_ERR_ARG, the message
  * naming the offender, nothing changed.  Waits for a pending M-step and norms pass; changes no unit state, no parameter
  * and nothing vlgp_hstep_prepare built.  Fixed-order reductions, no atomics: the same bits on every run. */
@@ -219,7 +222,8 @@ int vlgp_clear_prior(vlgp_ctx* ctx);
 int vlgp_get_prior(vlgp_ctx* ctx, int T, double* G, int* rank_out);
 
 /* ---- E-step ----------------------------------------------------------- */
-/* core.update_w (vlgp/core.py:419-442).  This and vlgp_update_v take a masked fit set (vlgp_replicate_masked). */
+/* core.update_w (vlgp/core.py:419-442).  This and vlgp_update_v take a masked fit set (vlgp_replicate_masked), no other
+ * replicated set. */
 int vlgp_update_w(vlgp_ctx* ctx, int set);
 /* core.update_v (vlgp/core.py:445-471); vb == 0 is the reference's early
  * return for method != "VB". */
@@ -236,7 +240,7 @@ int vlgp_estep_wait(vlgp_ctx* ctx);
 /* core.mstep (vlgp/core.py:129-249) over the concatenation of all units of
  * the set.  With a communicator attached the sufficient statistics are
  * all-reduced over ranks once per Newton iteration.  A masked fit set (vlgp_replicate_masked, one replica): every
- * channel over its observed rows only; see there for its limits.  Other replicated sets: VLGP_ERR_STATE. */
+ * channel over its observed rows only; see there for its limits.  Other replicated sets: VLGP_ERR_STATE (DESIGN.md 4.6). */
 int vlgp_mstep(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, double eps,
                double learning_rate, double da_bound, double db_bound, int* n_failed);
 

@@ -176,10 +176,6 @@ def test_bad_groups_are_refused_and_the_handle_lives_on(V):
             with pytest.raises(V.VlgpError, match=r"status -1.*" + what):
                 eng.replicate(0, 2, groups=bad)
         eng.replicate(0, 2, groups=[[1, 3], [5]])
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.mstep(2, 2)
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.elbo(2)
         eng.estep(2, 2)
         sums, rate = eng.loglik(2, want_rate=True)
         assert sums.shape == (3, 4) and rate.shape == (400, 3) and np.all(np.isfinite(sums))

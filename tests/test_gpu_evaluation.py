@@ -127,36 +127,3 @@ def test_many_latents_take_the_sequential_path(V):
     assert relerr(got["ll"], want_ll) < STAGE
     with pytest.raises(V.VlgpError):
         V.evaluation.leave_one_out(trials, params, config, channels=[0], path="batched")
-
-
-def test_replicated_set_refuses_other_entry_points(V):
-    from vlgp_amd.api import bind_priors
-    from vlgp_amd.engine import Engine
-
-    trials, params, config = problem(seed=23, M=4, T=100, N=10)
-    L, N = params["zdim"], params["ydim"]
-    units = [{"y": t["y"], "x": None, "mu": np.zeros((t["y"].shape[0], L)), "v": None, "w": None} for t in trials]
-    with Engine(N, L, 1, 50) as eng:
-        eng.set_params(params["a"], params["b"][:1], params["noise"])
-        eng.upload(0, units)
-        bind_priors(eng, trials, dict(params))
-        eng.replicate(0, 2, [1, 3, 5])
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.mstep(2, 2)
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.update_w(2)
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.hstep_objective(2, 100, 1.0, [0], np.log(np.array([[1.0, 1e-2, 1e-4]])))
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.norms(2)
-        with pytest.raises(V.VlgpError, match="source of a replicated set"):
-            eng.free_units(0)
-        with pytest.raises(V.VlgpError, match="source of a replicated set"):
-            eng.upload(0, units)
-        eng.estep(2, 2)
-        got = eng.download(2, ("mu",))["mu"]
-        assert got.shape == (3 * sum(t["y"].shape[0] for t in trials), L)
-        sums, rate = eng.loglik(2, want_rate=True)
-        assert sums.shape == (3, 4) and rate.shape == (got.shape[0] // 3, 3)
-        eng.free_units(2)
-        eng.free_units(0)

@@ -302,40 +302,6 @@ def test_relaxed_entry_points_match_the_oracle_on_a_masked_fit_set(V, clean_env)
         assert e < STAGE, (k, e)
 
 
-def test_other_replicated_sets_are_still_refused(V, clean_env):
-    c, p = stage_problem()
-    T, L = 40, c["L"]
-    two = np.stack([make_mask("random30", c, seed=s) for s in (1, 2)])
-    logp = np.log(np.array([[1.0, 1e-2, 1e-4]]))
-    calls = {
-        "vlgp_update_w": lambda e: e.update_w(2), "vlgp_update_v": lambda e: e.update_v(2, True),
-        "vlgp_norms": lambda e: e.norms(2), "vlgp_norms_begin": lambda e: e.norms_begin(2),
-        "vlgp_apply_latent_map": lambda e: e.apply_latent_map(2, np.eye(L)),
-        "vlgp_latent_moments": lambda e: e.latent_moments(2),
-        "vlgp_hstep_prepare": lambda e: e.hstep_prepare(2, T), "vlgp_hstep_begin": lambda e: e.hstep_begin(2, T),
-        "vlgp_hstep_objective": lambda e: e.hstep_objective(2, T, 1.0, [1], logp),
-        "vlgp_mstep_begin": lambda e: e.mstep(2, 1),
-    }
-    with V.Engine(c["N"], L, 1, 50) as eng:
-        eng.set_params(p["a"], p["b"], np.ones(c["N"]))
-        eng.set_prior(T, O.build_prior([T], p["omega"], p["sigma"], 50)[T])
-        eng.upload(0, units_of(p))
-        for how, kw in (("groups", dict(groups=[[0, 3]])), ("two masks", dict(held_out=two))):
-            eng.replicate(0, 2, **kw)
-            for name, call in calls.items():
-                with pytest.raises(V.VlgpError, match="%s refuses a replicated set" % name):
-                    call(eng)
-            eng.free_units(2)
-        # ... and what stays refused for a masked fit set
-        eng.replicate(0, 2, held_out=two[:1])
-        for name, call in (("vlgp_elbo", lambda e: e.elbo(2)), ("vlgp_project_units",
-                           lambda e: e.project_latent(2, np.zeros((c["N"], L)), np.zeros(L))),
-                           ("vlgp_stash_mu", lambda e: e.stash_mu(2)),
-                           ("vlgp_cut_units", lambda e: e.cut(2, 1, np.array([0]), 20))):
-            with pytest.raises(V.VlgpError, match="%s refuses a replicated set" % name):
-                call(eng)
-
-
 # ------------------------------------------------------------------ 5. the whole fit against the restatement
 @pytest.mark.parametrize("constrain_latent", [False, "both"])
 def test_fit_with_missing_follows_the_restatement(V, clean_env, constrain_latent):

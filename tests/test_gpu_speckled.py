@@ -240,19 +240,7 @@ def test_refusals_leave_a_working_handle(V):
         assert 2 not in eng.sets
         with pytest.raises(V.VlgpError, match="status -1"):
             eng.replicate(0, 2, held_out=held[:0])  # n_rep < 1
-        eng.cut(0, 1, np.arange(0, rows, 50), 50)
-        with pytest.raises(V.VlgpError, match="status -3.*plain uploaded set"):
-            eng.replicate(1, 2, held_out=held)  # a cut source
-        eng.free_units(1)
-        eng.replicate(0, 2, held_out=held)
-        with pytest.raises(V.VlgpError, match="status -3.*plain uploaded set"):
-            eng.replicate(2, 3, held_out=np.zeros((1, 2 * rows, N), dtype=bool))  # a replicated source
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.mstep(2, 2)
-        with pytest.raises(V.VlgpError, match="replicated"):
-            eng.elbo(2)
-        eng.free_units(2)
-        both = held.copy()
+        both = held.copy()  # (which sets the replicate calls and the other entry points take: test_gpu_set_kinds.py)
         both[1, 3, 4] = both[0, 3, 4] = True  # one entry held out twice
         eng.replicate(0, 2, held_out=both)
         with pytest.raises(V.VlgpError, match="status -1.*overlap"):

@@ -123,23 +123,90 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     return us;
 }
 
-// a replicated set (vlgp_replicate_units) takes the E-step, downloads, vlgp_loglik and vlgp_free_units; everything else
-// would read its aliased y / x with the replicas' row count, or mix the replicas' excluded channels back in
-#define NOT_REPLICATED(ctx, us, what)                                                                                \
-    do {                                                                                                             \
-        if ((us)->rep_src >= 0)                                                                                      \
-            return vlgp_fail(ctx, VLGP_ERR_STATE, "%s refuses a replicated set (leave-one-out replicas of set %d: "    \
-                             "E-step, download, loglik and free only)", what, (us)->rep_src);                        \
-    } while (0)
-// ... but a MASKED FIT SET -- vlgp_replicate_masked with one replica: the source's rows, units and y / x, its own mu, v, w,
-// dmu, one mask bit per entry of y -- is a set the fit runs on.  The entry points that read mu, v, w, dmu alone (norms,
-// latent map, moments, H-step) take it as any set; update_w / update_v go through the split E-step's masked row passes;
-// the M-step has masked kernels (mstep.hip).  Group replicas and masked sets of several replicas stay refused as above.
-static inline bool masked_fit_set(const UnitSet* us) { return us->rep_src >= 0 && us->rep_by_row && us->n_rep == 1; }
-#define NOT_REPLICATED_BUT_FIT(ctx, us, what)                \
-    do {                                                     \
-        if (!masked_fit_set(us)) NOT_REPLICATED(ctx, us, what); \
-    } while (0)
+// ---- which entry point takes which kind of set -----------------------------------------------------
+// ONE table: X(entry point, kinds it takes, what it says to a refused set that is not replicated).  A refused replicated
+// set is told "<entry point> refuses a replicated set (...)"; the replicate calls say their text to every refused set.
+// SET_FIT = not replicated, or a masked set of one replica: that one is the source's rows, units and y / x with its own
+// mu, v, w, dmu and one mask bit per entry of y, so the entry points that read mu, v, w, dmu alone (norms, latent map,
+// moments, H-step) take it as any set, update_w / update_v go through the split E-step's masked row passes and the
+// M-step has masked kernels (mstep.hip).  Everything else would read a replicated set's aliased y / x with the replicas'
+// row count, or mix the left-out channels and entries back in.  Without SET_SOURCE a set that is the source of replicas
+// is refused as well: its rows must stay while replicas alias them.
+#define NOT_REPLICATED (SET_PLAIN | SET_TILING | SET_COPIED | SET_SOURCE)
+#define SET_ADMISSION(X)                                                                                              \
+    X(vlgp_estep, SET_ANY, nullptr)                                                                                   \
+    X(vlgp_download_units, SET_ANY, nullptr)                                                                          \
+    X(vlgp_free_units, SET_ANY & ~SET_SOURCE, nullptr)                                                                \
+    X(vlgp_upload_units, SET_ANY & ~SET_SOURCE, nullptr)                                                              \
+    X(vlgp_loglik, SET_ANY & ~SET_COPIED, "vlgp_loglik on a copied cut: merge it and score the source set")           \
+    X(vlgp_update_w, SET_FIT | SET_SOURCE, nullptr)                                                                   \
+    X(vlgp_update_v, SET_FIT | SET_SOURCE, nullptr)                                                                   \
+    X(vlgp_mstep_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \
+    X(vlgp_hstep_objective, SET_FIT | SET_SOURCE, nullptr)                                                            \
+    X(vlgp_hstep_prepare, SET_FIT | SET_SOURCE, nullptr)                                                              \
+    X(vlgp_hstep_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \
+    X(vlgp_apply_latent_map, SET_FIT | SET_SOURCE, nullptr)                                                           \
+    X(vlgp_norms, SET_FIT | SET_SOURCE, nullptr)                                                                      \
+    X(vlgp_norms_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \
+    X(vlgp_latent_moments, SET_FIT | SET_SOURCE, nullptr)                                                             \
+    X(vlgp_elbo, NOT_REPLICATED, nullptr)                                                                             \
+    X(vlgp_forecast, NOT_REPLICATED, nullptr) /* (a cut is refused once its priors are bound: see there) */           \
+    X(vlgp_stash_mu, NOT_REPLICATED, nullptr)                                                                         \
+    X(vlgp_set_overlaps, NOT_REPLICATED, nullptr) /* (and equal-length units that are no tiling cut: see there) */    \
+    X(vlgp_unshare_mu, NOT_REPLICATED, nullptr)                                                                       \
+    X(vlgp_project_units, NOT_REPLICATED, nullptr) /* (a tiling cut is refused after the arguments: see there) */     \
+    X(vlgp_merge_units, SET_TILING | SET_COPIED | SET_SOURCE, "set %d is not a cut")                                  \
+    X(vlgp_cut_units, SET_PLAIN | SET_COPIED | SET_SOURCE, "cannot cut a set that is itself a cut") /* the source */  \
+    X(vlgp_replicate, SET_PLAIN | SET_SOURCE,                                                                         \
+      "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)") /* the source, _groups / _masked */ \
+    X(destination, SET_ANY & ~SET_SOURCE, nullptr) /* of vlgp_cut_units and the replicate calls: any set, or none yet */
+struct Admission { const char* what; unsigned kinds; const char* refusal; };
+#define X(name, kinds, refusal) static const Admission admit_##name = {#name, kinds, refusal};
+SET_ADMISSION(X)
+#undef X
+
+static int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a) {
+    if (us->is_source() && !(a.kinds & SET_SOURCE))
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", set);
+    if (us->is(a.kinds)) return VLGP_OK;
+    if (us->is(SET_REPLICATED) && &a != &admit_vlgp_replicate)
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "%s refuses a replicated set (leave-one-out replicas of set %d: "
+                         "E-step, download, loglik and free only)", a.what, us->rep.src);
+    return vlgp_fail(ctx, VLGP_ERR_STATE, a.refusal, set);
+}
+
+// How a set-taking entry point opens: what it waits for and invalidates, in this order, then the set and its admission.
+enum : unsigned {
+    OPEN_COLLECT = 1,   // host-side ranks of a lazy prior build (vlgp_prior_collect)
+    OPEN_STALE = 2,     // unit state changes: the cached H-step moments are stale
+    OPEN_JOIN = 4,      // vlgp_join_m: the M-step lane and a queued norms pass, write_epoch bumped
+    OPEN_WAIT = 8,      // the same two waits without the bump: the call only reads (what vlgp_hstep_prepare built stays)
+    OPEN_PARAMS = 16,   // parameters must be set
+    OPEN_DEVICE = 32,   // hipSetDevice
+    OPEN_EMPTY = 64,    // the slot may be empty (upload, free)
+};
+#define NEED_PARAMS(ctx) \
+    if (!(ctx)->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)")
+static int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a) {
+    NEED_CTX(ctx);
+    if (how & OPEN_COLLECT) CHK(vlgp_prior_collect(ctx));
+    if (how & OPEN_STALE) ctx->hmom_us = nullptr;
+    if (how & OPEN_JOIN) CHK(vlgp_join_m(ctx));
+    if (how & OPEN_WAIT) {
+        CHK(wait_norms(ctx));
+        if (ctx->m_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_m_done));
+    }
+    if (how & OPEN_PARAMS) NEED_PARAMS(ctx);
+    if (how & OPEN_DEVICE) HIPCHK(ctx, hipSetDevice(ctx->dev));
+    if (!(*out = vlgp_get_set(ctx, set, !(how & OPEN_EMPTY)))) return VLGP_ERR_ARG;
+    return a ? admit(ctx, set, *out, *a) : VLGP_OK;  // (null: the entry point checks its arguments first, then admits)
+}
+// ... and one that makes set dst out of set src (a cut, replicas): both slots, then the call's own arguments
+static int open_pair(vlgp_ctx* ctx, int src, int dst, bool bad_args, const char* bad, UnitSet** s, UnitSet** d) {
+    CHK(open_set(ctx, src, OPEN_STALE | OPEN_JOIN | OPEN_DEVICE, s, nullptr));
+    if (!(*d = vlgp_get_set(ctx, dst, false))) return VLGP_ERR_ARG;
+    return bad_args ? vlgp_fail(ctx, VLGP_ERR_ARG, "%s", bad) : VLGP_OK;
+}
 
 // ---- profiling -----------------------------------------------------------
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st) {
@@ -506,10 +573,10 @@ static void free_set(vlgp_ctx* ctx, UnitSet& us) {
     if (!us.valid) return;
     (void)hipStreamSynchronize(ctx->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
-    if (us.rep_src >= 0) {  // replicas: y, x, xb are the source's
-        fr(us.mu); fr(us.v); fr(us.w); fr(us.d_rep_ch); fr(us.d_rep_pair); fr(us.d_rep_mask); fr(us.d_rep_wconst); fr(us.d_rep_nobs);
-        fr(us.d_rep_xa);
-        ctx->sets[us.rep_src].rep_users--;
+    if (us.is(SET_REPLICATED)) {  // replicas: y, x, xb are the source's
+        Replicas& r = us.rep;
+        fr(us.mu); fr(us.v); fr(us.w); fr(r.d_ch); fr(r.d_pair); fr(r.d_mask); fr(r.d_wconst); fr(r.d_nobs); fr(r.d_xa);
+        ctx->sets[r.src].rep_users--;
         us.d_xb = nullptr;
     } else if (!us.alias) {
         fr(us.y); fr(us.x); fr(us.mu); fr(us.v); fr(us.w);
@@ -517,6 +584,13 @@ static void free_set(vlgp_ctx* ctx, UnitSet& us) {
     fr(us.dmu); fr(us.d_off); fr(us.d_src_start); fr(us.d_unit_prior); fr(us.d_xb); fr(us.d_scratch); fr(us.d_mu_stash);
     fr(us.d_links);
     us = UnitSet();
+}
+
+// ... and, first, the tiling cuts that share its rows
+static void free_with_tiling_cuts(vlgp_ctx* ctx, int set) {
+    for (auto& other : ctx->sets)
+        if (other.valid && other.is(SET_TILING) && other.parent == set) free_set(ctx, other);
+    free_set(ctx, ctx->sets[set]);
 }
 
 extern "C" int vlgp_create(int device, int N, int L, int P, int R, const uint8_t* gauss_mask, vlgp_ctx** out) {
@@ -611,7 +685,7 @@ extern "C" int vlgp_destroy(vlgp_ctx* ctx) {
     // aliased sets first, then owners
     for (int pass = 0; pass < 2; ++pass)
         for (auto& us : ctx->sets)
-            if (us.valid && (pass == 1 || us.alias)) free_set(ctx, us);
+            if (us.valid && (pass == 1 || us.is(SET_TILING))) free_set(ctx, us);
     free_priors(ctx);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(ctx->d_gauss); fr(ctx->d_a); fr(ctx->d_b); fr(ctx->d_noise); fr(ctx->d_da); fr(ctx->d_db);
@@ -691,20 +765,12 @@ static int up(vlgp_ctx* ctx, double** dst, const double* src, int64_t n) {
 
 extern "C" int vlgp_upload_units(vlgp_ctx* ctx, int set, int M, const int64_t* offsets, const double* y,
                                  const double* x, const double* mu, const double* v, const double* w) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;  // unit state changes: cached H-step moments are stale
-    CHK(vlgp_join_m(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, false);
-    if (!us) return VLGP_ERR_ARG;
-    if (us->rep_users > 0)
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", set);
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_STALE | OPEN_JOIN | OPEN_DEVICE | OPEN_EMPTY, &us, &admit_vlgp_upload_units));
     if (M < 1 || !offsets || !y) return vlgp_fail(ctx, VLGP_ERR_ARG, "upload needs M >= 1, offsets and y");
     if (offsets[0] != 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "offsets[0] must be 0");
     if (!x && ctx->P != 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "x == NULL (all ones) requires xdim == 1");
-    for (auto& other : ctx->sets)
-        if (other.valid && other.alias && other.parent == set) free_set(ctx, other);
-    free_set(ctx, *us);
+    free_with_tiling_cuts(ctx, set);
     CHK(set_offsets(ctx, *us, M, offsets));
     const int64_t rows = us->rows;
     CHK(up(ctx, &us->y, y, rows * ctx->N));
@@ -720,18 +786,10 @@ extern "C" int vlgp_upload_units(vlgp_ctx* ctx, int set, int M, const int64_t* o
 }
 
 extern "C" int vlgp_cut_units(vlgp_ctx* ctx, int src, int dst, int M_dst, const int64_t* start, int window) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;  // unit state changes: cached H-step moments are stale
-    CHK(vlgp_join_m(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* s = vlgp_get_set(ctx, src, true);
-    UnitSet* d = vlgp_get_set(ctx, dst, false);
-    if (!s || !d) return VLGP_ERR_ARG;
-    if (src == dst || M_dst < 1 || window < 1 || !start) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad cut arguments");
-    if (s->alias) return vlgp_fail(ctx, VLGP_ERR_STATE, "cannot cut a set that is itself a cut");
-    NOT_REPLICATED(ctx, s, "vlgp_cut_units");
-    if (d->rep_users > 0)
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", dst);
+    UnitSet *s = nullptr, *d = nullptr;
+    CHK(open_pair(ctx, src, dst, src == dst || M_dst < 1 || window < 1 || !start, "bad cut arguments", &s, &d));
+    CHK(admit(ctx, src, s, admit_vlgp_cut_units));
+    CHK(admit(ctx, dst, d, admit_destination));
     bool exact = (int64_t)M_dst * window == s->rows;
     for (int k = 0; k < M_dst; ++k) {
         if (start[k] < 0 || start[k] + window > s->rows)
@@ -767,25 +825,17 @@ extern "C" int vlgp_cut_units(vlgp_ctx* ctx, int src, int dst, int M_dst, const 
 }
 
 extern "C" int vlgp_merge_units(vlgp_ctx* ctx, int cut_set) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;  // unit state changes: cached H-step moments are stale
-    CHK(vlgp_join_m(ctx));
-    UnitSet* c = vlgp_get_set(ctx, cut_set, true);
-    if (!c) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, c, "vlgp_merge_units");
-    if (c->parent < 0) return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is not a cut", cut_set);
-    if (c->alias) return VLGP_OK;
+    UnitSet* c = nullptr;
+    CHK(open_set(ctx, cut_set, OPEN_STALE | OPEN_JOIN, &c, &admit_vlgp_merge_units));
+    if (c->is(SET_TILING)) return VLGP_OK;
     UnitSet* p = vlgp_get_set(ctx, c->parent, true);
     if (!p) return VLGP_ERR_STATE;
     return launch_scatter(ctx, *c, *p, (int)(c->off[1] - c->off[0]));
 }
 
 extern "C" int vlgp_stash_mu(vlgp_ctx* ctx, int set, int restore) {
-    NEED_CTX(ctx);
-    CHK(vlgp_join_m(ctx));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_stash_mu");
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_JOIN, &us, &admit_vlgp_stash_mu));
     const size_t nb = (size_t)us->rows * ctx->L * sizeof(double);
     if (!restore) {
         if (!us->d_mu_stash) HIPCHK(ctx, hipMalloc(&us->d_mu_stash, nb));
@@ -799,10 +849,8 @@ extern "C" int vlgp_stash_mu(vlgp_ctx* ctx, int set, int restore) {
 }
 
 extern "C" int vlgp_download_units(vlgp_ctx* ctx, int set, double* mu, double* v, double* w, double* dmu) {
-    NEED_CTX(ctx);
-    CHK(vlgp_join_m(ctx));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_JOIN, &us, &admit_vlgp_download_units));
     const size_t nb = (size_t)us->rows * ctx->L * sizeof(double);
     if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, us->mu, nb, hipMemcpyDeviceToHost, ctx->stream));
     if (v) HIPCHK(ctx, hipMemcpyAsync(v, us->v, nb, hipMemcpyDeviceToHost, ctx->stream));
@@ -813,26 +861,18 @@ extern "C" int vlgp_download_units(vlgp_ctx* ctx, int set, double* mu, double* v
 }
 
 extern "C" int vlgp_free_units(vlgp_ctx* ctx, int set) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;  // unit state changes: cached H-step moments are stale
-    CHK(vlgp_join_m(ctx));
-    UnitSet* us = vlgp_get_set(ctx, set, false);
-    if (!us) return VLGP_ERR_ARG;
-    if (us->rep_users > 0)
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", set);
-    for (auto& other : ctx->sets)
-        if (other.valid && other.alias && other.parent == set) free_set(ctx, other);
-    free_set(ctx, *us);
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_STALE | OPEN_JOIN | OPEN_EMPTY, &us, &admit_vlgp_free_units));
+    free_with_tiling_cuts(ctx, set);
     return VLGP_OK;
 }
 
 // ---- leave-group-out replicas and held-out likelihood --------------------------
 // what every replicate call checks of its two sets once its own arguments are sound
 static int replicas_check(vlgp_ctx* ctx, int src, int dst, int n_rep, const UnitSet* s, const UnitSet* d) {
-    if (s->rep_src >= 0 || s->parent >= 0 || s->alias || !s->stage_start.empty())
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)", src);
-    if (d->rep_users > 0)
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", dst);
+    CHK(admit(ctx, src, s, admit_vlgp_replicate));
+    if (!s->stage_start.empty()) return vlgp_fail(ctx, VLGP_ERR_STATE, admit_vlgp_replicate.refusal, src);
+    CHK(admit(ctx, dst, d, admit_destination));
     if ((int64_t)n_rep * s->M > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "too many replicated units");
     return VLGP_OK;
 }
@@ -841,9 +881,7 @@ static int replicas_check(vlgp_ctx* ctx, int src, int dst, int n_rep, const Unit
 // (enqueued; the caller adds its tables and synchronises).  From `valid` on free_set releases whatever was allocated,
 // should a later step fail.
 static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s, UnitSet* d) {
-    for (auto& other : ctx->sets)
-        if (other.valid && other.alias && other.parent == dst) free_set(ctx, other);
-    free_set(ctx, *d);
+    free_with_tiling_cuts(ctx, dst);
     const int Ms = s->M, L = ctx->L;
     const int64_t rs = s->rows;
     std::vector<int64_t> off((size_t)n_rep * Ms + 1);
@@ -851,10 +889,10 @@ static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s,
         for (int m = 0; m < Ms; ++m) off[(size_t)k * Ms + m] = k * rs + s->off[m];
     off[(size_t)n_rep * Ms] = n_rep * rs;
     CHK(set_offsets(ctx, *d, n_rep * Ms, off.data()));
-    d->rep_src = src;
-    d->n_rep = n_rep;
-    d->rows_src = rs;
-    d->rep_nw = (ctx->N + 63) / 64;
+    d->rep.src = src;
+    d->rep.n = n_rep;
+    d->rep.rows_src = rs;
+    d->rep.nw = (ctx->N + 63) / 64;
     d->x_ones = s->x_ones;
     d->y = s->y;  // aliased: a copy per replica would be rows x N doubles each
     d->x = s->x;
@@ -865,7 +903,7 @@ static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s,
     CHK(dev_alloc(ctx, &d->v, n_rep * rs * L, false));
     CHK(dev_alloc(ctx, &d->w, n_rep * rs * L, false));
     CHK(dev_alloc(ctx, &d->dmu, n_rep * rs * L, false));
-    HIPCHK(ctx, hipMalloc(&d->d_rep_xa, sizeof(d->rep_xh)));
+    HIPCHK(ctx, hipMalloc(&d->rep.d_xa, sizeof(d->rep.xh)));
     for (int k = 0; k < n_rep; ++k) {
         const int64_t o = k * rs * L;
         HIPCHK(ctx, hipMemcpyAsync(d->mu + o, s->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
@@ -878,15 +916,9 @@ static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s,
 
 extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* group_start,
                                      const int* channel) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;
-    CHK(vlgp_join_m(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* s = vlgp_get_set(ctx, src, true);
-    UnitSet* d = vlgp_get_set(ctx, dst, false);
-    if (!s || !d) return VLGP_ERR_ARG;
-    if (src == dst || n_rep < 1 || !channel || !group_start || group_start[0] != 0)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "bad replicate arguments");
+    UnitSet *s = nullptr, *d = nullptr;
+    CHK(open_pair(ctx, src, dst, src == dst || n_rep < 1 || !channel || !group_start || group_start[0] != 0,
+                  "bad replicate arguments", &s, &d));
     // the groups as bit masks (one bit per channel), the pairs' replicas: every argument is checked before any state moves
     const int nw = (ctx->N + 63) / 64;
     std::vector<unsigned long long> mask((size_t)n_rep * nw, 0ull);
@@ -908,15 +940,15 @@ extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep,
     const int n_pairs = group_start[n_rep];
     CHK(replicas_check(ctx, src, dst, n_rep, s, d));
     CHK(replicas_make(ctx, src, dst, n_rep, s, d));
-    d->n_pairs = n_pairs;
-    d->rep_ch.assign(channel, channel + n_pairs);
-    HIPCHK(ctx, hipMalloc(&d->d_rep_ch, sizeof(int) * n_pairs));
-    HIPCHK(ctx, hipMalloc(&d->d_rep_pair, sizeof(int) * n_pairs));
-    HIPCHK(ctx, hipMalloc(&d->d_rep_mask, sizeof(unsigned long long) * mask.size()));
-    HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * 16 * n_rep));
-    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_ch, channel, sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_pair, pair_rep.data(), sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_mask, mask.data(), sizeof(unsigned long long) * mask.size(), hipMemcpyHostToDevice,
+    Replicas& r = d->rep;
+    r.n_pairs = n_pairs;
+    HIPCHK(ctx, hipMalloc(&r.d_ch, sizeof(int) * n_pairs));
+    HIPCHK(ctx, hipMalloc(&r.d_pair, sizeof(int) * n_pairs));
+    HIPCHK(ctx, hipMalloc(&r.d_mask, sizeof(unsigned long long) * mask.size()));
+    HIPCHK(ctx, hipMalloc(&r.d_wconst, sizeof(double) * 16 * n_rep));
+    HIPCHK(ctx, hipMemcpyAsync(r.d_ch, channel, sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(r.d_pair, pair_rep.data(), sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(r.d_mask, mask.data(), sizeof(unsigned long long) * mask.size(), hipMemcpyHostToDevice,
                                ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the channel list is the caller's again, the host tables may go)
     return VLGP_OK;
@@ -925,14 +957,8 @@ extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep,
 // Speckled hold-out: replica k leaves out the entries (row, n) whose bit is set in held_out[(k rows_src + row) nw + (n >> 6)].
 // The mask goes to the device as the caller packed it -- (n_rep rows_src, nw) is the row order of the replicated set.
 extern "C" int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint64_t* held_out) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;
-    CHK(vlgp_join_m(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* s = vlgp_get_set(ctx, src, true);
-    UnitSet* d = vlgp_get_set(ctx, dst, false);
-    if (!s || !d) return VLGP_ERR_ARG;
-    if (src == dst || n_rep < 1 || !held_out) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad replicate arguments");
+    UnitSet *s = nullptr, *d = nullptr;
+    CHK(open_pair(ctx, src, dst, src == dst || n_rep < 1 || !held_out, "bad replicate arguments", &s, &d));
     CHK(replicas_check(ctx, src, dst, n_rep, s, d));
     // no bit at a channel >= N; whether two replicas hold the same entry out (vlgp_loglik then writes no rate)
     const int N = ctx->N, nw = (N + 63) / 64;
@@ -953,22 +979,22 @@ extern "C" int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep,
             }
         }
     CHK(replicas_make(ctx, src, dst, n_rep, s, d));
-    d->rep_by_row = true;
-    d->rep_overlap = overlap;
-    d->n_pairs = 0;
+    Replicas& rp = d->rep;
+    rp.by_row = true;
+    rp.overlap = overlap;
     const size_t words = (size_t)n_rep * rs * nw;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "mask words are 64 bits");
-    HIPCHK(ctx, hipMalloc(&d->d_rep_mask, sizeof(uint64_t) * words));
-    if (ctx->n_gauss > 0) HIPCHK(ctx, hipMalloc(&d->d_rep_wconst, sizeof(double) * (size_t)n_rep * rs * ctx->L));
-    HIPCHK(ctx, hipMemcpyAsync(d->d_rep_mask, held_out, sizeof(uint64_t) * words, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMalloc(&rp.d_mask, sizeof(uint64_t) * words));
+    if (ctx->n_gauss > 0) HIPCHK(ctx, hipMalloc(&rp.d_wconst, sizeof(double) * (size_t)n_rep * rs * ctx->L));
+    HIPCHK(ctx, hipMemcpyAsync(rp.d_mask, held_out, sizeof(uint64_t) * words, hipMemcpyHostToDevice, ctx->stream));
     std::vector<double> nobs;  // one replica: a masked fit set, whose M-step divides by the observed rows of each channel
     if (n_rep == 1) {
         nobs.assign((size_t)N, (double)rs);
         for (int64_t r = 0; r < rs; ++r)
             for (int n = 0; n < N; ++n)
                 if ((held_out[(size_t)r * nw + (n >> 6)] >> (n & 63)) & 1ull) nobs[n] -= 1.0;
-        HIPCHK(ctx, hipMalloc(&d->d_rep_nobs, sizeof(double) * (size_t)N));
-        HIPCHK(ctx, hipMemcpyAsync(d->d_rep_nobs, nobs.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMalloc(&rp.d_nobs, sizeof(double) * (size_t)N));
+        HIPCHK(ctx, hipMemcpyAsync(rp.d_nobs, nobs.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the mask is the caller's again)
     return VLGP_OK;
@@ -982,27 +1008,21 @@ extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, 
 }
 
 extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums) {
-    NEED_CTX(ctx);
-    CHK(vlgp_join_m(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
     if (!sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik needs sums");
-    if (us->parent >= 0 && !us->alias)
-        return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on a copied cut: merge it and score the source set");
-    const bool rep = us->rep_src >= 0, by_row = rep && us->rep_by_row;
-    if (by_row && rate && us->rep_overlap)
+    CHK(admit(ctx, set, us, admit_vlgp_loglik));
+    const bool by_row = us->is(SET_BY_ROW);
+    if (by_row && rate && us->rep.overlap)
         return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: the masks of set %d overlap (an entry is held out by more than one "
                          "replica): no rate, sums only", set);
-    UnitSet& rows_of = rep ? ctx->sets[us->rep_src] : *us;  // the y / x rows
+    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
     if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
-    const int slots = by_row ? us->n_rep * ctx->N : (rep ? us->n_pairs : ctx->N);
-    const int64_t n_rate = by_row ? us->rows_src * ctx->N : (rep ? us->rows_src * us->n_pairs : us->rows * ctx->N);
-    const int64_t o_sums = rate ? n_rate : 0;
+    const LoglikShape S = vlgp_loglik_shape(ctx, *us);
+    const int64_t slots = S.slots, n_rate = S.n_rate, o_sums = rate ? n_rate : 0;
     double* d_rate = nullptr;
     double* d_out = nullptr;
-    HIPCHK(ctx, hipMalloc(&d_out, sizeof(double) * (size_t)(o_sums + 4 * (int64_t)slots)));
+    HIPCHK(ctx, hipMalloc(&d_out, sizeof(double) * (size_t)(o_sums + 4 * slots)));
     if (rate) d_rate = d_out;
     int rc = VLGP_OK;
     if (by_row && rate &&  // NaN (every byte 0xff) where no replica holds the entry out
@@ -1024,17 +1044,10 @@ extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double*
 // ---- variational lower bound -----------------------------------------------------
 // what vlgp_elbo and vlgp_forecast do first: a plain set with parameters, xb and its priors bound, nothing pending.  The
 // waits of vlgp_join_m without its epoch bump: both calls only read, so what vlgp_hstep_prepare built stays valid
-static int open_posterior(vlgp_ctx* ctx, int set, const char* what, UnitSet** out) {
-    CHK(vlgp_prior_collect(ctx));
-    CHK(wait_norms(ctx));
-    if (ctx->m_pending) HIPCHK(ctx, hipEventSynchronize(ctx->ev_m_done));
-    if (!ctx->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)");
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = *out = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, what);
-    if (!us->x_ones) CHK(vlgp_refresh_xb(ctx, *us));
-    return vlgp_bind_priors(ctx, *us);
+static int open_posterior(vlgp_ctx* ctx, int set, const Admission& a, UnitSet** out) {
+    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, out, &a));
+    if (!(*out)->x_ones) CHK(vlgp_refresh_xb(ctx, **out));
+    return vlgp_bind_priors(ctx, **out);
 }
 
 // the largest effective rank among the set's lengths: it sizes the LDS of the (unit, latent) kernels
@@ -1061,9 +1074,8 @@ static hipError_t count_flags(vlgp_ctx* ctx, const int* d_flag, int64_t tasks, i
 
 extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms,
                          int* n_failed) {
-    NEED_CTX(ctx);
     UnitSet* us = nullptr;
-    CHK(open_posterior(ctx, set, "vlgp_elbo", &us));
+    CHK(open_posterior(ctx, set, admit_vlgp_elbo, &us));
     if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
     if (n_failed) *n_failed = 0;
     const int rp = set_rank_max(ctx, *us);
@@ -1095,10 +1107,9 @@ extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, doubl
 // ---- forward prediction ------------------------------------------------------------
 extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
                              const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed) {
-    NEED_CTX(ctx);
     UnitSet* us = nullptr;
-    CHK(open_posterior(ctx, set, "vlgp_forecast", &us));
-    if (us->parent >= 0) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_forecast refuses a cut set (set %d is cut from set %d)", set, us->parent);
+    CHK(open_posterior(ctx, set, admit_vlgp_forecast, &us));
+    if (us->is(SET_TILING | SET_COPIED)) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_forecast refuses a cut set (set %d is cut from set %d)", set, us->parent);
     if (n_lengths < 1 || !lengths || !n_ext || !G_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs lengths, n_ext and G_ext");
     if (!mu_ext || !v_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs mu_ext and v_ext");
     const int N = ctx->N, L = ctx->L, R = ctx->R, M = us->M;
@@ -1388,31 +1399,16 @@ static int end_count(vlgp_ctx* ctx, int* n_failed) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return VLGP_OK;
 }
-#define NEED_PARAMS(ctx) \
-    if (!(ctx)->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)")
 
 extern "C" int vlgp_update_w(vlgp_ctx* ctx, int set) {
-    NEED_CTX(ctx);
-    CHK(vlgp_prior_collect(ctx));
-    ctx->hmom_us = nullptr;  // unit state changes: cached H-step moments are stale
-    CHK(vlgp_join_m(ctx));
-    NEED_PARAMS(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_update_w");
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_STALE | OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_update_w));
     return launch_estep(ctx, *us, EM_W, 0, 0.0, 0);
 }
 
 extern "C" int vlgp_update_v(vlgp_ctx* ctx, int set, int vb, int* n_failed) {
-    NEED_CTX(ctx);
-    CHK(vlgp_prior_collect(ctx));
-    CHK(vlgp_join_m(ctx));
-    NEED_PARAMS(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_update_v");
+    UnitSet* us = nullptr;  // (no OPEN_STALE: v is not among what the H-step moments are built from)
+    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_update_v));
     if (n_failed) *n_failed = 0;
     if (!vb) return VLGP_OK;
     CHK(begin_count(ctx));
@@ -1456,14 +1452,8 @@ static int estep_staged(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double
 }
 
 extern "C" int vlgp_estep(vlgp_ctx* ctx, int set, int n_iter, double dmu_bound, int vb, int* n_failed) {
-    NEED_CTX(ctx);
-    CHK(vlgp_prior_collect(ctx));
-    ctx->hmom_us = nullptr;  // unit state changes: cached H-step moments are stale
-    CHK(vlgp_join_m(ctx));
-    NEED_PARAMS(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_STALE | OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_estep));
     if (n_failed) *n_failed = 0;
     if (n_iter < 1) return VLGP_OK;  // core.py:24-25
     if (!(dmu_bound > 0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "dmu_bound must be positive");
@@ -1479,12 +1469,9 @@ extern "C" int vlgp_estep(vlgp_ctx* ctx, int set, int n_iter, double dmu_bound, 
 
 extern "C" int vlgp_set_overlaps(vlgp_ctx* ctx, int set, int n_stages, const int* stage_start, int n_links,
                                  const int* links, const int* link_start) {
-    NEED_CTX(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_set_overlaps");
-    if (us->alias || us->Tmin != us->Tmax)
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_DEVICE, &us, &admit_vlgp_set_overlaps));
+    if (us->is(SET_TILING) || us->Tmin != us->Tmax)
         return vlgp_fail(ctx, VLGP_ERR_STATE, "overlaps belong to a copied cut of equal-length units");
     if (n_stages < 1 || !stage_start || stage_start[0] != 0 || stage_start[n_stages] != us->M || n_links < 0 ||
         (n_links > 0 && (!links || !link_start)))
@@ -1524,23 +1511,18 @@ extern "C" int vlgp_set_overlaps(vlgp_ctx* ctx, int set, int n_stages, const int
 }
 
 extern "C" int vlgp_unshare_mu(vlgp_ctx* ctx, int set) {
-    NEED_CTX(ctx);
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_unshare_mu");
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, 0, &us, &admit_vlgp_unshare_mu));
     us->share_mu = false;
     return VLGP_OK;
 }
 
 extern "C" int vlgp_mstep_begin(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, double eps, double lr,
                                 double da_bound, double db_bound) {
-    NEED_CTX(ctx);
-    NEED_PARAMS(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
+    NEED_CTX(ctx);  // (an M-step in flight had its parameters: asking this first changes no answer)
     if (ctx->m_pending) return vlgp_fail(ctx, VLGP_ERR_STATE, "an M-step is already in flight (call vlgp_mstep_end)");
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_mstep_begin");
+    UnitSet* us = nullptr;  // (no OPEN_JOIN: the call that starts the lane has nothing of it to wait for)
+    CHK(open_set(ctx, set, OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_mstep_begin));
     if (!(da_bound > 0) || !(db_bound > 0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "da_bound/db_bound must be positive");
     // fork: the M-step lane starts after everything already queued on the main stream
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -1600,21 +1582,15 @@ extern "C" int vlgp_mstep(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, d
 
 extern "C" int vlgp_hstep_objective(vlgp_ctx* ctx, int set, int window, double dt, int n_eval, const int* latent,
                                     const double* logp, double* ll, double* dll) {
-    NEED_CTX(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_hstep_objective");
+    UnitSet* us = nullptr;  // (no OPEN_JOIN: it runs beside the M-step lane)
+    CHK(open_set(ctx, set, OPEN_DEVICE, &us, &admit_vlgp_hstep_objective));
     if (n_eval < 1 || !latent || !logp || !ll || !dll) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad hstep arguments");
     return launch_hstep(ctx, *us, window, dt, n_eval, latent, logp, ll, dll);
 }
 
 extern "C" int vlgp_hstep_prepare(vlgp_ctx* ctx, int set, int window) {
-    NEED_CTX(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_hstep_prepare");
+    UnitSet* us = nullptr;  // (no OPEN_JOIN: it runs beside the M-step lane)
+    CHK(open_set(ctx, set, OPEN_DEVICE, &us, &admit_vlgp_hstep_prepare));
     ctx->hprep = false;
     if (ctx->hmom_bracket || window < 1) return VLGP_OK;
     // On the MAIN stream, behind everything queued so far -- the call may come while the E-step still runs (the host
@@ -1628,10 +1604,8 @@ extern "C" int vlgp_hstep_prepare(vlgp_ctx* ctx, int set, int window) {
 }
 
 extern "C" int vlgp_hstep_begin(vlgp_ctx* ctx, int set, int window) {
-    NEED_CTX(ctx);
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_hstep_begin");
+    UnitSet* us = nullptr;  // (host bookkeeping only: no wait, no device call)
+    CHK(open_set(ctx, set, 0, &us, &admit_vlgp_hstep_begin));
     ctx->hmom_bracket = true;
     // the first objective call inside the bracket builds the moments and the w copy -- unless vlgp_hstep_prepare did,
     // for this set and window, and no entry point that may change the units ran since
@@ -1664,7 +1638,7 @@ extern "C" int vlgp_apply_latent_map(vlgp_ctx* ctx, int set, const double* map, 
     HIPCHK(ctx, hipSetDevice(ctx->dev));
     UnitSet* us = vlgp_get_set(ctx, set, true);
     if (!us || !map) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad latent map arguments");
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_apply_latent_map");
+    CHK(admit(ctx, set, us, admit_vlgp_apply_latent_map));
     const int L = ctx->L;
     // staged through a pinned and a device buffer of its own, reused after the event behind the last kernel that read
     // them: nothing waits here (this is the first call of every EM iteration, constrain_loading)
@@ -1702,11 +1676,8 @@ static int moments_host(vlgp_ctx* ctx, UnitSet& us, std::vector<double>& out) {
 extern "C" int vlgp_norms_begin(vlgp_ctx* ctx, int set);
 extern "C" int vlgp_norms_end(vlgp_ctx* ctx, double out[2]);
 extern "C" int vlgp_norms(vlgp_ctx* ctx, int set, double out[2]) {
-    NEED_CTX(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_norms");
+    UnitSet* us = nullptr;  // (no OPEN_JOIN: it runs beside the M-step lane)
+    CHK(open_set(ctx, set, OPEN_DEVICE, &us, &admit_vlgp_norms));
     if (ctx->world == 1) {  // one rank: the kernel of the two-halves form (the same sums, bit for bit)
         CHK(vlgp_norms_begin(ctx, set));
         return vlgp_norms_end(ctx, out);
@@ -1722,11 +1693,8 @@ extern "C" int vlgp_norms(vlgp_ctx* ctx, int set, double out[2]) {
 }
 
 extern "C" int vlgp_norms_begin(vlgp_ctx* ctx, int set) {
-    NEED_CTX(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_norms_begin");
+    UnitSet* us = nullptr;  // (no OPEN_JOIN: it runs beside the M-step lane)
+    CHK(open_set(ctx, set, OPEN_DEVICE, &us, &admit_vlgp_norms_begin));
     CHK(wait_norms(ctx));  // (a pass never collected: dropped)
     ctx->x_pending = 0;
     ctx->x_set = set;
@@ -1762,11 +1730,8 @@ extern "C" int vlgp_norms_end(vlgp_ctx* ctx, double out[2]) {
 }
 
 extern "C" int vlgp_latent_moments(vlgp_ctx* ctx, int set, double* sum1, double* sum2, double* count) {
-    NEED_CTX(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED_BUT_FIT(ctx, us, "vlgp_latent_moments");
+    UnitSet* us = nullptr;  // (no OPEN_JOIN: it runs beside the M-step lane)
+    CHK(open_set(ctx, set, OPEN_DEVICE, &us, &admit_vlgp_latent_moments));
     std::vector<double> m;
     CHK(moments_host(ctx, *us, m));
     const int L = ctx->L, t = L * (L + 1) / 2;
@@ -1789,15 +1754,10 @@ extern "C" int vlgp_latent_moments(vlgp_ctx* ctx, int set, double* sum1, double*
 }
 
 extern "C" int vlgp_project_units(vlgp_ctx* ctx, int set, const double* proj, const double* shift, double* colsum) {
-    NEED_CTX(ctx);
-    ctx->hmom_us = nullptr;  // mu changes
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    CHK(vlgp_join_m(ctx));
-    UnitSet* us = vlgp_get_set(ctx, set, true);
-    if (!us) return VLGP_ERR_ARG;
-    NOT_REPLICATED(ctx, us, "vlgp_project_units");
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_STALE | OPEN_JOIN | OPEN_DEVICE, &us, &admit_vlgp_project_units));
     if (!proj || !shift) return vlgp_fail(ctx, VLGP_ERR_ARG, "null projection");
-    if (us->alias) return vlgp_fail(ctx, VLGP_ERR_STATE, "project the owning set, not an aliased cut");
+    if (us->is(SET_TILING)) return vlgp_fail(ctx, VLGP_ERR_STATE, "project the owning set, not an aliased cut");
     const int N = ctx->N, L = ctx->L;
     const int64_t G = (us->rows + 63) / 64;
     const int64_t o_proj = 0, o_shift = (int64_t)N * L, o_out = o_shift + L + (L & 1), o_part = o_out + N + (N & 1);

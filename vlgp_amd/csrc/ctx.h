@@ -24,6 +24,46 @@ struct Prior {
     int index = -1;               // row in the device prior table
 };
 
+// The kinds of unit set, one bit each, and the masks the host code asks for (api.hip holds the table of which
+// entry point takes which kinds).
+enum : unsigned {
+    SET_PLAIN = 1,        // uploaded (vlgp_upload_units)
+    SET_TILING = 2,       // a cut whose windows tile the source: shares y / x / mu / v / w with `parent` (alias)
+    SET_COPIED = 4,       // a cut with rows of its own, with or without overlaps (vlgp_set_overlaps)
+    SET_GROUPS = 8,       // replicas that leave groups of channels out (vlgp_replicate_groups / _units)
+    SET_MASKED = 16,      // replicas that leave single entries out (vlgp_replicate_masked), two or more of them
+    SET_MASKED_FIT = 32,  // ... exactly one: the source's rows with a mask, the set a fit with missing observations runs on
+    SET_REPLICATED = SET_GROUPS | SET_MASKED | SET_MASKED_FIT,
+    SET_BY_ROW = SET_MASKED | SET_MASKED_FIT,                    // one mask per row, not one per replica
+    SET_FIT = SET_PLAIN | SET_TILING | SET_COPIED | SET_MASKED_FIT,  // the fit (update_w / v, M-step, H-step, norms) may run on it
+    SET_SOURCE = 64,      // admission only: the call also takes a set that is the source of replicas
+    SET_ANY = 127,
+};
+
+// Replicated set (vlgp_replicate_groups; vlgp_replicate_units = singleton groups): n copies of set src's units,
+// replica-major (unit k M_src + m), replica k leaving a group of channels out of its E-step.  The n_pairs (replica,
+// left-out channel) pairs are listed in the caller's order: pair p is channel d_ch[p] of replica d_pair[p].  The
+// E-step reads the groups as bit masks, nw = (N + 63) / 64 words per replica, bit n & 63 of word n >> 6 set when
+// the replica leaves channel n out.  y and xb are the source's (aliased, never freed here); mu, v, w, dmu are the
+// replicas' own.  The source counts the replica sets that alias it (UnitSet::rep_users) and refuses re-upload / free.
+// A masked set (vlgp_replicate_masked) is the general form, one mask per ROW: by_row, d_mask (n rows_src, nw) indexed by
+// the replicated row, d_wconst (n rows_src, L) or null without a Gaussian channel, no pairs (n_pairs == 0); overlap:
+// some (row, channel) is held out by more than one replica (decided on the host when the set is made: vlgp_loglik then
+// has no single replica to write that entry's rate from).
+struct Replicas {
+    int src = -1;                 // the set whose y / x / xb rows these are; -1: not a replicated set
+    bool by_row = false, overlap = false;
+    int n = 0, n_pairs = 0, nw = 0;
+    int64_t rows_src = 0;
+    int* d_ch = nullptr;          // groups: (n_pairs) left-out channel of each pair
+    int* d_pair = nullptr;        // groups: (n_pairs) replica of each pair
+    unsigned long long* d_mask = nullptr;  // groups (n, nw), by_row (n rows_src, nw): membership masks
+    double* d_wconst = nullptr;   // Gaussian constant of w (estep_split.hip): groups (n, 16) per replica, by_row per row
+    double* d_nobs = nullptr;     // by_row with n == 1 only: (N) observed rows per channel (M-step noise)
+    void* d_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
+    double xh[8] = {};
+};
+
 struct UnitSet {
     bool valid = false;
     int M = 0;
@@ -54,32 +94,17 @@ struct UnitSet {
     int* d_links = nullptr;         // (n_links, 3): first unit, second unit, shared rows
     int n_links = 0;
     bool share_mu = true;           // false once the segments' mu was rebound (constrain_loading "svd")
-    // Replicated set (vlgp_replicate_groups; vlgp_replicate_units = singleton groups): n_rep copies of set rep_src's units,
-    // replica-major (unit k M_src + m), replica k leaving a group of channels out of its E-step.  The n_pairs (replica,
-    // left-out channel) pairs are listed in the caller's order: pair p is channel rep_ch[p] of replica rep_pair[p].  The
-    // E-step reads the groups as bit masks, rep_nw = (N + 63) / 64 words per replica, bit n & 63 of word n >> 6 set when
-    // the replica leaves channel n out.  y and xb are the source's (aliased, never freed here); mu, v, w, dmu are the
-    // replicas' own.  The source counts the replica sets that alias it (rep_users) and refuses re-upload / free.
-    // A masked set (vlgp_replicate_masked) is the general form, one mask per ROW: rep_by_row, d_rep_mask (n_rep rows_src,
-    // rep_nw) indexed by the replicated row, d_rep_wconst (n_rep rows_src, L) or null without a Gaussian channel, no pairs
-    // (n_pairs == 0); rep_overlap: some (row, channel) is held out by more than one replica (decided on the host when the
-    // set is made: vlgp_loglik then has no single replica to write that entry's rate from).
-    bool rep_by_row = false;
-    bool rep_overlap = false;
-    int rep_src = -1;
-    int n_rep = 0;
-    int n_pairs = 0;
-    int rep_nw = 0;
-    int64_t rows_src = 0;
-    std::vector<int> rep_ch;
-    int* d_rep_ch = nullptr;          // (n_pairs) left-out channel of each pair
-    int* d_rep_pair = nullptr;        // (n_pairs) replica of each pair
-    unsigned long long* d_rep_mask = nullptr;  // (n_rep, rep_nw) membership masks
-    double* d_rep_wconst = nullptr;   // (n_rep, 16): Gaussian constant of w per replica (estep_split.hip); masked: per row
-    double* d_rep_nobs = nullptr;     // masked fit set (masked, n_rep == 1): (N) observed rows per channel (M-step noise)
-    void* d_rep_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
-    double rep_xh[8] = {};
-    int rep_users = 0;
+    Replicas rep;                   // what a replicated set holds beside its own mu, v, w, dmu (default: not replicated)
+    int rep_users = 0;              // replicated sets whose y / x / xb are this set's rows
+
+    // What kind of set this is: exactly one SET_* bit.  Every question the host code asks about a set is a
+    // mask of kinds: us.is(SET_REPLICATED), us.is(SET_BY_ROW), us.is(SET_FIT).
+    unsigned kind() const {
+        if (rep.src >= 0) return !rep.by_row ? SET_GROUPS : (rep.n == 1 ? SET_MASKED_FIT : SET_MASKED);
+        return alias ? SET_TILING : (parent >= 0 ? SET_COPIED : SET_PLAIN);
+    }
+    bool is(unsigned kinds) const { return (kind() & kinds) != 0; }
+    bool is_source() const { return rep_users > 0; }  // replicas alias its rows: no re-upload, no free, no new contents
 };
 
 // Every debug / test switch the library reads from the environment, ONE table: X(name, field, kind, default, lo, hi, what).
@@ -257,6 +282,21 @@ struct vlgp_ctx {
     std::string err;
 };
 
+// the set that owns this set's y / x / xb rows: the set itself, or the source of its replicas
+inline UnitSet& vlgp_rows_owner(vlgp_ctx* ctx, UnitSet& us) { return us.rep.src >= 0 ? ctx->sets[us.rep.src] : us; }
+
+// What vlgp_loglik writes for a set, and how its row pass is launched: `slots` rows of four sums, `n_rate` rates,
+// grid.y of the launch and what to say when that exceeds the grid's limit of 65535.
+struct LoglikShape { int64_t slots, n_rate; int grid_y; const char* limit; };
+inline LoglikShape vlgp_loglik_shape(const vlgp_ctx* ctx, const UnitSet& us) {
+    if (us.is(SET_BY_ROW))
+        return {(int64_t)us.rep.n * ctx->N, us.rep.rows_src * ctx->N, us.rep.n, "vlgp_loglik: at most 65535 replicas per masked set"};
+    if (us.is(SET_GROUPS))
+        return {us.rep.n_pairs, us.rep.rows_src * us.rep.n_pairs, us.rep.n_pairs,
+                "vlgp_loglik: at most 65535 (replica, channel) pairs per set"};
+    return {ctx->N, us.rows * ctx->N, 1, ""};
+}
+
 // ---- error plumbing ------------------------------------------------------
 int vlgp_fail(vlgp_ctx* ctx, int code, const char* fmt, ...);
 #define HIPCHK(ctx, call)                                                          \
@@ -335,8 +375,8 @@ int launch_moments(vlgp_ctx* ctx, UnitSet& us);  // tri(L) gram | sum mu | sum v
 int launch_project(vlgp_ctx* ctx, UnitSet& us, const double* d_proj, const double* d_shift, double* d_part,
                    double* d_out);  // mu = y proj - shift; d_out = column sums of y
 int launch_gather(vlgp_ctx* ctx, UnitSet& src, UnitSet& dst, int window);
-// plug-in rates and per-channel log-likelihood sums of a set (evaluate.hip): d_rate (rows, N) for a plain set, (rows_src,
-// n_pairs) for a replicated one, or null; d_sums (slots, 4) with slots = N or n_pairs, written in a fixed order
+// plug-in rates and per-channel log-likelihood sums of a set (evaluate.hip): d_rate (vlgp_loglik_shape's n_rate) or null;
+// d_sums (slots, 4), written in a fixed order
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums);
 // d_sums (slots, 4) = the partials d_part (slots, n_blk, 4) of each slot added in workgroup order (evaluate.hip)
 int launch_sums_finish(vlgp_ctx* ctx, int slots, int n_blk, const double* d_part, double* d_sums);

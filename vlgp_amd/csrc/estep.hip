@@ -443,12 +443,10 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     if (need_prior) CHK(vlgp_bind_priors(ctx, us));
     if (report) {
         // (no x.b refresh: the families choose by sizes and switches only)
-    } else if (us.rep_src >= 0) {  // replicated set: x.b of the source rows, the split E-step or an error (never another family)
-        UnitSet& src = ctx->sets[us.rep_src];
+    } else {  // (a replicated set: x.b of the source rows; it takes the split E-step or an error, never another family)
+        UnitSet& src = vlgp_rows_owner(ctx, us);
         if (!src.x_ones) CHK(vlgp_refresh_xb(ctx, src));
         us.d_xb = src.d_xb;
-    } else if (!us.x_ones) {
-        CHK(vlgp_refresh_xb(ctx, us));
     }
 
     // ranks and LDS demands over the priors this set uses
@@ -482,7 +480,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
         int handled = 0;
         CHK(launch_estep_split(ctx, us, A, rs, &handled, report));
         if (handled) { *path = handled == 2 ? VLGP_PATH_ESTEP_LSPLIT : (handled == 3 ? VLGP_PATH_ESTEP_SPLIT_MIXED : VLGP_PATH_ESTEP_SPLIT); return VLGP_OK; }
-        if (us.rep_src >= 0)
+        if (us.is(SET_REPLICATED))
             return vlgp_fail(ctx, VLGP_ERR_STATE, "replicated set: only the split E-step leaves a channel out, and it declined");
     }
 

@@ -1979,9 +1979,9 @@ SplitPlan plan_estep_split(const vlgp_ctx* ctx, const UnitSet& us, const RankSum
     SplitPlan P;
     const int N = ctx->N, L = ctx->L;
     const Switches& sw = ctx->sw;
-    // a replicated set (vlgp_replicate_units) runs here or nowhere: only these row passes leave a channel out, so neither
+    // a replicated set (any of SET_REPLICATED) runs here or nowhere: only these row passes leave a channel out, so neither
     // the switches nor the size heuristics may send it to another kernel family -- a limit it exceeds is an error
-    const bool rep = us.rep_src >= 0;
+    const bool rep = us.is(SET_REPLICATED);
 #define SPLIT_DECLINE(cond, code, what) \
     do { if (cond) { P.decline_code = code; P.decline = what; return P; } } while (0)
     SPLIT_DECLINE(!rep && sw.estep_split == 0, VLGP_ESPLIT_OFF, "VLGP_ESTEP_SPLIT=0");
@@ -2106,7 +2106,7 @@ void report_split_plan(const vlgp_ctx* ctx, const RankSummary& rs, const SplitPl
 int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummary& rs, int* handled, int* report) {
     *handled = 0;
     const SplitPlan P = plan_estep_split(ctx, us, rs, E.mode, E.n_iter);
-    const bool rep = us.rep_src >= 0;
+    const bool rep = us.is(SET_REPLICATED), by_row = us.is(SET_BY_ROW);
     if (report) {
         report[EP_DECLINE] = P.decline_code;
         if (P.decline) return VLGP_OK;
@@ -2137,20 +2137,19 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     HIPCHK(ctx, hipGetLastError());
     ExclArgs XA{};  // replicated set: its replica table, source rows, per-replica wconst
     if (rep) {
-        const UnitSet& src = ctx->sets[us.rep_src];
-        XA.mask = us.d_rep_mask;
-        XA.wconst = us.d_rep_wconst;
-        XA.y = src.y;
+        XA.mask = us.rep.d_mask;
+        XA.wconst = us.rep.d_wconst;
+        XA.y = vlgp_rows_owner(ctx, us).y;
         XA.xb = E.xb;  // (launch_estep points the replicas' xb at the source's, refreshed)
-        XA.rows_src = us.rows_src;
+        XA.rows_src = us.rep.rows_src;
         XA.row_base = 0;
         XA.mu_lm = nullptr;  // (set below, with the latent-major copies)
-        if (!us.rep_by_row)
-            hipLaunchKernelGGL(esplit_excl_wconst, dim3((unsigned)((us.n_rep * 16 + 255) / 256)), dim3(256), 0, ctx->stream, N,
-                               L, us.n_rep, us.rep_nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_mask, us.d_rep_wconst);
-        else if (us.d_rep_wconst)  // (null: no Gaussian channel, the row passes take the constant as 0)
+        if (!by_row)
+            hipLaunchKernelGGL(esplit_excl_wconst, dim3((unsigned)((us.rep.n * 16 + 255) / 256)), dim3(256), 0, ctx->stream, N,
+                               L, us.rep.n, us.rep.nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.rep.d_mask, us.rep.d_wconst);
+        else if (us.rep.d_wconst)  // (null: no Gaussian channel, the row passes take the constant as 0)
             hipLaunchKernelGGL(esplit_row_wconst, dim3((unsigned)((us.rows + 255) / 256)), dim3(256), 0, ctx->stream, N, L,
-                               us.rows, us.rep_nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.d_rep_mask, us.d_rep_wconst);
+                               us.rows, us.rep.nw, ctx->d_a, ctx->d_noise, ctx->d_gauss, us.rep.d_mask, us.rep.d_wconst);
         HIPCHK(ctx, hipGetLastError());
     }
 
@@ -2169,9 +2168,9 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     }
     if (rep) {  // the replica table the row passes read (a host copy that outlives the asynchronous upload)
         XA.mu_lm = A.mu;
-        static_assert(sizeof(ExclArgs) <= sizeof(us.rep_xh), "UnitSet::rep_xh too small for ExclArgs");
-        memcpy(us.rep_xh, &XA, sizeof(ExclArgs));
-        HIPCHK(ctx, hipMemcpyAsync(us.d_rep_xa, us.rep_xh, sizeof(ExclArgs), hipMemcpyHostToDevice, ctx->stream));
+        static_assert(sizeof(ExclArgs) <= sizeof(us.rep.xh), "Replicas::xh too small for ExclArgs");
+        memcpy(us.rep.xh, &XA, sizeof(ExclArgs));
+        HIPCHK(ctx, hipMemcpyAsync(us.rep.d_xa, us.rep.xh, sizeof(ExclArgs), hipMemcpyHostToDevice, ctx->stream));
     }
     A.failg = reinterpret_cast<int*>(us.d_scratch + P.o_failg);
     A.xl = us.d_scratch + P.o_xl;
@@ -2193,8 +2192,7 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     const int kind = lng ? VLGP_PROF_ESTEP_LONG
                          : (P.maxra <= 16 ? VLGP_PROF_ESTEP_RA16 : (P.maxra <= 24 ? VLGP_PROF_ESTEP_RA24 : VLGP_PROF_ESTEP_RA32));
     vlgp_prof_begin(ctx, kind);
-    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.d_rep_xa) : nullptr,
-                   rep && us.rep_by_row};
+    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.rep.d_xa) : nullptr, by_row};
     int rc = VLGP_OK;
     if (with_mean) rc = run_ya(ctx, main_lane, A, LT, cols, ycoef);
 

@@ -132,39 +132,37 @@ int launch_sums_finish(vlgp_ctx* ctx, int slots, int n_blk, const double* d_part
 
 static int launch_loglik_masked(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums) {
     LlMaskArgs A;
-    A.m = fill_row_model(ctx, ctx->sets[us.rep_src], us, vb);
+    const LoglikShape S = vlgp_loglik_shape(ctx, us);
+    A.m = fill_row_model(ctx, vlgp_rows_owner(ctx, us), us, vb);
     A.n_blk = (int)((A.m.rows + 255) / 256);
-    A.nw = us.rep_nw;
-    A.mask = us.d_rep_mask;
+    A.nw = us.rep.nw;
+    A.mask = us.rep.d_mask;
     A.rate = d_rate;
-    const int64_t slots = (int64_t)us.n_rep * ctx->N;
     if (A.m.rows < 1 || A.n_blk < 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on an empty set");
-    if (us.n_rep > 65535) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: at most 65535 replicas per masked set");
-    if (slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: too many (replica, channel) slots");
-    CHK(vlgp_ensure_work(ctx, slots * A.n_blk * 4 + 8));
+    if (S.grid_y > 65535) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s", S.limit);
+    if (S.slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: too many (replica, channel) slots");
+    CHK(vlgp_ensure_work(ctx, S.slots * A.n_blk * 4 + 8));
     A.part = ctx->d_work;
-    hipLaunchKernelGGL(ll_rows_masked, dim3((unsigned)A.n_blk, (unsigned)us.n_rep), dim3(256), 0, ctx->stream, A);
+    hipLaunchKernelGGL(ll_rows_masked, dim3((unsigned)A.n_blk, (unsigned)S.grid_y), dim3(256), 0, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
-    return launch_sums_finish(ctx, (int)slots, A.n_blk, ctx->d_work, d_sums);
+    return launch_sums_finish(ctx, (int)S.slots, A.n_blk, ctx->d_work, d_sums);
 }
 
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums) {
-    const bool rep = us.rep_src >= 0;
-    if (rep && us.rep_by_row) return launch_loglik_masked(ctx, us, vb, d_rate, d_sums);
+    if (us.is(SET_BY_ROW)) return launch_loglik_masked(ctx, us, vb, d_rate, d_sums);
+    const LoglikShape S = vlgp_loglik_shape(ctx, us);
     LlArgs A;
-    A.m = fill_row_model(ctx, rep ? ctx->sets[us.rep_src] : us, us, vb);
+    A.m = fill_row_model(ctx, vlgp_rows_owner(ctx, us), us, vb);
     A.n_blk = (int)((A.m.rows + 255) / 256);
-    A.ch = rep ? us.d_rep_ch : nullptr;
-    A.pair_rep = rep ? us.d_rep_pair : nullptr;
-    A.n_pairs = rep ? us.n_pairs : 0;
+    A.ch = us.rep.d_ch;  // (null, null, 0 unless the set is group replicas)
+    A.pair_rep = us.rep.d_pair;
+    A.n_pairs = us.rep.n_pairs;
     A.rate = d_rate;
-    const int slots = rep ? us.n_pairs : ctx->N;
     if (A.m.rows < 1 || A.n_blk < 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_loglik on an empty set");
-    if (rep && us.n_pairs > 65535)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: at most 65535 (replica, channel) pairs per set");
-    CHK(vlgp_ensure_work(ctx, (int64_t)slots * A.n_blk * 4 + 8));
+    if (S.grid_y > 65535) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s", S.limit);
+    CHK(vlgp_ensure_work(ctx, S.slots * A.n_blk * 4 + 8));
     A.part = ctx->d_work;
-    hipLaunchKernelGGL(ll_rows, dim3((unsigned)A.n_blk, (unsigned)(rep ? us.n_pairs : 1)), dim3(256), 0, ctx->stream, A);
+    hipLaunchKernelGGL(ll_rows, dim3((unsigned)A.n_blk, (unsigned)S.grid_y), dim3(256), 0, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
-    return launch_sums_finish(ctx, slots, A.n_blk, ctx->d_work, d_sums);
+    return launch_sums_finish(ctx, (int)S.slots, A.n_blk, ctx->d_work, d_sums);
 }

@@ -1149,8 +1149,8 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
                  double da_bound, double db_bound) {
     const int N = ctx->N, L = ctx->L, P = ctx->P;
     const bool gen = mstep_generic(ctx, L, P);  // beyond the compiled sizes: loop-based kernels, solves in global memory
-    // a masked fit set (api.hip lets no other replicated set in): the compiled Poisson kernels on one rank, or an error
-    const bool masked = us.rep_src >= 0;
+    // a masked fit set (the one replicated kind in SET_FIT): the compiled Poisson kernels on one rank, or an error
+    const bool masked = us.is(SET_REPLICATED);
     if (masked) {
         if (ctx->n_gauss > 0)
             return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: the handle has Gaussian channels (their least-squares "
@@ -1160,7 +1160,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
                              "VLGP_MSTEP_GENERIC) take no mask");
         if (L > 10) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: more than 10 latents (L > 10)");
         if (ctx->world > 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: more than one rank");
-        if (!us.d_rep_mask || !us.d_rep_nobs) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: the set has no mask");
+        if (!us.is(SET_MASKED_FIT) || !us.rep.d_mask || !us.rep.d_nobs) return vlgp_fail(ctx, VLGP_ERR_STATE, "masked M-step: the set has no mask");
     }
     const int km = masked ? K_MASKED : 0;
     const Geometry g = plan(ctx, us.rows);
@@ -1191,7 +1191,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
         auto pk = [&](const void* p_) { key.push_back((double)(uintptr_t)p_); };
         pk(us.y); pk(us.x_ones ? nullptr : us.x); pk(us.mu); pk(us.v); pk(us.w); pk(us.dmu); pk(W); pk(ctx->d_a); pk(ctx->d_b);
         pk(ctx->d_noise); pk(ctx->d_da); pk(ctx->d_db); pk(ctx->d_fail_m); pk(ctx->d_gauss);
-        pk(masked ? us.d_rep_mask : nullptr); pk(masked ? us.d_rep_nobs : nullptr); key.push_back((double)masked);
+        pk(masked ? us.rep.d_mask : nullptr); pk(masked ? us.rep.d_nobs : nullptr); key.push_back((double)masked);
         for (double v_ : {(double)us.rows, (double)N, (double)L, (double)P, (double)ctx->n_gauss, (double)n_iter,
                           (double)use_hessian, eps, lr, da_bound, db_bound, (double)noise_passes, (double)gen, ctx->sw.mstep_wg_per_cu})
             key.push_back(v_);
@@ -1212,7 +1212,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
     A.N = N; A.L = L; A.P = P; A.rows = us.rows; A.rows_per_wg = g.rows_per_wg; A.CT = g.CT; A.S = g.S;
     A.y = us.y; A.x = us.x_ones ? nullptr : us.x; A.mu = us.mu; A.v = us.v;
     A.a = ctx->d_a; A.b = ctx->d_b; A.gauss = ctx->d_gauss; A.mean = d_mean; A.partial = d_part;
-    if (masked) A.mask = us.d_rep_mask;  // (in the slot of gauss: the Newton launch gets nobs in the slot of mean)
+    if (masked) A.mask = us.rep.d_mask;  // (in the slot of gauss: the Newton launch gets nobs in the slot of mean)
 
     auto reduce_to = [&](int K, double* dst) -> int {
         const int64_t n = (int64_t)K * N;
@@ -1259,12 +1259,12 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
             } else {
             CHK(launch_accum(ctx, K_NOISE1 | km, g, A, d_cache));
             CHK(reduce_to(1, d_s1));
-            if (masked) hipLaunchKernelGGL(noise_mean_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.d_rep_nobs, d_s1, d_mean);
+            if (masked) hipLaunchKernelGGL(noise_mean_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.rep.d_nobs, d_s1, d_mean);
             else hipLaunchKernelGGL(noise_mean_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N,
                                total_rows, d_s1, d_mean);
             CHK(launch_accum(ctx, K_NOISE2 | km, g, A, d_cache));
             CHK(reduce_to(1, d_s1));
-            if (masked) hipLaunchKernelGGL(noise_final_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.d_rep_nobs, d_s1, ctx->d_noise);
+            if (masked) hipLaunchKernelGGL(noise_final_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.rep.d_nobs, d_s1, ctx->d_noise);
             else hipLaunchKernelGGL(noise_final_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N,
                                total_rows, d_s1, ctx->d_noise);
             HIPCHK(ctx, hipGetLastError());
@@ -1273,7 +1273,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
         if (any_poisson) {
             vlgp_prof_begin(ctx, VLGP_PROF_MSTEP, st);
             MArgs An = A;
-            if (masked) An.nobs = us.d_rep_nobs;  // (the Newton launch reads no mean)
+            if (masked) An.nobs = us.rep.d_nobs;  // (the Newton launch reads no mean)
             int rc = launch_accum(ctx, K_NEWTON | km, g, An, d_cache);
             vlgp_prof_end(ctx, VLGP_PROF_MSTEP, (double)us.rows, st);
             CHK(rc);

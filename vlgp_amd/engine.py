@@ -15,6 +15,7 @@ Two layers:
   what :func:`vlgp_amd.fit` builds -- the data stays resident on the GPU and
   nothing crosses PCIe between stages.
 """
+import collections
 import ctypes as C
 import logging
 import os
@@ -67,6 +68,11 @@ def unpack_mask(words, n_channels):
     return bits[..., :int(n_channels)].astype(bool)
 
 
+class Replicas(collections.namedtuple("Replicas", "n channels by_entry")):
+    """What ``Engine.replicate`` made of a set: ``n`` replicas; ``channels``, the left-out channel of every (replica,
+    channel) pair in the caller's order, or None when the replicas leave single entries out (``by_entry``)."""
+
+
 class Engine:
     """One GPU, one handle (include/vlgp_hip.h)."""
 
@@ -85,7 +91,7 @@ class Engine:
             check(rc, None)
         self.h = h
         self.sets = {}  # set id -> (M, rows, offsets)
-        self.replicas = {}  # replicated set id -> (replicas, its held-out channels, one per pair) (Engine.replicate)
+        self.replicas = {}  # replicated set id -> Replicas (Engine.replicate)
         self.state_epoch = 0  # bumped by every call that can change a set's mu (em_iteration's norm cache keys on it)
         self.rank, self.world = 0, 1
         self.host_exchange = False
@@ -246,7 +252,7 @@ class Engine:
             self._ck(self.lib.vlgp_replicate_groups(self.h, int(src), int(dst), k, iptr(start), iptr(ch)))
         roff = np.concatenate([r * rows + off[:-1] for r in range(k)] + [np.array([k * rows], dtype=np.int64)])
         self.sets[dst] = (k * m, k * rows, roff)
-        self.replicas[dst] = (k, ch)
+        self.replicas[dst] = Replicas(k, ch, held_out is not None)
 
     def loglik(self, set_id, vb=True, want_rate=False):
         """Plug-in rates and per-channel log-likelihood sums of a set (vlgp_loglik): ``(sums, rate)``, sums
@@ -256,12 +262,12 @@ class Engine:
         where no replica holds the entry out."""
         _, rows, _ = self.sets[set_id]
         rep = self.replicas.get(set_id)
-        rows_out = rows if rep is None else rows // max(rep[0], 1)
-        if rep is not None and rep[1] is None:
-            sums = np.empty((rep[0], self.N, 4))
+        rows_out = rows if rep is None else rows // max(rep.n, 1)
+        if rep is not None and rep.by_entry:
+            sums = np.empty((rep.n, self.N, 4))
             rate = np.empty((rows_out, self.N)) if want_rate else None
         else:
-            slots = self.N if rep is None else len(rep[1])
+            slots = self.N if rep is None else len(rep.channels)
             sums = np.empty((slots, 4))
             rate = np.empty((rows_out, slots)) if want_rate else None
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
