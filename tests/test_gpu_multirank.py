@@ -189,6 +189,58 @@ def test_two_ranks_default_initialisation_matches_single_process():
     assert relerr(np.concatenate([r0[6], r1[6]]), one[6]) < PARAM_TOL
 
 
+ORDER_SENSITIVE = (1e16, 1.0, -1e16)  # (1e16 + 1) - 1e16 = 0 but (1e16 - 1e16) + 1 = 1: the sum's bits tell the order
+
+
+def _contribution(rank, n):
+    return ORDER_SENSITIVE[rank % 3] * (1.0 + np.arange(n))
+
+
+def _exchange_worker(rank, world, ids, q):
+    os.environ["VLGP_COMM_TRANSPORT"] = "shm"
+    sys.path.insert(0, ROOT)
+    import vlgp_amd as V
+
+    got = []
+    with V.Engine(4, 2, 1, 50) as eng:
+        for nth, (uid, uid_aux) in enumerate(ids):  # the second comm_init on the same engine: the transport fallback's path
+            eng.comm_init(uid, rank, world, uid_aux)
+            assert eng.transport == "shm" and eng.host_exchange is True and eng.rccl_ranks == (0, 0)
+            for n in ((1, 5, 1000) if nth == 0 else (5,)):
+                got.append(eng.allreduce_host(_contribution(rank, n)))
+            eng.barrier()
+    q.put((rank, got))
+
+
+def test_three_ranks_sum_in_rank_order_and_a_second_comm_init_leaks_nothing():
+    """Three processes on device 0 over the shared-memory transport: allreduce_host gives every rank the bits of the
+    NumPy sum in rank order from 0.0; after a barrier a second comm_init with fresh ids (the path a transport fallback
+    takes) closes what the first one opened -- no segment is left behind -- and the lanes still add correctly."""
+    import glob
+    import multiprocessing as mp
+
+    world, before = 3, set(glob.glob("/dev/shm/vlgp_*"))
+    ids = [tuple(("test-%d-%d-%d" % (os.getpid(), nth, lane)).encode().ljust(128, b"\0") for lane in (0, 1))
+           for nth in (0, 1)]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_exchange_worker, args=(r, world, ids, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(_collect(q, procs, limit=120.0), key=lambda r: r[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for i, n in enumerate((1, 5, 1000, 5)):
+        want = np.zeros(n)
+        for r in range(world):
+            want = want + _contribution(r, n)
+        for rank, got in res:
+            assert got[i].shape == (n,) and np.array_equal(got[i].view(np.uint64), want.view(np.uint64)), (rank, n)
+    assert np.all(_contribution(0, 5) + _contribution(2, 5) + _contribution(1, 5) != want)  # (another order: other bits)
+    assert set(glob.glob("/dev/shm/vlgp_*")) <= before
+
+
 def test_bench_launch_line_two_ranks_one_gpu():
     env = dict(os.environ, VLGP_COMM_TRANSPORT="shm", VLGP_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",

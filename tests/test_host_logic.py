@@ -42,20 +42,28 @@ def _switch_table():
 
 
 def test_the_environment_is_read_by_the_switch_reader_and_the_communicator_only():
-    """One lifetime for every library-side switch: vlgp_read_switches (create, reload) is the only reader.  The only
-    other getenv calls name the transport settings the communicator set-up shares with dist.py."""
-    reader_calls = 0
+    """One lifetime for every library-side switch: vlgp_read_switches (create, reload; api.hip) is the only reader.  The
+    only other getenv calls are in comm.hip and name the transport settings the communicator set-up shares with dist.py;
+    they are read at set-up, none inside an all-reduce."""
+    reader_calls, named = 0, set()
     for f in sorted(os.listdir(CSRC)):
-        if not f.endswith((".hip", ".h")):
+        if not f.endswith((".hip", ".h", ".c", ".cpp")):
             continue
         src = open(os.path.join(CSRC, f)).read()
         for m in re.finditer(r"getenv\s*\(([^)]*)\)", src):
             arg = m.group(1).strip()
-            if f == "api.hip" and arg == "name":
+            if f == "api.hip":
+                assert arg == "name", m.group(0)
                 reader_calls += 1
                 continue
-            assert arg.strip('"') in TRANSPORT_SETTINGS and f == "api.hip", (f, m.group(0))
-    assert reader_calls == 1
+            assert f == "comm.hip" and arg.strip('"') in TRANSPORT_SETTINGS, (f, m.group(0))
+            named.add(arg.strip('"'))
+    assert reader_calls == 1 and named == TRANSPORT_SETTINGS
+    comm = open(os.path.join(CSRC, "comm.hip")).read()
+    for fn in ("static int shm_allreduce(", "int vlgp_hx_allreduce(", "int vlgp_allreduce("):
+        body = comm[comm.index(fn):comm.index("\n}\n", comm.index(fn))]
+        assert "VLGP_OK" in body and "getenv" not in body and "VLGP_SHM_TIMEOUT_S" not in body, fn
+    assert "getenv" not in open(os.path.join(CSRC, "host_exchange.h")).read()
     api = open(os.path.join(CSRC, "api.hip")).read()
     reader = api[api.index("static double read_switch("):api.index("void vlgp_read_switches(")]
     assert "getenv(name)" in reader

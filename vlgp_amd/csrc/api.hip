@@ -1,13 +1,11 @@
 // C ABI of libvlgp_hip.so (include/vlgp_hip.h): handle management, host<->device
-// marshalling, RCCL plumbing and the thin wrappers around the kernel launchers.
-#include <dlfcn.h>
+// marshalling and the thin wrappers around the kernel launchers (communication between ranks: comm.hip).
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <chrono>
-#include <time.h>
 
 #include <algorithm>
 #include <new>
@@ -27,9 +25,6 @@ int vlgp_fail(vlgp_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-#define NEED_CTX(ctx) \
-    if (!(ctx)) return vlgp_fail(nullptr, VLGP_ERR_ARG, "null handle")
-
 static int dev_alloc(vlgp_ctx* ctx, double** p, int64_t n, bool zero) {
     *p = nullptr;
     if (n <= 0) n = 1;
@@ -38,29 +33,20 @@ static int dev_alloc(vlgp_ctx* ctx, double** p, int64_t n, bool zero) {
     return VLGP_OK;
 }
 
-int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n) {
-    if (n <= ctx->work_len) return VLGP_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_work) HIPCHK(ctx, hipFree(ctx->d_work));
-    ctx->d_work = nullptr;
-    ctx->work_len = 0;
+// a workspace of at least n doubles, grown with headroom once the stream that uses it has drained
+static int ensure_work(vlgp_ctx* ctx, hipStream_t st, double** buf, int64_t* len, int64_t n) {
+    if (n <= *len) return VLGP_OK;
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (*buf) HIPCHK(ctx, hipFree(*buf));
+    *buf = nullptr;
+    *len = 0;
     const int64_t cap = n + n / 4 + 1024;
-    HIPCHK(ctx, hipMalloc(&ctx->d_work, (size_t)cap * sizeof(double)));
-    ctx->work_len = cap;
+    HIPCHK(ctx, hipMalloc(buf, (size_t)cap * sizeof(double)));
+    *len = cap;
     return VLGP_OK;
 }
-
-int vlgp_ensure_work_m(vlgp_ctx* ctx, int64_t n) {
-    if (n <= ctx->work_m_len) return VLGP_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->mstream));
-    if (ctx->d_work_m) HIPCHK(ctx, hipFree(ctx->d_work_m));
-    ctx->d_work_m = nullptr;
-    ctx->work_m_len = 0;
-    const int64_t cap = n + n / 4 + 1024;
-    HIPCHK(ctx, hipMalloc(&ctx->d_work_m, (size_t)cap * sizeof(double)));
-    ctx->work_m_len = cap;
-    return VLGP_OK;
-}
+int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n) { return ensure_work(ctx, ctx->stream, &ctx->d_work, &ctx->work_len, n); }
+int vlgp_ensure_work_m(vlgp_ctx* ctx, int64_t n) { return ensure_work(ctx, ctx->mstream, &ctx->d_work_m, &ctx->work_m_len, n); }
 
 // wait for a queued norms pass (vlgp_norms_begin): its sequence word in mapped host memory
 static int wait_norms(vlgp_ctx* ctx) {
@@ -244,315 +230,6 @@ static void prof_drain(vlgp_ctx* ctx) {
     ctx->pending.clear();
 }
 
-// ---- RCCL (loaded lazily: single-GPU use never touches it) ---------------
-typedef struct { char internal[128]; } rccl_uid;
-typedef int (*fn_getuid)(rccl_uid*);
-typedef int (*fn_initrank)(void**, int, rccl_uid, int);
-typedef int (*fn_allreduce)(const void*, void*, size_t, int, int, void*, hipStream_t);
-typedef int (*fn_destroy)(void*);
-typedef const char* (*fn_errstr)(int);
-typedef int (*fn_count)(void*, int*);
-static struct {
-    void* lib = nullptr;
-    fn_getuid get_uid = nullptr;
-    fn_initrank init_rank = nullptr;
-    fn_allreduce all_reduce = nullptr;
-    fn_destroy destroy = nullptr;
-    fn_errstr errstr = nullptr;
-    fn_count count = nullptr;  // ncclCommCount: what RCCL itself says the communicator spans
-} g_rccl;
-
-static int rccl_load(vlgp_ctx* ctx) {
-    if (g_rccl.lib) return VLGP_OK;
-    void* lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) lib = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!lib) return vlgp_fail(ctx, VLGP_ERR_COMM, "cannot load librccl.so: %s", dlerror());
-    g_rccl.get_uid = (fn_getuid)dlsym(lib, "ncclGetUniqueId");
-    g_rccl.init_rank = (fn_initrank)dlsym(lib, "ncclCommInitRank");
-    g_rccl.all_reduce = (fn_allreduce)dlsym(lib, "ncclAllReduce");
-    g_rccl.destroy = (fn_destroy)dlsym(lib, "ncclCommDestroy");
-    g_rccl.errstr = (fn_errstr)dlsym(lib, "ncclGetErrorString");
-    g_rccl.count = (fn_count)dlsym(lib, "ncclCommCount");
-    if (!g_rccl.get_uid || !g_rccl.init_rank || !g_rccl.all_reduce || !g_rccl.destroy)
-        return vlgp_fail(ctx, VLGP_ERR_COMM, "librccl.so lacks an expected symbol");
-    g_rccl.lib = lib;
-    return VLGP_OK;
-}
-
-
-// ---- shared-memory test transport --------------------------------------------------
-// VLGP_COMM_TRANSPORT=shm replaces RCCL by an all-reduce through a POSIX shared-memory
-// segment (device -> host, sum in rank order, host -> device).  It exists so that the
-// full multi-rank protocol -- sharding, the per-Newton-iteration M-step reductions, the
-// H-step rounds, the norms -- can be exercised by several processes that share ONE GPU
-// (RCCL refuses two ranks on a device).  It is a test vehicle, not a data path.
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <unistd.h>
-#define SHM_MAX_RANKS 16
-#define SHM_SLOT_DOUBLES (1 << 17)
-struct ShmRegion {
-    volatile long long ready[SHM_MAX_RANKS];
-    volatile long long done[SHM_MAX_RANKS];
-    double slot[SHM_MAX_RANKS][SHM_SLOT_DOUBLES];
-};
-struct ShmComm {
-    ShmRegion* reg = nullptr;
-    long long seq = 0;
-    int rank = 0, world = 1;
-    char name[64];
-};
-static bool shm_mode() {
-    const char* t = getenv("VLGP_COMM_TRANSPORT");
-    return t && strcmp(t, "shm") == 0;
-}
-static ShmComm* shm_open_comm(const char id[VLGP_UNIQUE_ID_BYTES], int rank, int world) {
-    if (world > SHM_MAX_RANKS) return nullptr;
-    ShmComm* c = new ShmComm();
-    c->rank = rank; c->world = world;
-    unsigned long long h = 1469598103934665603ULL;
-    for (int i = 0; i < VLGP_UNIQUE_ID_BYTES; ++i) h = (h ^ (unsigned char)id[i]) * 1099511628211ULL;
-    snprintf(c->name, sizeof(c->name), "/vlgp_shm_%016llx", h);
-    int fd = shm_open(c->name, O_CREAT | O_RDWR, 0600);
-    if (fd < 0) { delete c; return nullptr; }
-    if (ftruncate(fd, sizeof(ShmRegion)) != 0) { close(fd); delete c; return nullptr; }
-    void* p = mmap(nullptr, sizeof(ShmRegion), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (p == MAP_FAILED) { delete c; return nullptr; }
-    c->reg = (ShmRegion*)p;  // a fresh segment is zero-filled: ready/done start at 0, seq at 1
-    return c;
-}
-static void shm_close_comm(ShmComm* c) {
-    if (!c) return;
-    if (c->reg) munmap((void*)c->reg, sizeof(ShmRegion));
-    if (c->rank == 0) shm_unlink(c->name);
-    delete c;
-}
-static int shm_allreduce(vlgp_ctx* ctx, ShmComm* c, hipStream_t st, double* d_buf, int64_t n) {
-    if (n > SHM_SLOT_DOUBLES) return vlgp_fail(ctx, VLGP_ERR_COMM, "shm transport: buffer of %lld doubles too large", (long long)n);
-    const long long s = ++c->seq;
-    ShmRegion* R = c->reg;
-    // a rank that died must not hang the others: every wait gives up after VLGP_SHM_TIMEOUT_S (default 60 s)
-    const char* tmo_s = getenv("VLGP_SHM_TIMEOUT_S");
-    const double tmo = tmo_s ? atof(tmo_s) : 60.0;
-    auto wait_ge = [&](volatile long long* p, long long want) {
-        const auto t0 = std::chrono::steady_clock::now();
-        while (*p < want) {
-            usleep(20);
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > tmo) return false;
-        }
-        return true;
-    };
-    // nobody may still be reading my slot from the previous round
-    for (int k = 0; k < c->world; ++k)
-        if (!wait_ge(&R->done[k], s - 1)) return vlgp_fail(ctx, VLGP_ERR_COMM, "shm transport: rank %d is not responding", k);
-    HIPCHK(ctx, hipMemcpyAsync((void*)R->slot[c->rank], d_buf, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    __sync_synchronize();
-    R->ready[c->rank] = s;
-    for (int k = 0; k < c->world; ++k)
-        if (!wait_ge(&R->ready[k], s)) return vlgp_fail(ctx, VLGP_ERR_COMM, "shm transport: rank %d is not responding", k);
-    __sync_synchronize();
-    std::vector<double> sum((size_t)n, 0.0);
-    for (int k = 0; k < c->world; ++k)  // fixed rank order: every rank gets the same bits
-        for (int64_t i = 0; i < n; ++i) sum[(size_t)i] += R->slot[k][i];
-    __sync_synchronize();
-    R->done[c->rank] = s;
-    HIPCHK(ctx, hipMemcpyAsync(d_buf, sum.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return VLGP_OK;
-}
-
-// ---- host-side exchange of the H-step round sums -----------------------------------------
-// With several ranks every H-step round needs sum_ranks (ll, dll) for a handful of evaluations.
-// Each rank already has its own sums on the host (the round kernel's mailbox), so the cross-rank
-// sum is done there: one cache line per rank in a POSIX shared-memory segment, busy-polled, summed
-// in rank order (every rank gets the same bits).  ~3 us instead of an RCCL all-reduce plus a
-// device-to-host copy (~50 us) on the latency-critical path of ~40 dependent rounds per EM
-// iteration.  Single node only -- as is the rendezvous of the RCCL ids.
-#define HX_MAX_VALS 64
-struct HxRegion {
-    long long ready[SHM_MAX_RANKS][8];   // one cache line per counter
-    long long done[SHM_MAX_RANKS][8];
-    double slot[SHM_MAX_RANKS][HX_MAX_VALS];
-};
-struct HxComm {
-    HxRegion* reg = nullptr;
-    long long seq = 0;
-    int rank = 0, world = 1;
-    char name[64];
-};
-static HxComm* hx_open(const char id[VLGP_UNIQUE_ID_BYTES], int rank, int world) {
-    if (world > SHM_MAX_RANKS) return nullptr;
-    HxComm* c = new HxComm();
-    c->rank = rank; c->world = world;
-    unsigned long long h = 1469598103934665603ULL;
-    for (int i = 0; i < VLGP_UNIQUE_ID_BYTES; ++i) h = (h ^ (unsigned char)id[i]) * 1099511628211ULL;
-    snprintf(c->name, sizeof(c->name), "/vlgp_hx_%016llx", h);
-    int fd = shm_open(c->name, O_CREAT | O_RDWR, 0600);
-    if (fd < 0) { delete c; return nullptr; }
-    if (ftruncate(fd, sizeof(HxRegion)) != 0) { close(fd); delete c; return nullptr; }
-    void* p = mmap(nullptr, sizeof(HxRegion), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (p == MAP_FAILED) { delete c; return nullptr; }
-    c->reg = (HxRegion*)p;  // a fresh segment is zero-filled
-    return c;
-}
-static void hx_close(HxComm* c) {
-    if (!c) return;
-    if (c->reg) munmap((void*)c->reg, sizeof(HxRegion));
-    if (c->rank == 0) shm_unlink(c->name);
-    delete c;
-}
-static bool hx_wait(const long long* p, long long want) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        if (__atomic_load_n(p, __ATOMIC_ACQUIRE) >= want) return true;
-        if ((spins & 0xffff) == 0xffff &&
-            std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) return false;
-    }
-}
-int vlgp_hx_allreduce(vlgp_ctx* ctx, double* vals, int n) {
-    HxComm* c = (HxComm*)ctx->hx;
-    if (!c) return vlgp_fail(ctx, VLGP_ERR_STATE, "no host exchange segment");
-    if (n < 0 || n > HX_MAX_VALS) return vlgp_fail(ctx, VLGP_ERR_ARG, "host exchange of %d values", n);
-    const long long s = ++c->seq;
-    HxRegion* R = c->reg;
-    for (int k = 0; k < c->world; ++k)  // nobody may still be reading my slot from the previous round
-        if (!hx_wait(&R->done[k][0], s - 1)) return vlgp_fail(ctx, VLGP_ERR_COMM, "host exchange: rank %d is not responding", k);
-    for (int i = 0; i < n; ++i) R->slot[c->rank][i] = vals[i];
-    __atomic_store_n(&R->ready[c->rank][0], s, __ATOMIC_RELEASE);
-    for (int k = 0; k < c->world; ++k)
-        if (!hx_wait(&R->ready[k][0], s)) return vlgp_fail(ctx, VLGP_ERR_COMM, "host exchange: rank %d is not responding", k);
-    double sum[HX_MAX_VALS];
-    for (int i = 0; i < n; ++i) sum[i] = 0.0;
-    for (int k = 0; k < c->world; ++k)  // fixed rank order
-        for (int i = 0; i < n; ++i) sum[i] += R->slot[k][i];
-    __atomic_store_n(&R->done[c->rank][0], s, __ATOMIC_RELEASE);
-    for (int i = 0; i < n; ++i) vals[i] = sum[i];
-    return VLGP_OK;
-}
-
-int vlgp_allreduce(vlgp_ctx* ctx, double* d_buf, int64_t n) {
-    if (ctx->shm) return shm_allreduce(ctx, (ShmComm*)ctx->shm, ctx->stream, d_buf, n);
-    if (!ctx->comm) return VLGP_OK;
-    const int rc = g_rccl.all_reduce(d_buf, d_buf, (size_t)n, /*ncclDouble*/ 8, /*ncclSum*/ 0, ctx->comm, ctx->stream);
-    if (rc != 0)
-        return vlgp_fail(ctx, VLGP_ERR_COMM, "ncclAllReduce failed: %s", g_rccl.errstr ? g_rccl.errstr(rc) : "?");
-    return VLGP_OK;
-}
-
-int vlgp_allreduce_m(vlgp_ctx* ctx, double* d_buf, int64_t n) {
-    if (ctx->shm_m) return shm_allreduce(ctx, (ShmComm*)ctx->shm_m, ctx->mstream, d_buf, n);
-    if (!ctx->comm_m) {
-        if (ctx->shm) return vlgp_fail(ctx, VLGP_ERR_STATE, "multi-rank M-step needs vlgp_comm_init_aux");
-        if (ctx->comm)
-            return vlgp_fail(ctx, VLGP_ERR_STATE, "multi-rank M-step needs the second communicator (vlgp_comm_init_aux)");
-        return VLGP_OK;
-    }
-    const int rc = g_rccl.all_reduce(d_buf, d_buf, (size_t)n, /*ncclDouble*/ 8, /*ncclSum*/ 0, ctx->comm_m, ctx->mstream);
-    if (rc != 0)
-        return vlgp_fail(ctx, VLGP_ERR_COMM, "ncclAllReduce (M-step lane) failed: %s", g_rccl.errstr ? g_rccl.errstr(rc) : "?");
-    return VLGP_OK;
-}
-
-extern "C" int vlgp_comm_unique_id(char id[VLGP_UNIQUE_ID_BYTES]) {
-    if (shm_mode()) {  // any bytes unique to this call will do
-        memset(id, 0, VLGP_UNIQUE_ID_BYTES);
-        static int counter = 0;
-        snprintf(id, VLGP_UNIQUE_ID_BYTES, "shm-%d-%d-%ld", (int)getpid(), counter++, (long)time(nullptr));
-        return VLGP_OK;
-    }
-    CHK(rccl_load(nullptr));
-    rccl_uid u;
-    const int rc = g_rccl.get_uid(&u);
-    if (rc != 0) return vlgp_fail(nullptr, VLGP_ERR_COMM, "ncclGetUniqueId failed (%d)", rc);
-    memcpy(id, u.internal, VLGP_UNIQUE_ID_BYTES);
-    return VLGP_OK;
-}
-
-extern "C" int vlgp_comm_init(vlgp_ctx* ctx, const char id[VLGP_UNIQUE_ID_BYTES], int rank, int world) {
-    NEED_CTX(ctx);
-    if (world < 1 || rank < 0 || rank >= world) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad rank/world %d/%d", rank, world);
-    ctx->rank = rank;
-    ctx->world = world;
-    for (auto& us : ctx->sets) us.rows_all_ranks = 0.0;  // row totals exchanged under another communicator are stale
-    // a single rank needs no communicator; VLGP_FORCE_RCCL=1 builds one anyway so
-    // that the RCCL plumbing can be exercised on a one-GPU box (tests)
-    if (world == 1 && !getenv("VLGP_FORCE_RCCL")) return VLGP_OK;
-    if (world > 1 && !getenv("VLGP_NO_HOST_EXCHANGE")) {
-        hx_close((HxComm*)ctx->hx);  // a second vlgp_comm_init (transport fallback) starts over
-        ctx->hx = hx_open(id, rank, world);  // optional: without it the H-step rounds use the device all-reduce
-    }
-    if (shm_mode()) {
-        ctx->shm = shm_open_comm(id, rank, world);
-        if (!ctx->shm) return vlgp_fail(ctx, VLGP_ERR_COMM, "cannot open the shared-memory test transport");
-        return VLGP_OK;
-    }
-    CHK(rccl_load(ctx));
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    rccl_uid u;
-    memcpy(u.internal, id, VLGP_UNIQUE_ID_BYTES);
-    const int rc = g_rccl.init_rank(&ctx->comm, world, u, rank);
-    if (rc != 0)
-        return vlgp_fail(ctx, VLGP_ERR_COMM, "ncclCommInitRank failed: %s", g_rccl.errstr ? g_rccl.errstr(rc) : "?");
-    return VLGP_OK;
-}
-
-extern "C" int vlgp_comm_init_aux(vlgp_ctx* ctx, const char id[VLGP_UNIQUE_ID_BYTES]) {
-    NEED_CTX(ctx);
-    if (ctx->world == 1 && !getenv("VLGP_FORCE_RCCL")) return VLGP_OK;
-    if (shm_mode()) {
-        if (!ctx->shm) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_comm_init must precede vlgp_comm_init_aux");
-        ctx->shm_m = shm_open_comm(id, ctx->rank, ctx->world);
-        if (!ctx->shm_m) return vlgp_fail(ctx, VLGP_ERR_COMM, "cannot open the shared-memory test transport (aux)");
-        return VLGP_OK;
-    }
-    if (!ctx->comm) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_comm_init must precede vlgp_comm_init_aux");
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    rccl_uid u;
-    memcpy(u.internal, id, VLGP_UNIQUE_ID_BYTES);
-    const int rc = g_rccl.init_rank(&ctx->comm_m, ctx->world, u, ctx->rank);
-    if (rc != 0)
-        return vlgp_fail(ctx, VLGP_ERR_COMM, "ncclCommInitRank (aux) failed: %s", g_rccl.errstr ? g_rccl.errstr(rc) : "?");
-    return VLGP_OK;
-}
-
-extern "C" int vlgp_comm_host_exchange(vlgp_ctx* ctx) { return ctx && ctx->hx ? 1 : 0; }
-extern "C" int vlgp_comm_transport(vlgp_ctx* ctx) { return !ctx ? 0 : (ctx->comm ? 1 : (ctx->shm ? 2 : 0)); }
-
-extern "C" int vlgp_comm_rccl_ranks(vlgp_ctx* ctx, int* main_lane, int* m_lane) {
-    NEED_CTX(ctx);
-    if (!main_lane || !m_lane) return vlgp_fail(ctx, VLGP_ERR_ARG, "null out");
-    *main_lane = 0;
-    *m_lane = 0;
-    if (ctx->comm && g_rccl.count && g_rccl.count(ctx->comm, main_lane) != 0) *main_lane = -1;
-    if (ctx->comm_m && g_rccl.count && g_rccl.count(ctx->comm_m, m_lane) != 0) *m_lane = -1;
-    return VLGP_OK;
-}
-
-extern "C" int vlgp_comm_allreduce_host(vlgp_ctx* ctx, double* buf, int n) {
-    NEED_CTX(ctx);
-    if (n < 0 || (n > 0 && !buf)) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad allreduce arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->dev));
-    if (!ctx->comm && !ctx->shm) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return VLGP_OK;
-    }
-    const int m = n > 0 ? n : 1;
-    CHK(vlgp_ensure_work(ctx, m + 8));
-    CHK(vlgp_ensure_pinned(ctx, m + 8));
-    if (n > 0) memcpy(ctx->h_pinned, buf, sizeof(double) * n);
-    else ctx->h_pinned[0] = 0.0;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_work, ctx->h_pinned, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
-    CHK(vlgp_allreduce(ctx, ctx->d_work, m));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_work, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (n > 0) memcpy(buf, ctx->h_pinned, sizeof(double) * n);
-    return VLGP_OK;
-}
-
 // ---- lifetime --------------------------------------------------------------
 extern "C" int vlgp_abi_version(void) { return VLGP_ABI_VERSION; }
 
@@ -629,6 +306,8 @@ extern "C" int vlgp_create(int device, int N, int L, int P, int R, const uint8_t
         CREATE_CHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
         CREATE_CHK(hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio_hi));
         CREATE_CHK(hipStreamCreateWithPriority(&ctx->mstream, hipStreamNonBlocking, prio_lo));
+        ctx->lanes[LANE_MAIN].stream = ctx->stream;
+        ctx->lanes[LANE_M].stream = ctx->mstream;
     }
     CREATE_CHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     CREATE_CHK(hipEventCreate(&ctx->ev_m_start));
@@ -677,11 +356,7 @@ extern "C" int vlgp_destroy(vlgp_ctx* ctx) {
     ctx->m_graph_exec = nullptr;
     ctx->m_pending = false;
     prof_drain(ctx);
-    hx_close((HxComm*)ctx->hx);
-    shm_close_comm((ShmComm*)ctx->shm_m);
-    shm_close_comm((ShmComm*)ctx->shm);
-    if (ctx->comm_m && g_rccl.destroy) g_rccl.destroy(ctx->comm_m);
-    if (ctx->comm && g_rccl.destroy) g_rccl.destroy(ctx->comm);
+    vlgp_comm_close(ctx);
     // aliased sets first, then owners
     for (int pass = 0; pass < 2; ++pass)
         for (auto& us : ctx->sets)
@@ -1744,7 +1419,7 @@ extern "C" int vlgp_latent_moments(vlgp_ctx* ctx, int set, double* sum1, double*
         if (ctx->world > 1) {
             CHK(vlgp_ensure_work(ctx, 8));
             HIPCHK(ctx, hipMemcpy(ctx->d_work, &c, sizeof(double), hipMemcpyHostToDevice));
-            CHK(vlgp_allreduce(ctx, ctx->d_work, 1));
+            CHK(vlgp_allreduce(ctx, LANE_MAIN, ctx->d_work, 1));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             HIPCHK(ctx, hipMemcpy(&c, ctx->d_work, sizeof(double), hipMemcpyDeviceToHost));
         }

@@ -149,6 +149,17 @@ struct Switches {
 };
 void vlgp_read_switches(struct vlgp_ctx* ctx);
 
+// One lane of collectives: an RCCL communicator or the shared-memory test transport (VLGP_COMM_TRANSPORT=shm), neither on
+// a single rank, and the stream its all-reduces are enqueued on.
+struct HostExchange;
+enum { LANE_MAIN = 0, LANE_M = 1 };
+struct CommLane {
+    void* rccl = nullptr;         // ncclComm_t
+    HostExchange* shm = nullptr;
+    hipStream_t stream = nullptr; // vlgp_ctx::stream / mstream
+    bool open() const { return rccl || shm; }
+};
+
 struct ProfSlot {
     int64_t launches = 0;
     double ms = 0.0;
@@ -188,7 +199,6 @@ struct vlgp_ctx {
     double* d_work_m = nullptr;
     int64_t work_m_len = 0;
     int* d_fail_m = nullptr;
-    void* comm_m = nullptr;       // its own ncclComm_t (collectives of one communicator must not interleave)
     hipEvent_t ev_fork = nullptr, ev_m_start = nullptr, ev_m_done = nullptr;
     bool m_pending = false;
     // single rank: the M-step's launch sequence (52 launches at Mniter = 25) as an instantiated hipGraph, replayed while
@@ -242,11 +252,9 @@ struct vlgp_ctx {
     struct PendingProf { int kind; hipEvent_t a, b; double units; bool done; };
     std::vector<PendingProf> pending;
 
-    // RCCL
-    void* comm = nullptr;         // ncclComm_t
-    void* shm = nullptr;          // shared-memory test transport (VLGP_COMM_TRANSPORT=shm), main lane
-    void* shm_m = nullptr;        // ... M-step lane
-    void* hx = nullptr;           // host-side exchange segment for the H-step round sums (single node)
+    // communication (comm.hip): the main lane and the M-step lane's own (collectives of one communicator must not interleave)
+    CommLane lanes[2];
+    HostExchange* hx = nullptr;   // host-side exchange segment for the H-step round sums (single node)
     int rank = 0, world = 1;
 
     // second lane of the split E-step (estep_split.hip): half of the unit set runs its sweeps here
@@ -306,6 +314,8 @@ int vlgp_fail(vlgp_ctx* ctx, int code, const char* fmt, ...);
             return vlgp_fail(ctx, VLGP_ERR_HIP, "%s failed: %s (%s:%d)", #call,    \
                              hipGetErrorString(e__), __FILE__, __LINE__);          \
     } while (0)
+#define NEED_CTX(ctx) \
+    if (!(ctx)) return vlgp_fail(nullptr, VLGP_ERR_ARG, "null handle")
 #define CHK(expr)                 \
     do {                          \
         int rc__ = (expr);        \
@@ -316,9 +326,9 @@ int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n_doubles);
 int vlgp_ensure_pinned(vlgp_ctx* ctx, int64_t n_doubles);
 // dynamic-LDS ceiling of kernel fn raised to `bytes`, once per handle: the attribute is per device, one handle = one device
 int vlgp_raise_lds(vlgp_ctx* ctx, const void* fn, int bytes);
-int vlgp_allreduce(vlgp_ctx* ctx, double* d_buf, int64_t n);  // in place, sum, on ctx->stream
+int vlgp_allreduce(vlgp_ctx* ctx, int lane, double* d_buf, int64_t n);  // in place, sum, on the lane's stream
 int vlgp_hx_allreduce(vlgp_ctx* ctx, double* h_vals, int n);   // host values, n <= 64, rank-order sum; needs ctx->hx
-int vlgp_allreduce_m(vlgp_ctx* ctx, double* d_buf, int64_t n);  // same on the M-step lane (comm_m, mstream)
+void vlgp_comm_close(vlgp_ctx* ctx);  // both lanes and the host exchange
 int vlgp_ensure_work_m(vlgp_ctx* ctx, int64_t n_doubles);
 int vlgp_join_m(vlgp_ctx* ctx);  // wait for a pending asynchronous M-step
 int vlgp_bind_priors(vlgp_ctx* ctx, UnitSet& us);             // (re)build d_unit_prior

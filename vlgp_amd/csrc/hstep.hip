@@ -1421,7 +1421,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                     }
                 }
             } else {
-                CHK(vlgp_allreduce(ctx, W + o_red, 2LL * n_eval));
+                CHK(vlgp_allreduce(ctx, LANE_MAIN, W + o_red, 2LL * n_eval));
                 HIPCHK(ctx, hipMemcpyAsync(hres, W + o_red, sizeof(double) * 3 * n_eval, hipMemcpyDeviceToHost, ctx->stream));
                 HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             }
@@ -1512,7 +1512,7 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
     }
     hipLaunchKernelGGL(hstep_reduce_kernel, dim3(n_eval), dim3(256), 0, ctx->stream, M, W + o_out, W + o_red);
     HIPCHK(ctx, hipGetLastError());
-    CHK(vlgp_allreduce(ctx, W + o_red, 2LL * n_eval));
+    CHK(vlgp_allreduce(ctx, LANE_MAIN, W + o_red, 2LL * n_eval));
     double* hres = hp + 4 * n_eval + 8;
     HIPCHK(ctx, hipMemcpyAsync(hres, W + o_red, sizeof(double) * 2 * n_eval, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

@@ -1129,10 +1129,9 @@ static int latent_moments_st(vlgp_ctx* ctx, UnitSet& us, double* d_partial, doub
     HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
 }
-static int latent_moments(vlgp_ctx* ctx, UnitSet& us, double* d_partial, double* d_out, bool mlane) {
-    CHK(latent_moments_st(ctx, us, d_partial, d_out, mlane ? ctx->mstream : ctx->stream));
-    const int K = tri(ctx->L) + 3 * ctx->L + 1;
-    return mlane ? vlgp_allreduce_m(ctx, d_out, K) : vlgp_allreduce(ctx, d_out, K);
+static int latent_moments(vlgp_ctx* ctx, UnitSet& us, double* d_partial, double* d_out, int lane) {
+    CHK(latent_moments_st(ctx, us, d_partial, d_out, ctx->lanes[lane].stream));
+    return vlgp_allreduce(ctx, lane, d_out, tri(ctx->L) + 3 * ctx->L + 1);
 }
 
 // result (K doubles, all-reduced) is left at the head of ctx->d_work; the partials use its tail.  The
@@ -1142,7 +1141,7 @@ int launch_moments(vlgp_ctx* ctx, UnitSet& us) {
     const int K = tri(L) + 3 * L + 1;
     CHK(vlgp_ensure_work(ctx, 256LL * K + K + 64));
     double* d_partial = ctx->d_work + K + 64;
-    return latent_moments(ctx, us, d_partial, ctx->d_work, false);
+    return latent_moments(ctx, us, d_partial, ctx->d_work, LANE_MAIN);
 }
 
 int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double eps, double lr,
@@ -1219,13 +1218,13 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
         hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n + 63) / 64)), dim3(512), 0, st,
                            d_part, g.G, n, dst);
         HIPCHK(ctx, hipGetLastError());
-        return vlgp_allreduce_m(ctx, dst, n);
+        return vlgp_allreduce(ctx, LANE_M, dst, n);
     };
 
     // sweep-invariant moments
     CHK(launch_accum(ctx, K_PREP | km, g, A, d_cache));
     CHK(reduce_to(Kp, d_prep));
-    CHK(latent_moments(ctx, us, d_part, d_lat, true));
+    CHK(latent_moments(ctx, us, d_part, d_lat, LANE_M));
     double total_rows = (double)us.rows;
     if (ctx->world > 1 && us.rows_all_ranks > 0.0) {
         total_rows = us.rows_all_ranks;  // fixed at upload: exchanged once per set, not once per M-step
@@ -1234,7 +1233,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
         double h = total_rows;
         HIPCHK(ctx, hipMemcpyAsync(d_lat + Kl, &h, sizeof(double), hipMemcpyHostToDevice, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
-        CHK(vlgp_allreduce_m(ctx, d_lat + Kl, 1));
+        CHK(vlgp_allreduce(ctx, LANE_M, d_lat + Kl, 1));
         HIPCHK(ctx, hipMemcpyAsync(&h, d_lat + Kl, sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         total_rows = h;
