@@ -201,6 +201,25 @@ int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell,
  * and nothing vlgp_hstep_prepare built.  Fixed-order reductions, no atomics: the same bits on every run. */
 int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
                   const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed);
+/* Importance weights of the marginal likelihood log p(y_unit) of every unit of a set that is not replicated (DESIGN.md
+ * 4.6: VLGP_ERR_STATE otherwise), the fitted posterior as proposal (the IWAE estimate).  Per (unit, latent), with G, mu, v,
+ * w, g, H = Lc Lc' and m = H^-1 G' (g + w o mu) exactly as in vlgp_forecast (vb == 0 drops the v term of g: the Laplace
+ * approximation of a MAP fit), draw k of n_samples takes eps_k (r standard normals supplied by the caller):
+ *   d = Lc^-T eps_k,  beta_k = m + d,  x_k[t, l] = G[t, :] . beta_k
+ *   c[u, l, k] = -1/2 |beta_k|^2 + 1/2 |eps_k|^2 - 1/2 log det H       (log N(beta; 0, I) - log N(beta; m, H^-1))
+ *   ll[u, k] = sum_t sum_n log p(y[t, n] | eta = a_n . x_k[t] + (b x)_tn)   (no v term: x_k is a sample)
+ *     Poisson y eta - trunc_exp(eta) - lgamma(y + 1);   Gaussian -log(2 pi noise_n) / 2 - (y - eta)^2 / (2 noise_n)
+ *   log_w[u, k] = ll[u, k] + sum_l c[u, l, k]
+ * eps is (units, L, R, n_samples), the sample index contiguous; rows >= r of a (unit, latent) are never read.  log_w
+ * (units, n_samples); parts (units, n_samples, 2) = {ll, sum_l c}, whose two entries add to log_w, or NULL.  mean_k
+ * exp(log_w[u, k]) is unbiased for p(y_u) whatever mu, v, w hold: they decide its variance alone.  A pivot of H that is not
+ * positive and finite makes the unit's log_w NaN and is counted in *n_failed (may be NULL).  The samples are walked 64 at
+ * a time: the call's device memory does not grow with n_samples, and sample k's numbers are the same bits whatever
+ * n_samples is.  n_samples < 1 or a null eps or log_w: VLGP_ERR_ARG, the message naming the offender; parameters not
+ * set or a length without a prior: VLGP_ERR_STATE.  Waits for a pending M-step and norms pass; changes no unit state, no
+ * parameter and nothing vlgp_hstep_prepare built.  Fixed-order sums, no atomics: the same bits on every run. */
+int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* eps, double* log_w, double* parts,
+                  int* n_failed);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

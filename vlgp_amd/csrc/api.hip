@@ -137,6 +137,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_latent_moments, SET_FIT | SET_SOURCE, nullptr)                                                             \
     X(vlgp_elbo, NOT_REPLICATED, nullptr)                                                                             \
     X(vlgp_forecast, NOT_REPLICATED, nullptr) /* (a cut is refused once its priors are bound: see there) */           \
+    X(vlgp_marginal, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_stash_mu, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_set_overlaps, NOT_REPLICATED, nullptr) /* (and equal-length units that are no tiling cut: see there) */    \
     X(vlgp_unshare_mu, NOT_REPLICATED, nullptr)                                                                       \
@@ -832,6 +833,60 @@ extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, cons
         if (e == hipSuccess) e = count_flags(ctx, d_flag, tasks, n_failed);
         if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_forecast copy-out failed: %s", hipGetErrorString(e));
     }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---- importance weights of the marginal likelihood -----------------------------------
+extern "C" int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* eps, double* log_w,
+                             double* parts, int* n_failed) {
+    UnitSet* us = nullptr;
+    CHK(open_posterior(ctx, set, admit_vlgp_marginal, &us));
+    if (n_samples < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal: n_samples = %d, need >= 1", n_samples);
+    if (!eps || !log_w) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal needs eps and log_w");
+    const int L = ctx->L, R = ctx->R, M = us->M;
+    const int64_t tasks = (int64_t)M * L, K = n_samples;
+    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal: too many (unit, latent) pairs");
+    if (n_failed) *n_failed = 0;
+    const int rp = set_rank_max(ctx, *us);
+    const int tile_rows = marginal_tile_rows(L);
+    std::vector<int64_t> tile_off((size_t)M + 1, 0);  // first row tile of each unit
+    for (int m = 0; m < M; ++m) tile_off[(size_t)m + 1] = tile_off[(size_t)m] + (us->off[m + 1] - us->off[m] + tile_rows - 1) / tile_rows;
+    const int64_t n_tiles = tile_off[(size_t)M];
+    // one device block of the call's own, for 64 samples at a time whatever n_samples is:
+    // z | eps | beta | c | tile partials | log_w | parts | tile_off | flags
+    const int64_t o_eps = us->rows * L, o_beta = o_eps + tasks * R * 64, o_c = o_beta + tasks * R * 64, o_part = o_c + tasks * 64;
+    const int64_t o_lw = o_part + n_tiles * 64, o_parts = o_lw + (int64_t)M * 64, o_tab = o_parts + (int64_t)M * 128;
+    const int64_t o_flag = o_tab + M + 1, need = o_flag + (tasks + 1) / 2;
+    double* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
+    int* d_flag = reinterpret_cast<int*>(d + o_flag);
+    int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
+    int rc = VLGP_OK;
+    hipError_t e = hipMemcpyAsync(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal copy-in failed: %s", hipGetErrorString(e));
+    if (rc == VLGP_OK) rc = launch_forecast_z(ctx, *us, vb, d);
+    const size_t dbl = sizeof(double);
+    for (int64_t k0 = 0; k0 < K && rc == VLGP_OK; k0 += 64) {  // (the copies of a chunk and its kernels are stream-ordered)
+        const int kc = (int)std::min<int64_t>(64, K - k0);
+        e = hipMemcpy2DAsync(d + o_eps, 64 * dbl, eps + k0, (size_t)K * dbl, (size_t)kc * dbl, (size_t)(tasks * R),
+                             hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal copy-in failed: %s", hipGetErrorString(e));
+        if (rc == VLGP_OK)
+            rc = launch_marginal(ctx, *us, rp, kc, d, d + o_eps, d + o_beta, d + o_c, d + o_part, tile_rows, d_tab, n_tiles,
+                                 d + o_lw, d + o_parts, d_flag);
+        if (rc != VLGP_OK) break;
+        e = hipMemcpy2DAsync(log_w + k0, (size_t)K * dbl, d + o_lw, 64 * dbl, (size_t)kc * dbl, (size_t)M, hipMemcpyDeviceToHost,
+                             ctx->stream);
+        if (e == hipSuccess && parts)
+            e = hipMemcpy2DAsync(parts + 2 * k0, (size_t)K * 2 * dbl, d + o_parts, 128 * dbl, (size_t)kc * 2 * dbl, (size_t)M,
+                                 hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal copy-out failed: %s", hipGetErrorString(e));
+    }
+    if (rc == VLGP_OK && count_flags(ctx, d_flag, tasks, n_failed) != hipSuccess)
+        rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal: reading the flags failed");
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
     return rc;

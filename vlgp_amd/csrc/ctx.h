@@ -401,3 +401,12 @@ int launch_elbo(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_part, doub
 int launch_forecast(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_z, const int64_t* d_ext_off,
                     const int64_t* d_gx_off, const double* d_G_ext, double* d_mu_ext, double* d_v_ext, double* d_terms,
                     int* d_flag);
+int launch_forecast_z(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_z);  // its row pass alone: z = g + w o mu
+// importance weights of a plain set (marginal.hip): kc <= 64 joint draws of every latent path from the weight-space
+// posterior N(m, H^-1) built from d_z (launch_forecast_z), d_eps (M, L, R, 64) standard normals, sample contiguous.
+// Workspace: d_beta (M, L, R, 64), d_c (M, L, 64), d_part (tiles, 64); tile_rows from marginal_tile_rows(L), d_tile_off
+// (M + 1): first row tile of each unit.  Out: d_logw (M, 64), d_parts (M, 64, 2) = {ll, sum_l c}, d_flag (M, L)
+int marginal_tile_rows(int L);
+int launch_marginal(vlgp_ctx* ctx, UnitSet& us, int rp, int kc, const double* d_z, const double* d_eps, double* d_beta,
+                    double* d_c, double* d_part, int tile_rows, const int64_t* d_tile_off, int64_t n_tiles, double* d_logw,
+                    double* d_parts, int* d_flag);

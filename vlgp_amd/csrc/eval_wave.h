@@ -188,6 +188,36 @@ __device__ __forceinline__ double wave_solve_llt(const double* Lc, const double*
     return z;
 }
 
+// The weight-space posterior of one (unit, latent), beta ~ N(m, H^-1): pass 1 over the rows of G in tiles of 64
+// accumulates H = I_r + G' diag(w) G and G'z, then H = Lc Lc' (the factor in the lower triangle of Hm, dinv = 1 / diag Lc)
+// and m = H^-1 G'z, lane k returning entry k.  lds (zeroed here): Hm | tile | wv | zv at the caller's offsets; w, z are
+// the set's (rows, L) columns.  *bad: a pivot was not positive and finite.
+__device__ __forceinline__ double task_weight_posterior(const TaskView& t, int L, const double* w, const double* z, int rs,
+                                                        int lane, double* lds, int n_zero, double* Hm, double* tile,
+                                                        double* wv, double* zv, double* dinv, int* bad) {
+    const int T = t.T, r = t.r;
+    const int j = lane < r ? lane : 0;  // the lane's column (lanes >= r compute on column 0 and store nothing)
+    wave_zero(lds, n_zero, lane);
+    double cj = 0.0;
+    for (int t0 = 0; t0 < T; t0 += EW_TILE) {
+        const int nt = min(EW_TILE, T - t0);
+        stage_rows(t.G, r, r, rs, t0, nt, tile, lane);
+        if (lane < nt) {
+            const int64_t at = (t.r0 + t0 + lane) * L + t.l;
+            wv[lane] = w[at];
+            zv[lane] = z[at];
+        }
+        wave_sync();
+        for (int tt = 0; tt < nt; ++tt) cj = fma(tile[tt * rs + j], zv[tt], cj);
+        accum_gwg<false>(tile, wv, nt, r, rs, j, lane, Hm, nullptr);
+        wave_sync();  // (the tile is overwritten next)
+    }
+    if (lane < r) Hm[lane * rs + lane] += 1.0;
+    wave_sync();
+    *bad = wave_chol(Hm, r, rs, dinv, lane);
+    return wave_solve_llt(Hm, dinv, r, rs, lane < r ? cj : 0.0, lane);
+}
+
 // one staged row . beta
 __device__ __forceinline__ double tile_row_dot(const double* trow, const double* bet, int r) {
     double g = 0.0;

@@ -109,30 +109,11 @@ __global__ void __launch_bounds__(64) forecast_task(ForecastTaskArgs A) {
         return;
     }
     const double* __restrict__ Gx = A.G_ext + A.gx_off[t.u] + (int64_t)l * nx * A.R;
-    const int j = lane < r ? lane : 0;  // the lane's column (lanes >= r compute on column 0 and store nothing)
-    wave_zero(lds, rp * rs + EW_TILE * rs + EW_CH, lane);
 
-    // ---- pass 1: G'WG, G'z ----
-    double cj = 0.0;
-    for (int t0 = 0; t0 < T; t0 += EW_TILE) {
-        const int nt = min(EW_TILE, T - t0);
-        stage_rows(t.G, r, r, rs, t0, nt, tile, lane);
-        if (lane < nt) {
-            const int64_t at = (r0 + t0 + lane) * L + l;
-            wv[lane] = A.w[at];
-            zv[lane] = A.z[at];
-        }
-        wave_sync();
-        for (int tt = 0; tt < nt; ++tt) cj = fma(tile[tt * rs + j], zv[tt], cj);
-        accum_gwg<false>(tile, wv, nt, r, rs, j, lane, Hm, nullptr);
-        wave_sync();  // (the tile is overwritten next)
-    }
-    if (lane < r) Hm[lane * rs + lane] += 1.0;
-    wave_sync();
-
-    // ---- H = Lc Lc', beta = H^-1 G'z ----
-    const int bad = wave_chol(Hm, r, rs, dinv, lane);
-    const double bz = wave_solve_llt(Hm, dinv, r, rs, lane < r ? cj : 0.0, lane);
+    // ---- pass 1: G'WG, G'z; H = Lc Lc', beta = H^-1 G'z ----
+    int bad;
+    const double bz = task_weight_posterior(t, L, A.w, A.z, rs, lane, lds, rp * rs + EW_TILE * rs + EW_CH, Hm, tile, wv, zv,
+                                            dinv, &bad);
     if (lane < r) bet[lane] = bz;
     wave_sync();
 
@@ -188,6 +169,17 @@ __global__ void __launch_bounds__(64) forecast_task(ForecastTaskArgs A) {
 
 }  // namespace
 
+// z = g + w o mu of every (row, latent) into d_z (rows, L): the row pass, which vlgp_marginal shares
+int launch_forecast_z(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_z) {
+    ForecastRowArgs R;
+    R.m = fill_row_model(ctx, us, us, vb);
+    R.w = us.w;
+    R.z = d_z;
+    hipLaunchKernelGGL(forecast_rows, dim3((unsigned)((us.rows + 255) / 256)), dim3(256), 0, ctx->stream, R);
+    HIPCHK(ctx, hipGetLastError());
+    return VLGP_OK;
+}
+
 // d_z: (rows, L) doubles of workspace; d_ext_off (M + 1), d_gx_off (M): see ForecastTaskArgs; d_mu_ext, d_v_ext
 // (sum n_ext, L), d_terms (M, L, 2), d_flag (M, L)
 int launch_forecast(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_z, const int64_t* d_ext_off,
@@ -204,12 +196,7 @@ int launch_forecast(vlgp_ctx* ctx, UnitSet& us, int vb, int rp, double* d_z, con
     const size_t lds = sizeof(double) * (size_t)forecast_lds_doubles(K.rp, K.rs);
     if ((int64_t)lds > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: rank %d needs %zu bytes of LDS", rp, lds);
 
-    ForecastRowArgs R;
-    R.m = fill_row_model(ctx, us, us, vb);
-    R.w = us.w;
-    R.z = d_z;
-    hipLaunchKernelGGL(forecast_rows, dim3((unsigned)((us.rows + 255) / 256)), dim3(256), 0, ctx->stream, R);
-    HIPCHK(ctx, hipGetLastError());
+    CHK(launch_forecast_z(ctx, us, vb, d_z));
 
     K.mu = us.mu; K.w = us.w; K.z = d_z;
     K.ext_off = d_ext_off; K.gx_off = d_gx_off; K.G_ext = d_G_ext;

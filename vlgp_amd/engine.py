@@ -311,6 +311,25 @@ class Engine:
                                         dptr(G_all), dptr(mu_ext), dptr(v_ext), dptr(terms), C.byref(n)))
         return mu_ext, v_ext, terms, n.value
 
+    def marginal(self, set_id, eps, vb=True, want_parts=False):
+        """Importance weights of ``log p(y_unit)`` for every unit of a plain set under joint draws of its latent paths
+        from the fitted posterior (vlgp_marginal).  ``eps``: (units, L, R, n_samples) standard normals, the sample index
+        last; rows beyond a (unit, latent)'s effective rank are not read.  Returns ``(log_w, n_failed, parts)``: log_w
+        (units, n_samples); the number of (unit, latent) pairs whose factorisation failed (their unit's log_w is NaN);
+        with ``want_parts`` (units, n_samples, 2) = the log-likelihood of the draw and the prior-over-proposal term, which
+        add to log_w (else None).  Changes no state."""
+        units, _, _ = self.sets[set_id]
+        eps = _f64(eps)
+        if eps.ndim != 4 or eps.shape[:3] != (units, self.L, self.R) or eps.shape[3] < 1:
+            raise ValueError("eps must be (%d, %d, %d, n_samples >= 1), got %r" % (units, self.L, self.R, eps.shape))
+        K = eps.shape[3]
+        log_w = np.empty((units, K))
+        parts = np.empty((units, K, 2)) if want_parts else None
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_marginal(self.h, int(set_id), int(bool(vb)), K, dptr(eps), dptr(log_w), dptr(parts),
+                                        C.byref(n)))
+        return log_w, n.value, parts
+
     def unit_ranks(self, set_id):
         """(units, L) effective rank of the prior factor each (unit, latent) of the set is bound to."""
         _, _, off = self.sets[set_id]

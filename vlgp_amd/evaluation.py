@@ -72,8 +72,29 @@ factorisation that belong to the unobserved bins, ``mu``, ``v``, ``w`` are the u
 - ``bits_per_spike_past``: bits per spike against a constant rate at the channel's mean count over the HELD-IN rows --
   what is known at prediction time -- NaN where that mean is 0 and for Gaussian channels.
 
-Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``): the results are the same
-bits on every run.
+Marginal likelihood (``marginal_loglik``, ``vlgp_marginal``): the importance-sampling (IWAE) estimate of
+``log p(y_trial)`` with the fitted posterior as proposal.  For one unit of length ``T`` and latent ``l``:
+
+- ``G`` (``T x r``) is the compact prior factor bound to the unit's length; ``mu, v, w`` are the unit's stored columns.
+- ``g``, ``z = g + w o mu``, ``H = I_r + G' diag(w) G = Lc Lc'`` and ``m = H^-1 G' z`` are exactly those of the forward
+  prediction above (``m`` is its ``beta_hat``).  Under MAP the ``v`` term of ``g`` is dropped, and the proposal
+  ``N(m, H^-1)`` is then the Laplace approximation of the MAP fit.
+- draw ``k`` takes ``eps_k`` in ``R^r`` (standard normals supplied by the host), ``d = Lc^-T eps_k`` and
+  ``beta_k = m + d``.
+- ``c[u, l, k] = -1/2 |beta_k|^2 + 1/2 |eps_k|^2 - 1/2 log det H``: ``log N(beta; 0, I) - log N(beta; m, H^-1)``.
+- the path is ``x_k[t, l] = G[t, :] . beta_k``.
+- ``ll[u, k] = sum_t sum_n log p(y[t, n] | eta = a[:, n] . x_k[t] + (b x)_tn)`` with no ``v`` term, because ``x_k`` is a
+  sample: Poisson ``y eta - trunc_exp(eta) - lgamma(y + 1)``; Gaussian
+  ``-1/2 log(2 pi noise[n]) - (y - eta) ** 2 / (2 noise[n])``.
+- ``log_w[u, k] = ll[u, k] + sum_l c[u, l, k]``.
+- per unit ``iwae = logsumexp_k(log_w) - log K``, ``elbo_mc = mean_k log_w`` and ``ess = (sum w)^2 / sum w^2``.
+
+``mean_k w`` is unbiased for ``p(y_u)`` whatever ``mu, v, w`` hold; the stored posterior only decides the variance of the
+estimate, which ``ess`` (between 1 and ``K``) reports: near 1 a single draw carries the sum and ``iwae`` is little more
+than that draw's ``log_w``.
+
+Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``, ``vlgp_marginal``): the
+results are the same bits on every run.
 """
 import contextlib
 import math
@@ -87,7 +108,9 @@ from .util import _per_trial_entries
 
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
            "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
-           "entry_scores", "leave_entries_out", "impute"]
+           "entry_scores", "leave_entries_out", "impute", "marginal_loglik", "weights_summary"]
+
+SAMPLE_CHUNK = 64  # draws per device call: one lane per sample (csrc/marginal.hip)
 
 SET_TEST, SET_FORWARD, SET_REPLICAS = 0, 1, 2
 
@@ -590,3 +613,76 @@ def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0)
         "fp_bps": co_bits_per_spike(ll, ll_null, ny), "fp_bps_past": co_bits_per_spike(ll, ll_null_past, ny),
         "off_fixed_point": off, "n_failed": int(n_failed),
     }
+
+
+def weights_summary(log_w):
+    """Per unit, from importance weights ``log_w`` (units, K) or (K,): ``(iwae, elbo_mc, ess)`` with
+    ``iwae = logsumexp_k(log_w) - log K``, ``elbo_mc = mean_k log_w`` and ``ess = (sum w)^2 / sum w^2`` (pure host code).
+    The largest ``log_w`` of a row is taken out before the exponential, so values near -1e5 lose nothing; a row that
+    holds a NaN gives NaN three times."""
+    log_w = np.asarray(log_w, dtype=float)
+    if log_w.ndim not in (1, 2) or log_w.shape[-1] < 1:
+        raise ValueError("log_w must be (units, K) or (K,) with K >= 1")
+    K = log_w.shape[-1]
+    top = np.max(log_w, axis=-1)  # (NaN where the row holds one)
+    shift = np.where(np.isfinite(top), top, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        w = np.exp(log_w - shift[..., None])
+        s1, s2 = np.sum(w, axis=-1), np.sum(w * w, axis=-1)
+        iwae = shift + np.log(s1) - math.log(K)
+        ess = s1 * s1 / s2
+    bad = np.isnan(top)
+    return np.where(bad, np.nan, iwae), np.where(bad, np.nan, np.mean(log_w, axis=-1)), np.where(bad, np.nan, ess)
+
+
+def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infer=True, n_iter=None, device=0):
+    """Importance-weighted estimate of the marginal log-likelihood ``log p(y_trial)`` of every trial, the fitted
+    posterior as proposal (module docstring for the definitions).
+
+    ``infer=True`` is for held-out trials: the posterior comes from a zero start and ``n_iter`` E-step iterations
+    (default ``config["max_iter"]``), as ``leave_group_out`` infers its own, and the dicts' ``mu, v, w`` are not read.
+    ``infer=False`` is for a fit's own trials and uses their stored ``mu, v, w``.  The normals come from ``rng`` (a
+    ``numpy.random.Generator``; default ``np.random.default_rng(seed)``) in sample chunks of 64: chunk ``c`` is
+    ``rng.standard_normal((n_trials, L, R, min(64, left)))``, so the first samples are the same whatever ``n_samples`` is
+    and host memory does not grow with it.  Trials that carry ``missing`` raise ``ValueError``.  Neither ``params`` nor
+    the trials are modified.
+
+    Returns a dict: ``log_w`` (trials, n_samples); per trial ``iwae``, ``elbo_mc``, ``ess`` (``weights_summary``);
+    ``total``, the sum of ``iwae``; ``elbo``, the deterministic ``vlgp_elbo`` value of the same posterior, and
+    ``gap = total - elbo`` (NaN under MAP, where there is no bound); ``marginal_bps = (total - LL_null) /
+    (n_spikes ln 2)`` with ``LL_null`` the constant-rate null of ``bits_per_spike`` over all evaluated rows, NaN unless
+    every channel is Poisson; ``n_failed`` (failed E-step updates plus (trial, latent) pairs whose ``H`` could not be
+    factored: such a trial's ``log_w`` is NaN, and so is every number it enters)."""
+    _no_missing(trials, "marginal_loglik")
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
+        raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
+    K, L, R = int(n_samples), int(params["zdim"]), int(params["rank"])
+    vb = config["method"] == "VB"
+    rng = np.random.default_rng(seed) if rng is None else rng
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    if infer:
+        units = _zero_start(trials, L)
+    else:
+        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
+                  **{k: tr[k] if tr.get(k) is not None else np.zeros((T, L)) for k in ("v", "w")}}
+                 for tr, T in zip(trials, lengths)]
+    log_w = np.empty((len(trials), K))
+    with _resident(trials, params, units, device) as eng:
+        n_failed = 0
+        if infer:
+            n_failed = eng.estep(SET_TEST, int(config["max_iter"] if n_iter is None else n_iter), config["dmu_bound"], vb)
+        for k0 in range(0, K, SAMPLE_CHUNK):
+            kc = min(SAMPLE_CHUNK, K - k0)
+            log_w[:, k0:k0 + kc], bad, _ = eng.marginal(SET_TEST, rng.standard_normal((len(trials), L, R, kc)), vb=vb)
+        bound = elbo_from_terms(*eng.elbo(SET_TEST, vb=vb)[:2], eng.unit_ranks(SET_TEST), vb=vb)["elbo"]
+        sums, _ = eng.loglik(SET_TEST, vb=vb)
+        gauss = eng.gauss.copy()
+    iwae, elbo_mc, ess = weights_summary(log_w)
+    total = float(np.sum(iwae))
+    _, ll_null, ny, _ = bits_per_spike(sums, sum(lengths), gauss)
+    if gauss.any() or not np.sum(ny) > 0:
+        bps = float("nan")
+    else:
+        bps = float((total - np.sum(ll_null)) / (np.sum(ny) * math.log(2.0)))
+    return {"log_w": log_w, "iwae": iwae, "elbo_mc": elbo_mc, "ess": ess, "total": total, "elbo": bound,
+            "gap": total - bound, "marginal_bps": bps, "n_failed": int(n_failed) + int(bad)}

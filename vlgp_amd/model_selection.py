@@ -8,11 +8,15 @@ once and shared by every candidate, so the candidates are compared on paired fol
 With ``score="speckled_bps"`` the held-out trials are scored by ``evaluation.leave_entries_out`` instead: folds of single
 (bin, channel) entries are left out of the inference and predicted (the reference's ``gmap_speckled_cv`` scheme).  The fit
 itself sees whole training trials, never a mask: the trials are held out, the speckle is applied to the test trials.
+
+With ``score="marginal_bps"`` the held-out trials are scored as a whole by ``evaluation.marginal_loglik``: the
+importance-weighted marginal likelihood in bits per spike.  Nothing is left out of the inference and no replica is made,
+so the score has no limit on the number of latents.
 """
 import numpy as np
 
 from .api import fit
-from .evaluation import channel_folds, leave_entries_out, leave_group_out
+from .evaluation import channel_folds, leave_entries_out, leave_group_out, marginal_loglik
 
 __all__ = ["cross_validate", "trial_folds"]
 
@@ -80,9 +84,17 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
     ``score="speckled_bps"`` scores every trial fold with ``leave_entries_out(n_folds=n_channel_folds, seed=seed)``
     instead (the entry folds depend on the fold's row count alone, so the candidates still share them).  The dict then
     holds ``speckled_bps`` and ``mean_speckled_bps`` where the default has ``co_bps`` and ``mean_co_bps``, ``score``, and
-    no ``channel_folds``; ``best`` follows ``mean_speckled_bps``."""
-    if score not in ("co_bps", "speckled_bps"):
-        raise ValueError("score must be 'co_bps' or 'speckled_bps', got %r" % (score,))
+    no ``channel_folds``; ``best`` follows ``mean_speckled_bps``.
+
+    ``score="marginal_bps"`` scores every trial fold with ``marginal_loglik(n_samples=n_channel_folds * 16, seed=seed)``:
+    this score has no channel folds, so ``n_channel_folds`` sets the number of draws instead -- 16 for every replica the
+    other scores would have inferred, 80 at the default (``marginal_loglik``'s own default is 64).  The
+    dict holds ``marginal_bps`` (candidates, trial folds) and ``mean_marginal_bps``, ``ess_min`` (candidates, trial
+    folds), the smallest per-trial effective sample size of the fold -- near 1 the fold's estimate rests on single
+    draws and should not be trusted --, ``n_failed``, ``best``, ``errors`` and ``score``; no ``channel_folds`` and no
+    per-channel ``bits_per_spike``."""
+    if score not in ("co_bps", "speckled_bps", "marginal_bps"):
+        raise ValueError("score must be 'co_bps', 'speckled_bps' or 'marginal_bps', got %r" % (score,))
     if "comm" in fit_kwargs:
         raise ValueError("cross_validate runs on one process: it takes no comm")
     n_factors_list = [int(n) for n in n_factors_list]
@@ -90,12 +102,13 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
         raise ValueError("n_factors_list must hold positive integers")
     N = int(trials[0]["y"].shape[1])
     t_folds = trial_folds(len(trials), n_trial_folds, seed)
-    speckled = score == "speckled_bps"
-    c_folds = None if speckled else channel_folds(N, n_channel_folds, seed)
-    order = np.arange(N) if speckled else np.argsort([c for g in c_folds for c in g])  # channel-list -> plain order
+    speckled, marginal = score == "speckled_bps", score == "marginal_bps"
+    c_folds = None if speckled or marginal else channel_folds(N, n_channel_folds, seed)
+    order = np.arange(N) if c_folds is None else np.argsort([c for g in c_folds for c in g])  # channel-list -> plain order
     shape = (len(n_factors_list), len(t_folds))
     co_bps = np.full(shape, np.nan)
     bps = np.full(shape + (N,), np.nan)
+    ess_min = np.full(shape, np.nan)
     n_failed = np.zeros(shape, dtype=int)
     errors = []
     for f, test_idx in enumerate(t_folds):
@@ -108,7 +121,10 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
         for c, n in enumerate(n_factors_list):
             try:
                 fitted = _seeded_fit(seed, _fresh(trials, train_idx), n, device=device, verbose=False, **fold_kwargs)
-                if speckled:
+                if marginal:
+                    got = marginal_loglik(_fresh(trials, test_idx), fitted["params"], fitted["config"],
+                                          n_samples=int(n_channel_folds) * 16, seed=seed, n_iter=n_iter, device=device)
+                elif speckled:
                     got = leave_entries_out(_fresh(trials, test_idx), fitted["params"], fitted["config"],
                                             n_folds=n_channel_folds, seed=seed, n_iter=n_iter, device=device)
                 else:
@@ -118,9 +134,16 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
                 errors.append((n, f, "%s: %s" % (type(err).__name__, err)))
                 continue
             co_bps[c, f] = got[score]
-            bps[c, f] = got["bits_per_spike"][order]
             n_failed[c, f] = got["n_failed"]
+            if marginal:
+                ess_min[c, f] = np.min(got["ess"])
+            else:
+                bps[c, f] = got["bits_per_spike"][order]
     mean = np.array([np.mean(row) for row in co_bps])  # (NaN as soon as one fold of the candidate failed)
+    if marginal:
+        return {"n_factors": n_factors_list, "trial_folds": t_folds, "score": score, "marginal_bps": co_bps,
+                "ess_min": ess_min, "n_failed": n_failed, "mean_marginal_bps": mean,
+                "best": best_candidate(n_factors_list, mean), "errors": errors}
     if speckled:
         return {"n_factors": n_factors_list, "trial_folds": t_folds, "score": score, "speckled_bps": co_bps,
                 "bits_per_spike": bps, "n_failed": n_failed, "mean_speckled_bps": mean,
