@@ -220,6 +220,36 @@ int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* leng
  * parameter and nothing vlgp_hstep_prepare built.  Fixed-order sums, no atomics: the same bits on every run. */
 int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* eps, double* log_w, double* parts,
                   int* n_failed);
+/* Posterior-predictive log density of every observation under the set's current posterior: where vlgp_loglik scores an
+ * entry with the plug-in density p(y | E_q[rate]), this integrates the likelihood over the posterior of its linear
+ * predictor,
+ *   lpd[t, n] = log int p(y[t, n] | eta) N(eta; m, s2) d eta,   m = a_n.mu_t + (b x)_tn,   s2 = (a_n^2).v_t
+ * (s2 = 0 when vb == 0).  The caller passes the quadrature nodes: with (x_q, w_q) the n_nodes-point Gauss-Hermite rule,
+ *   z[q] = sqrt(2) x_q,   lwa[q] = log(w_q / sqrt(pi)) + x_q^2.
+ *   Gaussian  lpd = -log(2 pi (noise_n + s2)) / 2 - (y - m)^2 / (2 (noise_n + s2));   rate = m
+ *   Poisson   rate = trunc_exp(m + s2 / 2): vlgp_loglik's rate, and the predictive mean below the clamp of trunc_exp.
+ *             s2 < 1e-30:  lpd = y log rate - rate - lgamma(y + 1), vlgp_loglik's expression (MAP fits, v == 0).
+ *             Otherwise the rule is centred at the mode of the integrand g(e) = y e - ex(e) - (e - m)^2 / (2 s2),
+ *             ex(e) = exp(min(e, 10)):
+ *               e = min(log y, m + y s2) if y > ex(m), else e = m;
+ *               eight times  e -= (y - ex(e) - (e - m) / s2) / (-ex(e) - 1 / s2);
+ *               h = s2 ex(e) + 1,  tau = sqrt(s2) / sqrt(h),  eta_q = e + tau z[q],  c_q = min(eta_q, 10),
+ *               t_q = lwa[q] + y c_q - exp(c_q) - (eta_q - m)^2 / (2 s2),
+ *               lpd = -log(h) / 2 + logsumexp_q t_q - lgamma(y + 1).
+ *             The start and the fixed count of Newton steps are part of the definition; the centre decides the accuracy of
+ *             the rule, never its validity.  Against the exact integral the worst error over m in [-8, 5], sqrt(s2) in
+ *             [0.02, 1], y in [0, 100] is 1.5e-6 at 12 nodes and 2e-8 at 20; far outside that regime the rule degrades
+ *             (sqrt(s2) = 3, y = 0 at 12 nodes: 0.06 at m = 9; at m = 11 the eight steps no longer reach the mode and the
+ *             error is several nats).  n_nodes == 1 is the Laplace approximation.
+ * sums has vlgp_loglik's slots for every kind of set, slot 0 now holding sum lpd: Poisson {sum lpd, sum y, sum rate,
+ * sum lgamma(y + 1)}, Gaussian {sum lpd, sum y, sum m, sum y^2}.  rate and lpd have vlgp_loglik's rate layout and may be
+ * NULL; on a set made by vlgp_replicate_masked they are NaN where no replica holds the entry out, and asking for either when
+ * two replicas hold the same entry out is VLGP_ERR_ARG.  n_nodes outside [1, 64] or a null z, lwa or sums: VLGP_ERR_ARG,
+ * the message naming the offender, nothing changed.  Takes the sets vlgp_loglik takes.  Waits for a pending
+ * M-step and norms pass; changes no unit state, no parameter and nothing vlgp_hstep_prepare built.  This handle's units
+ * only; fixed-order sums, no atomics: the same bits on every run. */
+int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, double* rate,
+                    double* lpd, double* sums);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

@@ -117,6 +117,7 @@ _SIGNATURES = {
     "vlgp_replicate_groups": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
     "vlgp_forecast": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
     "vlgp_marginal": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
+    "vlgp_predictive": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -125,6 +125,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_free_units, SET_ANY & ~SET_SOURCE, nullptr)                                                                \
     X(vlgp_upload_units, SET_ANY & ~SET_SOURCE, nullptr)                                                              \
     X(vlgp_loglik, SET_ANY & ~SET_COPIED, "vlgp_loglik on a copied cut: merge it and score the source set")           \
+    X(vlgp_predictive, SET_ANY & ~SET_COPIED, "vlgp_predictive on a copied cut: merge it and score the source set")   \
     X(vlgp_update_w, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_update_v, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_mstep_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \
@@ -887,6 +888,54 @@ extern "C" int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, cons
     }
     if (rc == VLGP_OK && count_flags(ctx, d_flag, tasks, n_failed) != hipSuccess)
         rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal: reading the flags failed");
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---- posterior-predictive density ------------------------------------------------------
+// vlgp_loglik's shapes with a second per-entry output; the waits of a read-only call (no epoch bump) and a device block of
+// the call's own for the nodes, the outputs and the partials: d_work may belong to a prepared H-step
+extern "C" int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa,
+                               double* rate, double* lpd, double* sums) {
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
+    if (n_nodes < 1 || n_nodes > 64)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: n_nodes = %d, need 1 <= n_nodes <= 64", n_nodes);
+    if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive needs z, lwa and sums");
+    CHK(admit(ctx, set, us, admit_vlgp_predictive));
+    const bool by_row = us->is(SET_BY_ROW);
+    if (by_row && (rate || lpd) && us->rep.overlap)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: the masks of set %d overlap (an entry is held out by more than "
+                         "one replica): no rate or lpd, sums only", set);
+    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
+    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
+    const LoglikShape S = vlgp_loglik_shape(ctx, *us);
+    const int64_t n_blk = (rows_of.rows + 255) / 256;
+    if (S.slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: too many (replica, channel) slots");
+    // nodes (2 x 64) | rate | lpd | sums | partials
+    const int64_t o_rate = 128, o_lpd = o_rate + (rate ? S.n_rate : 0), o_sums = o_lpd + (lpd ? S.n_rate : 0);
+    const int64_t o_part = o_sums + 4 * S.slots, need = o_part + S.slots * n_blk * 4;
+    double* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
+    double* d_rate = rate ? d + o_rate : nullptr;
+    double* d_lpd = lpd ? d + o_lpd : nullptr;
+    int rc = VLGP_OK;
+    hipError_t e = hipMemcpyAsync(d, z, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + n_nodes, lwa, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && by_row && o_sums > o_rate)  // NaN (every byte 0xff) where no replica holds the entry out
+        e = hipMemsetAsync(d + o_rate, 0xff, sizeof(double) * (size_t)(o_sums - o_rate), ctx->stream);
+    if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_predictive copy-in failed: %s", hipGetErrorString(e));
+    if (rc == VLGP_OK) rc = launch_predictive(ctx, *us, vb, n_nodes, d, d_rate, d_lpd, d + o_part, d + o_sums);
+    if (rc == VLGP_OK) {
+        e = hipMemcpyAsync(sums, d + o_sums, sizeof(double) * 4 * (size_t)S.slots, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && rate)
+            e = hipMemcpyAsync(rate, d_rate, sizeof(double) * (size_t)S.n_rate, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && lpd)
+            e = hipMemcpyAsync(lpd, d_lpd, sizeof(double) * (size_t)S.n_rate, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_predictive copy-out failed: %s", hipGetErrorString(e));
+    }
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
     return rc;

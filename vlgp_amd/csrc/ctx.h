@@ -390,6 +390,11 @@ int launch_gather(vlgp_ctx* ctx, UnitSet& src, UnitSet& dst, int window);
 int launch_loglik(vlgp_ctx* ctx, UnitSet& us, int vb, double* d_rate, double* d_sums);
 // d_sums (slots, 4) = the partials d_part (slots, n_blk, 4) of each slot added in workgroup order (evaluate.hip)
 int launch_sums_finish(vlgp_ctx* ctx, int slots, int n_blk, const double* d_part, double* d_sums);
+// posterior-predictive log density of a set's entries and its per-channel sums (predictive.hip), shaped as launch_loglik:
+// d_nodes = z (n_nodes) | lwa (n_nodes), 1 <= n_nodes <= 64; d_rate, d_lpd (vlgp_loglik_shape's n_rate each) or null;
+// d_part: (slots, ceil(source rows / 256), 4) doubles of the caller's workspace; d_sums (slots, 4)
+int launch_predictive(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const double* d_nodes, double* d_rate, double* d_lpd,
+                      double* d_part, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace

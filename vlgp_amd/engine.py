@@ -68,6 +68,20 @@ def unpack_mask(words, n_channels):
     return bits[..., :int(n_channels)].astype(bool)
 
 
+MAX_NODES = 64  # the largest quadrature rule vlgp_predictive takes
+
+
+def hermite_nodes(n):
+    """Node tables of the ``n``-point Gauss-Hermite rule as vlgp_predictive takes them, ``1 <= n <= 64``:
+    ``(z, lwa)`` with ``z = sqrt(2) x`` and ``lwa = log(w / sqrt(pi)) + x ** 2`` for
+    ``(x, w) = numpy.polynomial.hermite.hermgauss(n)`` -- the rule for a standard normal, with the weight of the normal
+    whose nodes these are divided out again (``evaluation``'s docstring has the sum they enter)."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= MAX_NODES:
+        raise ValueError("n_nodes must be an integer in [1, %d], got %r" % (MAX_NODES, n))
+    x, w = np.polynomial.hermite.hermgauss(int(n))
+    return _f64(np.sqrt(2.0) * x), _f64(np.log(w / np.sqrt(np.pi)) + x * x)
+
+
 class Replicas(collections.namedtuple("Replicas", "n channels by_entry")):
     """What ``Engine.replicate`` made of a set: ``n`` replicas; ``channels``, the left-out channel of every (replica,
     channel) pair in the caller's order, or None when the replicas leave single entries out (``by_entry``)."""
@@ -272,6 +286,26 @@ class Engine:
             rate = np.empty((rows_out, slots)) if want_rate else None
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
         return sums, rate
+
+    def predictive(self, set_id, n_nodes=12, vb=True, want_rate=False, want_lpd=False):
+        """Posterior-predictive log density of a set's entries (vlgp_predictive): ``(sums, rate, lpd)``.  ``sums`` has
+        the shape and slots of ``loglik``'s with ``sum lpd`` in column 0; ``rate`` (``loglik``'s plug-in rate) and
+        ``lpd`` have the shape of ``loglik``'s rate, or are None.  ``n_nodes``: points of the mode-centred Gauss-Hermite
+        rule of the Poisson channels (``hermite_nodes``).  Changes no state."""
+        z, lwa = hermite_nodes(n_nodes)
+        _, rows, _ = self.sets[set_id]
+        rep = self.replicas.get(set_id)
+        rows_out = rows if rep is None else rows // max(rep.n, 1)
+        if rep is not None and rep.by_entry:
+            sums, slots = np.empty((rep.n, self.N, 4)), self.N
+        else:
+            slots = self.N if rep is None else len(rep.channels)
+            sums = np.empty((slots, 4))
+        rate = np.empty((rows_out, slots)) if want_rate else None
+        lpd = np.empty((rows_out, slots)) if want_lpd else None
+        self._ck(self.lib.vlgp_predictive(self.h, int(set_id), int(bool(vb)), len(z), dptr(z), dptr(lwa), dptr(rate),
+                                          dptr(lpd), dptr(sums)))
+        return sums, rate, lpd
 
     def elbo(self, set_id, vb=True, want_rows=False):
         """Terms of the variational lower bound of a plain set (vlgp_elbo): ``(row_sums, kl_terms, n_failed, row_ell)``

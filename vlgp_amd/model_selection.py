@@ -65,7 +65,7 @@ def best_candidate(n_factors_list, mean_co_bps):
 
 
 def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, seed=0, n_iter=None, device=0,
-                   score="co_bps", **fit_kwargs):
+                   score="co_bps", predictive=False, n_nodes=12, **fit_kwargs):
     """Score every ``n_factors`` of ``n_factors_list`` by co-smoothing bits per spike on held-out trials.
 
     For every trial fold and candidate: ``fit`` on fresh copies of the other trials (``fit_kwargs`` are ``fit``'s),
@@ -92,9 +92,15 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
     dict holds ``marginal_bps`` (candidates, trial folds) and ``mean_marginal_bps``, ``ess_min`` (candidates, trial
     folds), the smallest per-trial effective sample size of the fold -- near 1 the fold's estimate rests on single
     draws and should not be trusted --, ``n_failed``, ``best``, ``errors`` and ``score``; no ``channel_folds`` and no
-    per-channel ``bits_per_spike``."""
+    per-channel ``bits_per_spike``.
+
+    ``predictive=True`` scores ``co_bps`` and ``speckled_bps`` with the posterior-predictive density
+    (``evaluation``'s docstring), ``n_nodes`` quadrature nodes per Poisson entry; ``marginal_bps`` is a score of whole
+    trials with no plug-in form to replace, and raises ``ValueError`` with it."""
     if score not in ("co_bps", "speckled_bps", "marginal_bps"):
         raise ValueError("score must be 'co_bps', 'speckled_bps' or 'marginal_bps', got %r" % (score,))
+    if predictive and score == "marginal_bps":
+        raise ValueError("predictive=True applies to the per-entry scores 'co_bps' and 'speckled_bps', not to 'marginal_bps'")
     if "comm" in fit_kwargs:
         raise ValueError("cross_validate runs on one process: it takes no comm")
     n_factors_list = [int(n) for n in n_factors_list]
@@ -126,10 +132,11 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
                                           n_samples=int(n_channel_folds) * 16, seed=seed, n_iter=n_iter, device=device)
                 elif speckled:
                     got = leave_entries_out(_fresh(trials, test_idx), fitted["params"], fitted["config"],
-                                            n_folds=n_channel_folds, seed=seed, n_iter=n_iter, device=device)
+                                            n_folds=n_channel_folds, seed=seed, n_iter=n_iter, device=device,
+                                            predictive=predictive, n_nodes=n_nodes)
                 else:
                     got = leave_group_out(_fresh(trials, test_idx), fitted["params"], fitted["config"], groups=c_folds,
-                                          n_iter=n_iter, device=device)
+                                          n_iter=n_iter, device=device, predictive=predictive, n_nodes=n_nodes)
             except Exception as err:  # (the sweep goes on: one candidate's failure is a result, not the end)
                 errors.append((n, f, "%s: %s" % (type(err).__name__, err)))
                 continue
