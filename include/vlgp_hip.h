@@ -220,6 +220,42 @@ int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* leng
  * parameter and nothing vlgp_hstep_prepare built.  Fixed-order sums, no atomics: the same bits on every run. */
 int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* eps, double* log_w, double* parts,
                   int* n_failed);
+/* Joint Laplace posterior of every unit of a set that is not replicated (VLGP_ERR_STATE otherwise; 4.11):
+ * the mode of the posterior over ALL prior weights beta = (beta_1 ... beta_L) of a unit by a damped Newton iteration, the
+ * Laplace evidence, latent variances that include the coupling between latents, and joint Gaussian draws for the
+ * importance weights of vlgp_marginal.  For a unit of T rows, G_l (T x r_l) the compact prior factor of latent l, the
+ * stacked index (l, i) latent-major, D = sum_l r_l:
+ *   x[t, l] = G_l[t, :] . beta_l,   eta[t, n] = a_n . x[t] + (b x)_tn          (no v term: the model of vlgp_marginal's ll)
+ *   Poisson   lam = trunc_exp(eta),  ll = y eta - lam - lgamma(y + 1),  res = y - lam,  cur = lam
+ *   Gaussian  ll = -log(2 pi noise_n) / 2 - (y - eta)^2 / (2 noise_n),  res = (y - eta) / noise_n,  cur = 1 / noise_n
+ *   f(beta) = 1/2 |beta|^2 - sum_t sum_n ll
+ *   grad_l f = beta_l - G_l' g[:, l],   g[t, l] = sum_n a[l, n] res[t, n]
+ *   H[(l, i), (l', j)] = delta + sum_t G_l[t, i] c[t, l, l'] G_l'[t, j],   c[t, l, l'] = sum_n a[l, n] a[l', n] cur[t, n]
+ *   H = Lc Lc'; the mode is the zero of grad f, unique while no eta is above the clamp of trunc_exp.
+ * Start: the mean-field centres m_l = H_l^-1 G_l' (g + w o mu)_l of vlgp_forecast from the set's current mu, w, vb = 0.
+ * Step: d = H^-1 grad f, decrement = grad f' H^-1 grad f.  A unit stops converged when decrement <= tol, and not
+ * converged after max_iter factorisations of H.  The trial point beta - s d, s = 1, is accepted when
+ *   f(beta - s d) <= f(beta) - 1e-4 s decrement + 2^-46 (1/2 |beta - s d|^2 + sum of the absolute terms of ll),
+ * the last term being the rounding of the sum f is; otherwise s is halved, and a unit whose s falls below 2^-30 stops
+ * where it stands, not converged.  f never increases beyond that rounding.  Then
+ *   laplace = ll(beta) - 1/2 |beta|^2 - 1/2 log det H(beta)
+ *   mu[t, l] = G_l[t, :] . beta_l,   v[t, l] = G_l[t, :] (H^-1)_ll G_l[t, :]'
+ *   draw k:  beta_k = beta + Lc^-T eps_k,  c_k = -1/2 |beta_k|^2 + 1/2 |eps_k|^2 - 1/2 log det H,
+ *            log_w[u, k] = ll(beta_k) + c_k;  mean_k exp(log_w) is unbiased for p(y_u) wherever beta stands.
+ * beta (units, L, R), entries at or beyond r_l zero; stats (units, 8) = {laplace, ll(beta), |beta|^2, log det H, final
+ * decrement, factorisations taken, converged 0/1, D}; mu, v (rows, L); eps (units, L, R, n_samples) and log_w
+ * (units, n_samples) as in vlgp_marginal, rows >= r_l of eps never read; parts (units, n_samples, 2) = {ll, c}, whose two
+ * entries add to log_w.  n_samples == 0 computes the mode only: eps, log_w and parts are then ignored.  beta, mu, v, parts
+ * and n_failed may be NULL.  The samples are walked 64 at a time: device memory does not grow with n_samples, and sample
+ * k's numbers are the same bits whatever n_samples is.  A pivot of H that is not positive and finite makes the unit's
+ * stats[0 .. 4], mu, v and log_w NaN and is counted in *n_failed; a unit that ran out of iterations is no failure: it
+ * reports converged = 0 and is scored where it stands.  D > 512 for any unit, parameters not set or a length without a
+ * prior: VLGP_ERR_STATE (the message names D); max_iter < 1, tol not > 0, n_samples < 0, a null stats, or n_samples > 0
+ * with a null eps or log_w: VLGP_ERR_ARG, the message naming the offender, nothing changed.  Waits for a pending M-step
+ * and norms pass; changes no unit state, no parameter and nothing vlgp_hstep_prepare built.  Fixed-order sums, no atomics
+ * on doubles: the same bits on every run. */
+int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_samples, const double* eps, double* beta,
+                       double* stats, double* mu, double* v, double* log_w, double* parts, int* n_failed);
 /* Posterior-predictive log density of every observation under the set's current posterior: where vlgp_loglik scores an
  * entry with the plug-in density p(y | E_q[rate]), this integrates the likelihood over the posterior of its linear
  * predictor,

@@ -139,6 +139,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_elbo, NOT_REPLICATED, nullptr)                                                                             \
     X(vlgp_forecast, NOT_REPLICATED, nullptr) /* (a cut is refused once its priors are bound: see there) */           \
     X(vlgp_marginal, NOT_REPLICATED, nullptr)                                                                         \
+    X(vlgp_joint_laplace, NOT_REPLICATED, nullptr)                                                                    \
     X(vlgp_stash_mu, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_set_overlaps, NOT_REPLICATED, nullptr) /* (and equal-length units that are no tiling cut: see there) */    \
     X(vlgp_unshare_mu, NOT_REPLICATED, nullptr)                                                                       \
@@ -888,6 +889,96 @@ extern "C" int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, cons
     }
     if (rc == VLGP_OK && count_flags(ctx, d_flag, tasks, n_failed) != hipSuccess)
         rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal: reading the flags failed");
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---- joint Laplace posterior ----------------------------------------------------------
+extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_samples, const double* eps,
+                                  double* beta, double* stats, double* mu, double* v, double* log_w, double* parts,
+                                  int* n_failed) {
+    UnitSet* us = nullptr;
+    CHK(open_posterior(ctx, set, admit_vlgp_joint_laplace, &us));
+    if (max_iter < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: max_iter = %d, need >= 1", max_iter);
+    if (!(tol > 0.0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: tol = %g, need > 0", tol);
+    if (n_samples < 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples = %d, need >= 0", n_samples);
+    if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace needs stats");
+    if (n_samples > 0 && (!eps || !log_w)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples > 0 needs eps and log_w");
+    const int L = ctx->L, R = ctx->R, M = us->M;
+    const int64_t tasks = (int64_t)M * L, K = n_samples, rows = us->rows;
+    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: too many (unit, latent) pairs");
+    int Dmax = 1;
+    for (int m = 0; m < M; ++m) {  // D = sum_l r_l of the unit's length
+        const Prior& pr = ctx->priors.find((int)(us->off[m + 1] - us->off[m]))->second;  // (vlgp_bind_priors found every length)
+        int D = 0;
+        for (int l = 0; l < L; ++l) D += pr.rl[l];
+        if (D > 512)
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_joint_laplace: unit %d has D = %d weights, at most 512 are supported", m, D);
+        Dmax = std::max(Dmax, D);
+    }
+    if (n_failed) *n_failed = 0;
+    const int rp = set_rank_max(ctx, *us);
+    const int tile_rows = marginal_tile_rows(L);
+    std::vector<int64_t> tile_off((size_t)M + 1, 0);  // first row tile of each unit
+    for (int m = 0; m < M; ++m) tile_off[(size_t)m + 1] = tile_off[(size_t)m] + (us->off[m + 1] - us->off[m] + tile_rows - 1) / tile_rows;
+    const int64_t n_tiles = tile_off[(size_t)M];
+    // one device block of the call's own: the Newton workspace | stats | v | and for the draws, 64 at a time whatever
+    // n_samples is: eps | beta_k | c | tile partials | log_w | parts | tile_off
+    const int64_t o_stats = joint_work_doubles(ctx, *us, Dmax, nullptr), o_v = o_stats + 8 * (int64_t)M, o_eps = o_v + rows * L;
+    const int64_t o_beta = o_eps + (K ? tasks * R * 64 : 0), o_c = o_beta + (K ? tasks * R * 64 : 0), o_part = o_c + (K ? tasks * 64 : 0);
+    const int64_t o_lw = o_part + (K ? n_tiles * 64 : 0), o_parts = o_lw + (K ? (int64_t)M * 64 : 0);
+    const int64_t o_tab = o_parts + (K ? (int64_t)M * 128 : 0), need = o_tab + M + 1;
+    double* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
+    JointWork W;
+    W.base = d;
+    (void)joint_work_doubles(ctx, *us, Dmax, &W);
+    int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
+    const size_t dbl = sizeof(double);
+    int rc = launch_joint_init(ctx, *us, rp, W);
+    hipError_t e = hipSuccess;
+    // every round finishes a unit, factors it (at most max_iter times) or halves its step (at most 30 times per factor)
+    for (int64_t round = 0, done = 0; rc == VLGP_OK && done < M && round <= 32 * ((int64_t)max_iter + 1); ++round) {
+        rc = launch_joint_round(ctx, *us, W, max_iter, tol);
+        if (rc != VLGP_OK) break;
+        int nd = 0;
+        e = hipMemcpyAsync(&nd, W.n_done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace: a Newton round failed: %s", hipGetErrorString(e));
+        done = nd;
+    }
+    if (rc == VLGP_OK) rc = launch_joint_finish(ctx, *us, rp, W, d + o_stats, mu || v ? W.g : nullptr, mu || v ? d + o_v : nullptr);
+    if (rc == VLGP_OK) {
+        e = hipMemcpyAsync(stats, d + o_stats, dbl * 8 * (size_t)M, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && beta) e = hipMemcpyAsync(beta, W.beta, dbl * (size_t)(tasks * R), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && mu) e = hipMemcpyAsync(mu, W.g, dbl * (size_t)(rows * L), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && v) e = hipMemcpyAsync(v, d + o_v, dbl * (size_t)(rows * L), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && K)
+            e = hipMemcpyAsync(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size(), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace copy-out failed: %s", hipGetErrorString(e));
+    }
+    if (rc == VLGP_OK && n_failed)
+        for (int m = 0; m < M; ++m) *n_failed += stats[8 * (size_t)m] != stats[8 * (size_t)m] ? 1 : 0;  // (NaN: the unit failed)
+    for (int64_t k0 = 0; k0 < K && rc == VLGP_OK; k0 += 64) {  // (the copies of a chunk and its kernels are stream-ordered)
+        const int kc = (int)std::min<int64_t>(64, K - k0);
+        e = hipMemcpy2DAsync(d + o_eps, 64 * dbl, eps + k0, (size_t)K * dbl, (size_t)kc * dbl, (size_t)(tasks * R),
+                             hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace copy-in failed: %s", hipGetErrorString(e));
+        if (rc == VLGP_OK) rc = launch_joint_draw(ctx, *us, W, kc, d + o_eps, d + o_beta, d + o_c);
+        if (rc == VLGP_OK)
+            rc = launch_marginal_rows(ctx, *us, "vlgp_joint_laplace", kc, d + o_beta, d + o_c, d + o_part, tile_rows, d_tab,
+                                      n_tiles, d + o_lw, d + o_parts);
+        if (rc != VLGP_OK) break;
+        e = hipMemcpy2DAsync(log_w + k0, (size_t)K * dbl, d + o_lw, 64 * dbl, (size_t)kc * dbl, (size_t)M, hipMemcpyDeviceToHost,
+                             ctx->stream);
+        if (e == hipSuccess && parts)
+            e = hipMemcpy2DAsync(parts + 2 * k0, (size_t)K * 2 * dbl, d + o_parts, 128 * dbl, (size_t)kc * 2 * dbl, (size_t)M,
+                                 hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace copy-out failed: %s", hipGetErrorString(e));
+    }
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
     return rc;

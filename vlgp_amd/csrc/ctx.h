@@ -415,3 +415,24 @@ int marginal_tile_rows(int L);
 int launch_marginal(vlgp_ctx* ctx, UnitSet& us, int rp, int kc, const double* d_z, const double* d_eps, double* d_beta,
                     double* d_c, double* d_part, int tile_rows, const int64_t* d_tile_off, int64_t n_tiles, double* d_logw,
                     double* d_parts, int* d_flag);
+int launch_marginal_rows(vlgp_ctx* ctx, UnitSet& us, const char* who, int kc, const double* d_beta, const double* d_c,
+                         double* d_part, int tile_rows, const int64_t* d_tile_off, int64_t n_tiles, double* d_logw,
+                         double* d_parts);  // its row kernel and finish alone: beta_k and c come from the caller
+// joint Laplace posterior of a plain set (joint.hip).  JointWork: the call's device block cut into its pieces by
+// joint_work_doubles (which returns the doubles needed; W may be null to ask), Dmax the largest stacked dimension of the set.
+// launch_joint_init: the mean-field start; launch_joint_round: one row pass, the step decision and, where the step was
+// accepted, H, its factor and the next direction, W.n_done counting the finished units; launch_joint_finish: stats (M, 8)
+// and mu, v (rows, L) or null; launch_joint_draw: kc <= 64 draws into d_beta (M, L, R, 64), their c into d_c (M, L, 64)
+struct JointWork {
+    double* base = nullptr;
+    int Dmax = 0;
+    size_t state_bytes = 0;
+    double *beta = nullptr, *dvec = nullptr, *sd = nullptr, *x = nullptr, *llrow = nullptr, *absrow = nullptr, *g = nullptr;
+    double *c = nullptr, *res = nullptr, *cur = nullptr, *H = nullptr, *zw = nullptr;
+    int *si = nullptr, *n_done = nullptr;
+};
+int64_t joint_work_doubles(const vlgp_ctx* ctx, const UnitSet& us, int Dmax, JointWork* W);
+int launch_joint_init(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W);
+int launch_joint_round(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_iter, double tol);
+int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, double* d_stats, double* d_mu, double* d_v);
+int launch_joint_draw(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int kc, const double* d_eps, double* d_beta, double* d_c);

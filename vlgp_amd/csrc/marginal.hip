@@ -204,6 +204,30 @@ __global__ void __launch_bounds__(64) marginal_finish(MarginalFinishArgs A) {
 
 }  // namespace
 
+// the row kernel and the finish alone, for draws d_beta (M, L, R, 64) with their c in d_c (M, L, 64) already in place:
+// launch_marginal's second half, which vlgp_joint_laplace shares (its draws come from joint.hip)
+int launch_marginal_rows(vlgp_ctx* ctx, UnitSet& us, const char* who, int kc, const double* d_beta, const double* d_c,
+                         double* d_part, int tile_rows, const int64_t* d_tile_off, int64_t n_tiles, double* d_logw,
+                         double* d_parts) {
+    if (kc < 1 || kc > 64 || tile_rows < 1 || tile_rows > MR_ROWS || n_tiles < 1 || n_tiles > 0x7fffffffLL)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: %d samples in %lld tiles of %d rows", who, kc, (long long)n_tiles, tile_rows);
+    MarginalRowArgs R;
+    R.m = fill_row_model(ctx, us, us, 0);
+    R.P = fill_task_prior(ctx, us);
+    R.R = ctx->R; R.tile_rows = tile_rows;
+    R.tile_off = d_tile_off; R.beta = d_beta; R.part = d_part;
+    const size_t xs = sizeof(double) * 64 * (size_t)tile_rows * ctx->L;
+    if ((int64_t)xs > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: %d latents need %zu bytes of LDS", who, ctx->L, xs);
+    if (xs > 64 * 1024) CHK(vlgp_raise_lds(ctx, (const void*)marginal_rows, ctx->lds_max));
+    hipLaunchKernelGGL(marginal_rows, dim3((unsigned)n_tiles), dim3(64), xs, ctx->stream, R);
+    HIPCHK(ctx, hipGetLastError());
+
+    MarginalFinishArgs F = {us.M, ctx->L, kc, d_tile_off, d_part, d_c, d_logw, d_parts};
+    hipLaunchKernelGGL(marginal_finish, dim3((unsigned)us.M), dim3(64), 0, ctx->stream, F);
+    HIPCHK(ctx, hipGetLastError());
+    return VLGP_OK;
+}
+
 int launch_marginal(vlgp_ctx* ctx, UnitSet& us, int rp, int kc, const double* d_z, const double* d_eps, double* d_beta,
                     double* d_c, double* d_part, int tile_rows, const int64_t* d_tile_off, int64_t n_tiles, double* d_logw,
                     double* d_parts, int* d_flag) {
@@ -220,20 +244,5 @@ int launch_marginal(vlgp_ctx* ctx, UnitSet& us, int rp, int kc, const double* d_
     if (lds > 64 * 1024) CHK(vlgp_raise_lds(ctx, (const void*)marginal_task, ctx->lds_max));
     hipLaunchKernelGGL(marginal_task, dim3((unsigned)(us.M * ctx->L)), dim3(64), lds, ctx->stream, K);
     HIPCHK(ctx, hipGetLastError());
-
-    MarginalRowArgs R;
-    R.m = fill_row_model(ctx, us, us, 0);
-    R.P = K.P;
-    R.R = ctx->R; R.tile_rows = tile_rows;
-    R.tile_off = d_tile_off; R.beta = d_beta; R.part = d_part;
-    const size_t xs = sizeof(double) * 64 * (size_t)tile_rows * ctx->L;
-    if ((int64_t)xs > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal: %d latents need %zu bytes of LDS", ctx->L, xs);
-    if (xs > 64 * 1024) CHK(vlgp_raise_lds(ctx, (const void*)marginal_rows, ctx->lds_max));
-    hipLaunchKernelGGL(marginal_rows, dim3((unsigned)n_tiles), dim3(64), xs, ctx->stream, R);
-    HIPCHK(ctx, hipGetLastError());
-
-    MarginalFinishArgs F = {us.M, ctx->L, kc, d_tile_off, d_part, d_c, d_logw, d_parts};
-    hipLaunchKernelGGL(marginal_finish, dim3((unsigned)us.M), dim3(64), 0, ctx->stream, F);
-    HIPCHK(ctx, hipGetLastError());
-    return VLGP_OK;
+    return launch_marginal_rows(ctx, us, "vlgp_marginal", kc, d_beta, d_c, d_part, tile_rows, d_tile_off, n_tiles, d_logw, d_parts);
 }

@@ -364,6 +364,37 @@ class Engine:
                                         C.byref(n)))
         return log_w, n.value, parts
 
+    def joint_laplace(self, set_id, max_iter=50, tol=1e-10, eps=None):
+        """Joint Laplace posterior of every unit of a plain set (vlgp_joint_laplace): the mode of the posterior over all
+        prior weights of a unit by a damped Newton iteration started at the mean-field centres of the set's current
+        ``mu, w``.  ``eps``: None, or (units, L, R, n_samples) standard normals as ``marginal`` takes them, for draws from
+        the joint Gaussian ``N(beta, H^-1)``.  Returns a dict: ``beta`` (units, L, R); ``stats`` (units, 8) and its columns
+        ``laplace``, ``ll``, ``beta_sq``, ``logdet``, ``decrement``, ``n_newton``, ``converged``, ``D``; ``mu``, ``v``
+        (rows, L); ``n_failed`` (units whose ``H`` could not be factored: their numbers are NaN); with ``eps`` also
+        ``log_w`` (units, n_samples) and ``parts`` (units, n_samples, 2) = the log-likelihood of the draw and the
+        prior-over-proposal term, which add to ``log_w``.  Changes no state."""
+        units, rows, _ = self.sets[set_id]
+        K, log_w, parts = 0, None, None
+        if eps is not None:
+            eps = _f64(eps)
+            if eps.ndim != 4 or eps.shape[:3] != (units, self.L, self.R) or eps.shape[3] < 1:
+                raise ValueError("eps must be (%d, %d, %d, n_samples >= 1), got %r" % (units, self.L, self.R, eps.shape))
+            K = eps.shape[3]
+            log_w, parts = np.empty((units, K)), np.empty((units, K, 2))
+        beta = np.empty((units, self.L, self.R))
+        stats = np.empty((units, 8))
+        mu, v = np.empty((rows, self.L)), np.empty((rows, self.L))
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_joint_laplace(self.h, int(set_id), int(max_iter), float(tol), K, dptr(eps), dptr(beta),
+                                             dptr(stats), dptr(mu), dptr(v), dptr(log_w), dptr(parts), C.byref(n)))
+        out = {"beta": beta, "stats": stats, "mu": mu, "v": v, "n_failed": n.value,
+               "laplace": stats[:, 0].copy(), "ll": stats[:, 1].copy(), "beta_sq": stats[:, 2].copy(),
+               "logdet": stats[:, 3].copy(), "decrement": stats[:, 4].copy(), "n_newton": stats[:, 5].astype(np.int64),
+               "converged": stats[:, 6] > 0, "D": stats[:, 7].astype(np.int64)}
+        if eps is not None:
+            out.update(log_w=log_w, parts=parts)
+        return out
+
     def unit_ranks(self, set_id):
         """(units, L) effective rank of the prior factor each (unit, latent) of the set is bound to."""
         _, _, off = self.sets[set_id]

@@ -93,6 +93,32 @@ Marginal likelihood (``marginal_loglik``, ``vlgp_marginal``): the importance-sam
 estimate, which ``ess`` (between 1 and ``K``) reports: near 1 a single draw carries the sum and ``iwae`` is little more
 than that draw's ``log_w``.
 
+Joint Laplace posterior (``joint_posterior``, ``marginal_loglik(proposal="joint")``, ``vlgp_joint_laplace``).  Every
+posterior above is mean-field over latents; the posterior over ALL prior weights ``beta = (beta_1 ... beta_L)`` of a unit
+is log-concave and of small dimension ``D = sum_l r_l`` (at most 512 here), so a joint Newton iteration finds its mode.
+With ``G_l`` (``T x r_l``) the compact prior factor of latent ``l`` and the stacked index ``(l, i)`` latent-major:
+
+- ``x[t, l] = G_l[t, :] . beta_l`` and ``eta[t, n] = a_n . x[t] + (b x)_tn`` -- no ``v`` term: the model of ``ll`` above.
+- Poisson channels: ``lam = trunc_exp(eta)``, ``ll = y eta - lam - lgamma(y + 1)``, ``res = y - lam``, ``cur = lam``.
+  Gaussian channels: ``ll = -log(2 pi noise_n) / 2 - (y - eta) ** 2 / (2 noise_n)``, ``res = (y - eta) / noise_n``,
+  ``cur = 1 / noise_n``.
+- objective ``f(beta) = 1/2 |beta|^2 - sum_t sum_n ll``; gradient ``grad_l f = beta_l - G_l' g[:, l]`` with
+  ``g[t, l] = sum_n a[l, n] res[t, n]``.
+- Hessian ``H[(l, i), (l', j)] = delta + sum_t G_l[t, i] c[t, l, l'] G_l'[t, j]`` with
+  ``c[t, l, l'] = sum_n a[l, n] a[l', n] cur[t, n]``; its diagonal blocks are ``I + G_l' diag(w_l) G_l`` with the engine's
+  own ``w``.  ``H = Lc Lc'``.
+- the mode ``beta_hat`` is the zero of ``grad f``, unique while no ``eta`` is above the clamp of ``trunc_exp``: results are
+  pinned by stationarity, not by the path taken.
+- Newton start: the mean-field centres ``m_l`` above from the set's current ``mu, w``, with the ``v`` term dropped.
+  Step ``d = H^-1 grad f``; a unit stops when its decrement ``grad f' H^-1 grad f <= tol`` or after ``max_iter``
+  factorisations.  The trial point ``beta - s d``, ``s = 1``, is accepted when
+  ``f(beta - s d) <= f(beta) - 1e-4 s decrement + 2 ** -46 (1/2 |beta - s d|^2 + sum |ll terms|)`` (the last term: the
+  rounding of the sum); otherwise ``s`` is halved, and below ``2 ** -30`` the unit stops where it stands, not converged.
+- ``laplace = ll(beta_hat) - 1/2 |beta_hat|^2 - 1/2 log det H(beta_hat)``, the Laplace evidence ``log p(y_unit)``.
+- ``mu[t, l] = G_l[t, :] . beta_hat_l`` and ``v[t, l] = G_l[t, :] (H^-1)_ll G_l[t, :]'``.
+- draw ``k``: ``beta_k = beta_hat + Lc^-T eps_k``, ``c_k = -1/2 |beta_k|^2 + 1/2 |eps_k|^2 - 1/2 log det H``,
+  ``log_w[u, k] = ll(beta_k) + c_k``; ``mean_k exp(log_w)`` is unbiased for ``p(y_u)`` whatever ``beta_hat`` is.
+
 Posterior-predictive density (``predictive=True`` in ``loglik``, ``leave_one_out``, ``leave_group_out``,
 ``leave_entries_out``, ``forward_prediction``; ``Engine.predictive``, ``vlgp_predictive``).  The plug-in log-likelihood
 above sees the posterior variance ``v`` only through the mean of the rate: a posterior that is confidently wrong and one
@@ -129,7 +155,7 @@ the posterior of the linear predictor instead,
   expected log-likelihood (``elbo``'s per-entry term).
 
 Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``, ``vlgp_marginal``,
-``vlgp_predictive``): the results are the same bits on every run.
+``vlgp_predictive``, ``vlgp_joint_laplace``): the results are the same bits on every run.
 """
 import contextlib
 import math
@@ -144,7 +170,8 @@ from .util import _per_trial_entries
 
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
            "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
-           "entry_scores", "leave_entries_out", "impute", "marginal_loglik", "weights_summary", "hermite_nodes"]
+           "entry_scores", "leave_entries_out", "impute", "marginal_loglik", "weights_summary", "hermite_nodes",
+           "joint_posterior"]
 
 SAMPLE_CHUNK = 64  # draws per device call: one lane per sample (csrc/marginal.hip)
 
@@ -702,7 +729,8 @@ def weights_summary(log_w):
     return np.where(bad, np.nan, iwae), np.where(bad, np.nan, np.mean(log_w, axis=-1)), np.where(bad, np.nan, ess)
 
 
-def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infer=True, n_iter=None, device=0):
+def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infer=True, n_iter=None, device=0,
+                    proposal="posterior", max_iter=50, tol=1e-10):
     """Importance-weighted estimate of the marginal log-likelihood ``log p(y_trial)`` of every trial, the fitted
     posterior as proposal (module docstring for the definitions).
 
@@ -719,8 +747,16 @@ def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infe
     ``gap = total - elbo`` (NaN under MAP, where there is no bound); ``marginal_bps = (total - LL_null) /
     (n_spikes ln 2)`` with ``LL_null`` the constant-rate null of ``bits_per_spike`` over all evaluated rows, NaN unless
     every channel is Poisson; ``n_failed`` (failed E-step updates plus (trial, latent) pairs whose ``H`` could not be
-    factored: such a trial's ``log_w`` is NaN, and so is every number it enters)."""
+    factored: such a trial's ``log_w`` is NaN, and so is every number it enters).
+
+    ``proposal="joint"`` draws from the joint Laplace posterior ``N(beta_hat, H^-1)`` of every trial instead
+    (``joint_posterior``; ``max_iter`` and ``tol`` are its Newton iteration's), with the same normals, the same chunks of 64
+    and the same keys, plus per trial ``laplace``, the Laplace evidence, and ``converged``.  The Newton iteration runs once
+    and the device walks the chunks itself, so the normals of all chunks are held at once.  ``elbo`` and ``gap`` still
+    describe the mean-field posterior the Newton iteration started from.  Any other ``proposal`` raises ``ValueError``."""
     _no_missing(trials, "marginal_loglik")
+    if proposal not in ("posterior", "joint"):
+        raise ValueError("proposal must be 'posterior' or 'joint', got %r" % (proposal,))
     if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
         raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
     K, L, R = int(n_samples), int(params["zdim"]), int(params["rank"])
@@ -738,9 +774,17 @@ def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infe
         n_failed = 0
         if infer:
             n_failed = eng.estep(SET_TEST, int(config["max_iter"] if n_iter is None else n_iter), config["dmu_bound"], vb)
+        chunks = []
         for k0 in range(0, K, SAMPLE_CHUNK):
             kc = min(SAMPLE_CHUNK, K - k0)
-            log_w[:, k0:k0 + kc], bad, _ = eng.marginal(SET_TEST, rng.standard_normal((len(trials), L, R, kc)), vb=vb)
+            eps = rng.standard_normal((len(trials), L, R, kc))
+            if proposal == "joint":
+                chunks.append(eps)  # (one call: the Newton iteration runs once, the device walks the chunks itself)
+            else:
+                log_w[:, k0:k0 + kc], bad, _ = eng.marginal(SET_TEST, eps, vb=vb)
+        if proposal == "joint":
+            joint = eng.joint_laplace(SET_TEST, max_iter=max_iter, tol=tol, eps=np.concatenate(chunks, axis=3))
+            log_w[:], bad = joint["log_w"], joint["n_failed"]
         bound = elbo_from_terms(*eng.elbo(SET_TEST, vb=vb)[:2], eng.unit_ranks(SET_TEST), vb=vb)["elbo"]
         sums, _ = eng.loglik(SET_TEST, vb=vb)
         gauss = eng.gauss.copy()
@@ -751,5 +795,51 @@ def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infe
         bps = float("nan")
     else:
         bps = float((total - np.sum(ll_null)) / (np.sum(ny) * math.log(2.0)))
-    return {"log_w": log_w, "iwae": iwae, "elbo_mc": elbo_mc, "ess": ess, "total": total, "elbo": bound,
-            "gap": total - bound, "marginal_bps": bps, "n_failed": int(n_failed) + int(bad)}
+    out = {"log_w": log_w, "iwae": iwae, "elbo_mc": elbo_mc, "ess": ess, "total": total, "elbo": bound,
+           "gap": total - bound, "marginal_bps": bps, "n_failed": int(n_failed) + int(bad)}
+    if proposal == "joint":
+        out.update(laplace=joint["laplace"], converged=joint["converged"])
+    return out
+
+
+def joint_posterior(trials, params, config, infer=True, n_iter=None, max_iter=50, tol=1e-10, device=0):
+    """The joint Laplace posterior of every trial: the mode of the posterior over all prior weights of the trial, found by
+    a damped Newton iteration on the device (module docstring for the definitions).
+
+    ``infer=True`` is for held-out trials: an E-step from a zero start, ``n_iter`` iterations (default
+    ``config["max_iter"]``) as ``marginal_loglik`` runs it, gives the mean-field centres the Newton iteration starts from;
+    ``infer=False`` starts from the trials' stored ``mu, w``.  The mode does not depend on the start.  ``max_iter``: most
+    factorisations of ``H`` per trial; ``tol``: the Newton decrement at which a trial stops.  Trials that carry ``missing``
+    raise ``ValueError``.  Neither ``params`` nor the trials are modified.
+
+    Returns a dict: per trial ``mu``, ``v`` (T, L) -- ``v`` includes the coupling between latents, whatever
+    ``config["method"]`` is --, ``laplace`` (the Laplace evidence ``log p(y_trial)``), ``converged``, ``n_newton``; and
+    over all trials ``total``, the sum of ``laplace``; ``laplace_bps = (total - LL_null) / (n_spikes ln 2)`` by
+    ``marginal_loglik``'s null model, NaN unless every channel is Poisson; ``n_failed`` (failed E-step updates plus trials
+    whose ``H`` could not be factored: their numbers are NaN, and so is ``total``)."""
+    _no_missing(trials, "joint_posterior")
+    L = int(params["zdim"])
+    vb = config["method"] == "VB"
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    if infer:
+        units = _zero_start(trials, L)
+    else:
+        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
+                  **{k: tr[k] if tr.get(k) is not None else np.zeros((T, L)) for k in ("v", "w")}}
+                 for tr, T in zip(trials, lengths)]
+    with _resident(trials, params, units, device) as eng:
+        n_failed = 0
+        if infer:
+            n_failed = eng.estep(SET_TEST, int(config["max_iter"] if n_iter is None else n_iter), config["dmu_bound"], vb)
+        joint = eng.joint_laplace(SET_TEST, max_iter=max_iter, tol=tol)
+        sums, _ = eng.loglik(SET_TEST, vb=vb)
+        gauss = eng.gauss.copy()
+    total = float(np.sum(joint["laplace"]))
+    _, ll_null, ny, _ = bits_per_spike(sums, sum(lengths), gauss)
+    if gauss.any() or not np.sum(ny) > 0:
+        bps = float("nan")
+    else:
+        bps = float((total - np.sum(ll_null)) / (np.sum(ny) * math.log(2.0)))
+    return {"mu": _per_trial(joint["mu"], lengths), "v": _per_trial(joint["v"], lengths), "laplace": joint["laplace"],
+            "converged": joint["converged"], "n_newton": joint["n_newton"], "total": total, "laplace_bps": bps,
+            "n_failed": int(n_failed) + int(joint["n_failed"])}

@@ -65,7 +65,7 @@ def best_candidate(n_factors_list, mean_co_bps):
 
 
 def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, seed=0, n_iter=None, device=0,
-                   score="co_bps", predictive=False, n_nodes=12, **fit_kwargs):
+                   score="co_bps", predictive=False, n_nodes=12, proposal="posterior", **fit_kwargs):
     """Score every ``n_factors`` of ``n_factors_list`` by co-smoothing bits per spike on held-out trials.
 
     For every trial fold and candidate: ``fit`` on fresh copies of the other trials (``fit_kwargs`` are ``fit``'s),
@@ -96,7 +96,16 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
 
     ``predictive=True`` scores ``co_bps`` and ``speckled_bps`` with the posterior-predictive density
     (``evaluation``'s docstring), ``n_nodes`` quadrature nodes per Poisson entry; ``marginal_bps`` is a score of whole
-    trials with no plug-in form to replace, and raises ``ValueError`` with it."""
+    trials with no plug-in form to replace, and raises ``ValueError`` with it.
+
+    ``proposal`` is ``marginal_loglik``'s and is passed through to ``score="marginal_bps"`` alone: ``"joint"`` draws from
+    the joint Laplace posterior of every held-out trial (``evaluation.joint_posterior``), whose effective sample size
+    does not collapse when the latents are coupled through the loadings.  With another score ``proposal="joint"`` raises
+    ``ValueError``."""
+    if proposal not in ("posterior", "joint"):
+        raise ValueError("proposal must be 'posterior' or 'joint', got %r" % (proposal,))
+    if proposal != "posterior" and score != "marginal_bps":
+        raise ValueError("proposal=%r applies to score='marginal_bps', not to %r" % (proposal, score))
     if score not in ("co_bps", "speckled_bps", "marginal_bps"):
         raise ValueError("score must be 'co_bps', 'speckled_bps' or 'marginal_bps', got %r" % (score,))
     if predictive and score == "marginal_bps":
@@ -129,7 +138,8 @@ def cross_validate(trials, n_factors_list, n_trial_folds=4, n_channel_folds=5, s
                 fitted = _seeded_fit(seed, _fresh(trials, train_idx), n, device=device, verbose=False, **fold_kwargs)
                 if marginal:
                     got = marginal_loglik(_fresh(trials, test_idx), fitted["params"], fitted["config"],
-                                          n_samples=int(n_channel_folds) * 16, seed=seed, n_iter=n_iter, device=device)
+                                          n_samples=int(n_channel_folds) * 16, seed=seed, n_iter=n_iter, device=device,
+                                          proposal=proposal)
                 elif speckled:
                     got = leave_entries_out(_fresh(trials, test_idx), fitted["params"], fitted["config"],
                                             n_folds=n_channel_folds, seed=seed, n_iter=n_iter, device=device,
