@@ -497,6 +497,40 @@ int vlgp_debug_switch(vlgp_ctx* ctx, const char* name, double* value);
  * out[1] the sum of their predicted ranks (even + odd block), out[2] evaluations that took the dense round,
  * out[3] low-rank rounds re-run densely because a rank exceeded the prediction. */
 int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]);
+/* What the most recent vlgp_hstep_objective call on this handle launched, as launch_hstep_impl decided it: the values are
+ * noted where the launcher settles them, nothing is computed for the report and no launch depends on it.  All slots are 0
+ * before the first call; a call refused for its arguments leaves the report of the call before it.
+ * out, VLGP_HSTEP_PLAN_LEN ints, at the slots VLGP_HP_*:
+ *   PATH, VLGP_PATH_HSTEP_*;  RERUN, 1 when this is the dense round that repeated a low-rank round whose rank exceeded
+ *   the host's prediction (out[3] of vlgp_debug_hstep_stats counts them);
+ *   round kernels (paths LOWRANK, DENSE, MIXED): TC the compiled window (50, 64), NB the segment blocks per evaluation
+ *   of the first launch, WLM 1 when the round read w latent-major;  LOWRANK and MIXED also: N_LR and N_ROUGH, the
+ *   evaluations on the low-rank and on the dense kernel, RMAX the largest predicted rank, CLASS the register class the
+ *   round was compiled for (16, 24, 28, 32), TABG 1 when the tables stayed in global memory, FUSED 1 when the workgroups
+ *   factored the kernel blocks themselves (no tables launch), LDS the dynamic LDS of the low-rank launch in doubles,
+ *   RCAP + e the columns evaluation e < 16 had room for (its predicted rank, at least 4; 0: a rough one);
+ *   generic kernels (path GENERIC): NW waves per workgroup of the segment kernel, TM_GLOBAL 1 when the K block's
+ *   matrices but the factor lay in global memory, HUGE 1 when the factor did too;  path BIG: the path only.
+ * Slots a path does not use hold 0, except that a round whose K did not factor leaves its slots beside those of the
+ * generic kernels that then ran. */
+#define VLGP_HP_PATH 0
+#define VLGP_HP_TC 1
+#define VLGP_HP_N_LR 2
+#define VLGP_HP_N_ROUGH 3
+#define VLGP_HP_RMAX 4
+#define VLGP_HP_CLASS 5
+#define VLGP_HP_TABG 6
+#define VLGP_HP_FUSED 7
+#define VLGP_HP_NB 8
+#define VLGP_HP_LDS 9
+#define VLGP_HP_WLM 10
+#define VLGP_HP_NW 11
+#define VLGP_HP_TM_GLOBAL 12
+#define VLGP_HP_HUGE 13
+#define VLGP_HP_RERUN 14
+#define VLGP_HP_RCAP 15            /* 16 slots */
+#define VLGP_HSTEP_PLAN_LEN 31
+int vlgp_debug_hstep_plan(vlgp_ctx* ctx, int out[VLGP_HSTEP_PLAN_LEN]);
 /* What vlgp_mstep would launch on this handle for a set of `rows` rows (rows >= 1), computed by the functions the launches
  * themselves use; launches nothing, needs no set.  out[0] G, the workgroups along the rows (partial sums per statistic),
  * [1] rows per workgroup, [2] CT channels per tile, [3] S row slices per workgroup, [4] threads per workgroup, [5] channel

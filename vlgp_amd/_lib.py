@@ -30,6 +30,11 @@ EP = dict(FAMILY=0, DECLINE=1, LT=2, REC=3, MAXRA=4, USE_LANE=5, MIX=6, MAXRA_HI
 ESTEP_PLAN_LEN = 54
 ESPLIT = ("TAKEN", "OFF", "GENERIC", "L", "N", "LSPLIT_OFF", "LONG_RANK", "LONG_FEW", "SMALL_SET", "RANK", "REC")
 ECLASS = ("LANE", "LO", "HI")
+# vlgp_debug_hstep_plan: the report's slots (VLGP_HP_*) and its length, as include/vlgp_hip.h has them
+# (tests/test_gpu_hstep_shapes.py compares the two)
+HP = dict(PATH=0, TC=1, N_LR=2, N_ROUGH=3, RMAX=4, CLASS=5, TABG=6, FUSED=7, NB=8, LDS=9, WLM=10, NW=11, TM_GLOBAL=12, HUGE=13,
+          RERUN=14, RCAP=15)
+HSTEP_PLAN_LEN = 31
 HSTEP_PATHS = ("none", "lowrank", "dense", "big", "generic", "old", "mixed")  # VLGP_PATH_HSTEP_*
 ERR_STATE = -3  # VLGP_ERR_STATE: call sequence error (missing prior, a replicated set where a plain one is needed ...)
 
@@ -112,6 +117,7 @@ _SIGNATURES = {
     "vlgp_debug_reload_switches": (C.c_int, [_h]),
     "vlgp_debug_switch": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
     "vlgp_debug_hstep_stats": (C.c_int, [_h, _dp]),
+    "vlgp_debug_hstep_plan": (C.c_int, [_h, _ip]),
     "vlgp_debug_mstep_plan": (C.c_int, [_h, C.c_int64, _ip]),
     "vlgp_debug_estep_plan": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip]),
     "vlgp_replicate_groups": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),

@@ -1736,6 +1736,13 @@ extern "C" int vlgp_debug_hstep_stats(vlgp_ctx* ctx, double out[4]) {
     return VLGP_OK;
 }
 
+extern "C" int vlgp_debug_hstep_plan(vlgp_ctx* ctx, int out[VLGP_HSTEP_PLAN_LEN]) {
+    NEED_CTX(ctx);
+    if (!out) return vlgp_fail(ctx, VLGP_ERR_ARG, "null out");
+    for (int i = 0; i < VLGP_HSTEP_PLAN_LEN; ++i) out[i] = ctx->hplan[i];
+    return VLGP_OK;
+}
+
 extern "C" int vlgp_debug_mstep_plan(vlgp_ctx* ctx, int64_t rows, int out[12]) {
     NEED_CTX(ctx);
     if (rows < 1 || !out) return vlgp_fail(ctx, VLGP_ERR_ARG, "bad plan arguments");

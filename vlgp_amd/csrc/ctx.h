@@ -244,6 +244,7 @@ struct vlgp_ctx {
     double h_t0 = 0.0;
     int last_hstep_path = 0;      // VLGP_PATH_HSTEP_* of the most recent H-step objective call
     double hstat[4] = {0.0, 0.0, 0.0, 0.0};  // vlgp_debug_hstep_stats
+    int hplan[VLGP_HSTEP_PLAN_LEN] = {};     // vlgp_debug_hstep_plan: what the most recent objective call launched
 
     // profiling
     bool prof_on = false;

@@ -1186,6 +1186,9 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
     if (n_eval > 16) return vlgp_fail(ctx, VLGP_ERR_ARG, "at most 16 evaluations per call, got %d", n_eval);
     for (int i = 0; i < n_eval; ++i)
         if (latent[i] < 0 || latent[i] >= L) return vlgp_fail(ctx, VLGP_ERR_ARG, "latent index out of range");
+    int* hplan = ctx->hplan;  // vlgp_debug_hstep_plan: noted where the values are decided, read by nothing here
+    memset(hplan, 0, sizeof(ctx->hplan));
+    hplan[VLGP_HP_RERUN] = force_dense ? 1 : 0;  // (only the re-run after an overflow forces the dense round)
 
     if (fast) {
         HFastArgs F;
@@ -1306,6 +1309,16 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                 ctx->hstat[2] += n_eval;
             }
             ctx->last_hstep_path = lr ? (mixed ? VLGP_PATH_HSTEP_MIXED : VLGP_PATH_HSTEP_LOWRANK) : VLGP_PATH_HSTEP_DENSE;
+            hplan[VLGP_HP_PATH] = ctx->last_hstep_path;
+            hplan[VLGP_HP_TC] = TC;
+            hplan[VLGP_HP_NB] = R.nb;
+            hplan[VLGP_HP_WLM] = F.wlm != nullptr;
+            if (lr) {
+                hplan[VLGP_HP_N_LR] = n_lr;
+                hplan[VLGP_HP_N_ROUGH] = n_rough;
+                hplan[VLGP_HP_RMAX] = rmax;
+                for (int e = 0; e < n_eval; ++e) hplan[VLGP_HP_RCAP + e] = rcap[e];
+            }
             // single rank: the kernel publishes to the host mailbox.  Several ranks: same, then the ranks add
             // their sums on the host (vlgp_hx_allreduce); without the exchange segment the sums go through the
             // device all-reduce and a copy instead
@@ -1351,6 +1364,10 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                     const int grid = Rc.k_blocks + Rc.lr_nev * R.nb;
                     Rc.lds_doubles = need;
                     const bool fuse = sw.hstep_fuse_tables && rmax <= 24;
+                    hplan[VLGP_HP_CLASS] = rc_cls;
+                    hplan[VLGP_HP_TABG] = tabg;
+                    hplan[VLGP_HP_FUSED] = fuse;
+                    hplan[VLGP_HP_LDS] = need;
                     if (fuse && TC == 50 && ci == 0) CHK((launch_round_lr<50, 16, false, true>(ctx, Rc, grid, lds_bytes)));
                     else if (fuse && TC == 50 && ci == 1) CHK((launch_round_lr<50, 24, false, true>(ctx, Rc, grid, lds_bytes)));
                     else if (fuse && ci == 0) CHK((launch_round_lr<64, 16, false, true>(ctx, Rc, grid, lds_bytes)));
@@ -1474,6 +1491,8 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
     const bool big = T > 64 && T <= 128 && !sw.hstep_generic_seg;  // hstep_prep_big / hstep_seg_big
     ctx->last_hstep_path = big ? VLGP_PATH_HSTEP_BIG : VLGP_PATH_HSTEP_GENERIC;
+    hplan[VLGP_HP_PATH] = ctx->last_hstep_path;
+    hplan[VLGP_HP_HUGE] = huge;
     if (big) {
         const size_t lds_pb = (size_t)(4 * 64 * 66 + HmGeom<64>::TASK + 2 * 128) * 8;
         HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(hstep_prep_big),
@@ -1502,6 +1521,8 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
     S.bmat = huge ? W + o_bmat : nullptr;
     const int nw = huge ? 4 : ((size_t)2 * (T * (T | 1) + 2 * T) * 8 <= 160 * 1024 ? 2 : 1);
     const size_t lds_seg = huge ? (size_t)nw * 2 * T * 8 : (size_t)nw * (T * (T | 1) + 2 * T) * 8;
+    hplan[VLGP_HP_NW] = nw;
+    hplan[VLGP_HP_TM_GLOBAL] = P.tm != nullptr;
     if (lds_seg > 64 * 1024)
         HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(hstep_seg_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_seg));

@@ -639,6 +639,21 @@ class Engine:
         self._ck(self.lib.vlgp_debug_hstep_stats(self.h, dptr(out)))
         return out
 
+    def hstep_plan(self):
+        """What the most recent ``hstep_objective`` call launched (vlgp_debug_hstep_plan: noted by the launcher where it
+        decides, nothing recomputed).  A dict: ``path`` (one of _lib.HSTEP_PATHS), ``rerun`` (the dense round after a
+        low-rank overflow); round kernels: TC, nb, wlm; low-rank and mixed rounds also n_lr, n_rough, rmax, rc (the
+        register class 16 / 24 / 28 / 32), tabg, fused, lds (doubles), rcap (16 slots, per evaluation); generic kernels:
+        nw, tm_global, huge."""
+        out = np.zeros(_lib.HSTEP_PLAN_LEN, dtype=np.int32)
+        self._ck(self.lib.vlgp_debug_hstep_plan(self.h, iptr(out)))
+        o = [int(v) for v in out]
+        at = lambda name: o[_lib.HP[name]]
+        return dict(path=_lib.HSTEP_PATHS[at("PATH")], rerun=at("RERUN"), TC=at("TC"), nb=at("NB"), wlm=at("WLM"),
+                    n_lr=at("N_LR"), n_rough=at("N_ROUGH"), rmax=at("RMAX"), rc=at("CLASS"), tabg=at("TABG"), fused=at("FUSED"),
+                    lds=at("LDS"), rcap=o[_lib.HP["RCAP"]:_lib.HP["RCAP"] + 16], nw=at("NW"), tm_global=at("TM_GLOBAL"),
+                    huge=at("HUGE"))
+
     MSTEP_PLAN_KEYS = ("G", "rows_per_wg", "CT", "S", "nthr", "tiles", "LT", "PT", "exact", "fixed", "anyg", "noise_passes")
 
     def mstep_plan(self, rows):
