@@ -1,5 +1,6 @@
 // C ABI of libvlgp_hip.so (include/vlgp_hip.h): handle management, host<->device
-// marshalling and the thin wrappers around the kernel launchers (communication between ranks: comm.hip).
+// marshalling and the thin wrappers around the kernel launchers (communication between ranks: comm.hip; the read-only
+// scores of a set: eval_api.hip).
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -149,12 +150,13 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_replicate, SET_PLAIN | SET_SOURCE,                                                                         \
       "replicate a plain uploaded set (set %d is a cut, a replica or has overlaps)") /* the source, _groups / _masked */ \
     X(destination, SET_ANY & ~SET_SOURCE, nullptr) /* of vlgp_cut_units and the replicate calls: any set, or none yet */
-struct Admission { const char* what; unsigned kinds; const char* refusal; };
-#define X(name, kinds, refusal) static const Admission admit_##name = {#name, kinds, refusal};
+#define X(name, kinds, refusal) \
+    extern const Admission admit_##name; /* (ctx.h declares the ones eval_api.hip uses) */ \
+    const Admission admit_##name = {#name, kinds, refusal};
 SET_ADMISSION(X)
 #undef X
 
-static int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a) {
+int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a) {
     if (us->is_source() && !(a.kinds & SET_SOURCE))
         return vlgp_fail(ctx, VLGP_ERR_STATE, "set %d is the source of a replicated set: free the replicas first", set);
     if (us->is(a.kinds)) return VLGP_OK;
@@ -164,19 +166,10 @@ static int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a) 
     return vlgp_fail(ctx, VLGP_ERR_STATE, a.refusal, set);
 }
 
-// How a set-taking entry point opens: what it waits for and invalidates, in this order, then the set and its admission.
-enum : unsigned {
-    OPEN_COLLECT = 1,   // host-side ranks of a lazy prior build (vlgp_prior_collect)
-    OPEN_STALE = 2,     // unit state changes: the cached H-step moments are stale
-    OPEN_JOIN = 4,      // vlgp_join_m: the M-step lane and a queued norms pass, write_epoch bumped
-    OPEN_WAIT = 8,      // the same two waits without the bump: the call only reads (what vlgp_hstep_prepare built stays)
-    OPEN_PARAMS = 16,   // parameters must be set
-    OPEN_DEVICE = 32,   // hipSetDevice
-    OPEN_EMPTY = 64,    // the slot may be empty (upload, free)
-};
+// How a set-taking entry point opens (the OPEN_* flags: ctx.h), in this order, then the set and its admission.
 #define NEED_PARAMS(ctx) \
     if (!(ctx)->have_params) return vlgp_fail(ctx, VLGP_ERR_STATE, "parameters not set (vlgp_set_params)")
-static int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a) {
+int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a) {
     NEED_CTX(ctx);
     if (how & OPEN_COLLECT) CHK(vlgp_prior_collect(ctx));
     if (how & OPEN_STALE) ctx->hmom_us = nullptr;
@@ -545,7 +538,7 @@ extern "C" int vlgp_free_units(vlgp_ctx* ctx, int set) {
     return VLGP_OK;
 }
 
-// ---- leave-group-out replicas and held-out likelihood --------------------------
+// ---- leave-group-out replicas (their scores and every other read-only score: eval_api.hip) ----
 // what every replicate call checks of its two sets once its own arguments are sound
 static int replicas_check(vlgp_ctx* ctx, int src, int dst, int n_rep, const UnitSet* s, const UnitSet* d) {
     CHK(admit(ctx, src, s, admit_vlgp_replicate));
@@ -683,353 +676,6 @@ extern "C" int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, 
     std::vector<int> start((size_t)(n_rep > 0 ? n_rep : 0) + 1);  // (n_rep < 1 is refused there, after the set checks)
     for (size_t k = 0; k < start.size(); ++k) start[k] = (int)k;
     return vlgp_replicate_groups(ctx, src, dst, n_rep, start.data(), channel);
-}
-
-extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums) {
-    UnitSet* us = nullptr;
-    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
-    if (!sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik needs sums");
-    CHK(admit(ctx, set, us, admit_vlgp_loglik));
-    const bool by_row = us->is(SET_BY_ROW);
-    if (by_row && rate && us->rep.overlap)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik: the masks of set %d overlap (an entry is held out by more than one "
-                         "replica): no rate, sums only", set);
-    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
-    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
-    const LoglikShape S = vlgp_loglik_shape(ctx, *us);
-    const int64_t slots = S.slots, n_rate = S.n_rate, o_sums = rate ? n_rate : 0;
-    double* d_rate = nullptr;
-    double* d_out = nullptr;
-    HIPCHK(ctx, hipMalloc(&d_out, sizeof(double) * (size_t)(o_sums + 4 * slots)));
-    if (rate) d_rate = d_out;
-    int rc = VLGP_OK;
-    if (by_row && rate &&  // NaN (every byte 0xff) where no replica holds the entry out
-        hipMemsetAsync(d_rate, 0xff, sizeof(double) * (size_t)n_rate, ctx->stream) != hipSuccess)
-        rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_loglik: filling the rates failed");
-    if (rc == VLGP_OK) rc = launch_loglik(ctx, *us, vb, d_rate, d_out + o_sums);
-    if (rc == VLGP_OK) {
-        hipError_t e = hipMemcpyAsync(sums, d_out + o_sums, sizeof(double) * 4 * slots, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && rate)
-            e = hipMemcpyAsync(rate, d_rate, sizeof(double) * (size_t)n_rate, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_loglik copy-out failed: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
-    return rc;
-}
-
-// ---- variational lower bound -----------------------------------------------------
-// what vlgp_elbo and vlgp_forecast do first: a plain set with parameters, xb and its priors bound, nothing pending.  The
-// waits of vlgp_join_m without its epoch bump: both calls only read, so what vlgp_hstep_prepare built stays valid
-static int open_posterior(vlgp_ctx* ctx, int set, const Admission& a, UnitSet** out) {
-    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, out, &a));
-    if (!(*out)->x_ones) CHK(vlgp_refresh_xb(ctx, **out));
-    return vlgp_bind_priors(ctx, **out);
-}
-
-// the largest effective rank among the set's lengths: it sizes the LDS of the (unit, latent) kernels
-static int set_rank_max(vlgp_ctx* ctx, const UnitSet& us) {
-    int rp = 1, T_seen = -1;
-    for (int m = 0; m < us.M; ++m) {
-        const int T = (int)(us.off[m + 1] - us.off[m]);
-        if (T == T_seen) continue;
-        T_seen = T;
-        const Prior& pr = ctx->priors.find(T)->second;  // (vlgp_bind_priors found every length)
-        for (int l = 0; l < ctx->L; ++l) rp = std::max(rp, pr.rl[l]);
-    }
-    return rp;
-}
-
-// the flags of the (unit, latent) tasks, behind everything queued on the stream; *n_failed = how many are set
-static hipError_t count_flags(vlgp_ctx* ctx, const int* d_flag, int64_t tasks, int* n_failed) {
-    std::vector<int> flag((size_t)tasks);
-    hipError_t e = hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && n_failed) *n_failed = (int)(tasks - std::count(flag.begin(), flag.end(), 0));
-    return e;
-}
-
-extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms,
-                         int* n_failed) {
-    UnitSet* us = nullptr;
-    CHK(open_posterior(ctx, set, admit_vlgp_elbo, &us));
-    if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
-    if (n_failed) *n_failed = 0;
-    const int rp = set_rank_max(ctx, *us);
-    const int N = ctx->N, L = ctx->L;
-    const int64_t tasks = (int64_t)us->M * L;
-    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo: too many (unit, latent) pairs");
-    const int64_t n_blk = (us->rows + 255) / 256;
-    const int64_t o_sums = (int64_t)N * n_blk * 4, o_terms = o_sums + 4 * (int64_t)N, o_rows = o_terms + 4 * tasks;
-    const int64_t o_flag = o_rows + (row_ell ? us->rows : 0), need = o_flag + (tasks + 1) / 2;
-    if (need > ctx->elbo_len) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_elbo) HIPCHK(ctx, hipFree(ctx->d_elbo));
-        ctx->d_elbo = nullptr;
-        ctx->elbo_len = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_elbo, sizeof(double) * (size_t)(need + need / 4)));
-        ctx->elbo_len = need + need / 4;
-    }
-    double* d = ctx->d_elbo;
-    int* d_flag = reinterpret_cast<int*>(d + o_flag);
-    CHK(launch_elbo(ctx, *us, vb, rp, d, d + o_sums, row_ell ? d + o_rows : nullptr, d + o_terms, d_flag));
-    HIPCHK(ctx, hipMemcpyAsync(row_sums, d + o_sums, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(kl_terms, d + o_terms, sizeof(double) * 4 * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream));
-    if (row_ell)
-        HIPCHK(ctx, hipMemcpyAsync(row_ell, d + o_rows, sizeof(double) * (size_t)us->rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, count_flags(ctx, d_flag, tasks, n_failed));
-    return VLGP_OK;
-}
-
-// ---- forward prediction ------------------------------------------------------------
-extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
-                             const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed) {
-    UnitSet* us = nullptr;
-    CHK(open_posterior(ctx, set, admit_vlgp_forecast, &us));
-    if (us->is(SET_TILING | SET_COPIED)) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_forecast refuses a cut set (set %d is cut from set %d)", set, us->parent);
-    if (n_lengths < 1 || !lengths || !n_ext || !G_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs lengths, n_ext and G_ext");
-    if (!mu_ext || !v_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs mu_ext and v_ext");
-    const int N = ctx->N, L = ctx->L, R = ctx->R, M = us->M;
-    std::vector<int64_t> blk((size_t)n_lengths + 1, 0);  // offsets of the (L, n_ext[k], R) blocks inside G_ext
-    for (int k = 0; k < n_lengths; ++k) {
-        if (k > 0 && lengths[k] <= lengths[k - 1])
-            return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: lengths must be strictly increasing (lengths[%d] = %d)", k, lengths[k]);
-        if (n_ext[k] < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: n_ext[%d] = %d for length %d, need >= 1", k, n_ext[k], lengths[k]);
-        blk[(size_t)k + 1] = blk[(size_t)k] + (int64_t)L * n_ext[k] * R;
-    }
-    std::vector<int64_t> tab((size_t)2 * M + 1);  // ext_off (M + 1) | gx_off (M)
-    int64_t* ext_off = tab.data();
-    int64_t* gx_off = ext_off + M + 1;
-    ext_off[0] = 0;
-    for (int m = 0; m < M; ++m) {
-        const int T = (int)(us->off[m + 1] - us->off[m]);
-        const int* at = std::lower_bound(lengths, lengths + n_lengths, T);
-        if (at == lengths + n_lengths || *at != T)
-            return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: unit %d has length %d, which is not listed", m, T);
-        ext_off[m + 1] = ext_off[m] + n_ext[at - lengths];
-        gx_off[m] = blk[(size_t)(at - lengths)];
-    }
-    const int64_t tasks = (int64_t)M * L, n_out = ext_off[M] * L;
-    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: too many (unit, latent) pairs");
-    if (n_failed) *n_failed = 0;
-    const int rp = set_rank_max(ctx, *us);
-    // one device block of the call's own: z | G_ext | mu_ext | v_ext | terms | the two tables | flags
-    const int64_t o_g = us->rows * L, o_mu = o_g + blk[(size_t)n_lengths], o_v = o_mu + n_out, o_terms = o_v + n_out;
-    const int64_t o_tab = o_terms + 2 * tasks, o_flag = o_tab + (int64_t)tab.size(), need = o_flag + (tasks + 1) / 2;
-    double* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
-    int* d_flag = reinterpret_cast<int*>(d + o_flag);
-    int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
-    int rc = VLGP_OK;
-    hipError_t e = hipMemcpyAsync(d + o_g, G_ext, sizeof(double) * (size_t)blk[(size_t)n_lengths], hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_forecast copy-in failed: %s", hipGetErrorString(e));
-    if (rc == VLGP_OK)
-        rc = launch_forecast(ctx, *us, vb, rp, d, d_tab, d_tab + M + 1, d + o_g, d + o_mu, d + o_v, d + o_terms, d_flag);
-    if (rc == VLGP_OK) {
-        e = hipMemcpyAsync(mu_ext, d + o_mu, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(v_ext, d + o_v, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && fit_terms)
-            e = hipMemcpyAsync(fit_terms, d + o_terms, sizeof(double) * 2 * (size_t)tasks, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = count_flags(ctx, d_flag, tasks, n_failed);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_forecast copy-out failed: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-// ---- importance weights of the marginal likelihood -----------------------------------
-extern "C" int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* eps, double* log_w,
-                             double* parts, int* n_failed) {
-    UnitSet* us = nullptr;
-    CHK(open_posterior(ctx, set, admit_vlgp_marginal, &us));
-    if (n_samples < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal: n_samples = %d, need >= 1", n_samples);
-    if (!eps || !log_w) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal needs eps and log_w");
-    const int L = ctx->L, R = ctx->R, M = us->M;
-    const int64_t tasks = (int64_t)M * L, K = n_samples;
-    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal: too many (unit, latent) pairs");
-    if (n_failed) *n_failed = 0;
-    const int rp = set_rank_max(ctx, *us);
-    const int tile_rows = marginal_tile_rows(L);
-    std::vector<int64_t> tile_off((size_t)M + 1, 0);  // first row tile of each unit
-    for (int m = 0; m < M; ++m) tile_off[(size_t)m + 1] = tile_off[(size_t)m] + (us->off[m + 1] - us->off[m] + tile_rows - 1) / tile_rows;
-    const int64_t n_tiles = tile_off[(size_t)M];
-    // one device block of the call's own, for 64 samples at a time whatever n_samples is:
-    // z | eps | beta | c | tile partials | log_w | parts | tile_off | flags
-    const int64_t o_eps = us->rows * L, o_beta = o_eps + tasks * R * 64, o_c = o_beta + tasks * R * 64, o_part = o_c + tasks * 64;
-    const int64_t o_lw = o_part + n_tiles * 64, o_parts = o_lw + (int64_t)M * 64, o_tab = o_parts + (int64_t)M * 128;
-    const int64_t o_flag = o_tab + M + 1, need = o_flag + (tasks + 1) / 2;
-    double* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
-    int* d_flag = reinterpret_cast<int*>(d + o_flag);
-    int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
-    int rc = VLGP_OK;
-    hipError_t e = hipMemcpyAsync(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal copy-in failed: %s", hipGetErrorString(e));
-    if (rc == VLGP_OK) rc = launch_forecast_z(ctx, *us, vb, d);
-    const size_t dbl = sizeof(double);
-    for (int64_t k0 = 0; k0 < K && rc == VLGP_OK; k0 += 64) {  // (the copies of a chunk and its kernels are stream-ordered)
-        const int kc = (int)std::min<int64_t>(64, K - k0);
-        e = hipMemcpy2DAsync(d + o_eps, 64 * dbl, eps + k0, (size_t)K * dbl, (size_t)kc * dbl, (size_t)(tasks * R),
-                             hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal copy-in failed: %s", hipGetErrorString(e));
-        if (rc == VLGP_OK)
-            rc = launch_marginal(ctx, *us, rp, kc, d, d + o_eps, d + o_beta, d + o_c, d + o_part, tile_rows, d_tab, n_tiles,
-                                 d + o_lw, d + o_parts, d_flag);
-        if (rc != VLGP_OK) break;
-        e = hipMemcpy2DAsync(log_w + k0, (size_t)K * dbl, d + o_lw, 64 * dbl, (size_t)kc * dbl, (size_t)M, hipMemcpyDeviceToHost,
-                             ctx->stream);
-        if (e == hipSuccess && parts)
-            e = hipMemcpy2DAsync(parts + 2 * k0, (size_t)K * 2 * dbl, d + o_parts, 128 * dbl, (size_t)kc * 2 * dbl, (size_t)M,
-                                 hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal copy-out failed: %s", hipGetErrorString(e));
-    }
-    if (rc == VLGP_OK && count_flags(ctx, d_flag, tasks, n_failed) != hipSuccess)
-        rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_marginal: reading the flags failed");
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-// ---- joint Laplace posterior ----------------------------------------------------------
-extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_samples, const double* eps,
-                                  double* beta, double* stats, double* mu, double* v, double* log_w, double* parts,
-                                  int* n_failed) {
-    UnitSet* us = nullptr;
-    CHK(open_posterior(ctx, set, admit_vlgp_joint_laplace, &us));
-    if (max_iter < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: max_iter = %d, need >= 1", max_iter);
-    if (!(tol > 0.0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: tol = %g, need > 0", tol);
-    if (n_samples < 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples = %d, need >= 0", n_samples);
-    if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace needs stats");
-    if (n_samples > 0 && (!eps || !log_w)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples > 0 needs eps and log_w");
-    const int L = ctx->L, R = ctx->R, M = us->M;
-    const int64_t tasks = (int64_t)M * L, K = n_samples, rows = us->rows;
-    if (tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: too many (unit, latent) pairs");
-    int Dmax = 1;
-    for (int m = 0; m < M; ++m) {  // D = sum_l r_l of the unit's length
-        const Prior& pr = ctx->priors.find((int)(us->off[m + 1] - us->off[m]))->second;  // (vlgp_bind_priors found every length)
-        int D = 0;
-        for (int l = 0; l < L; ++l) D += pr.rl[l];
-        if (D > 512)
-            return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_joint_laplace: unit %d has D = %d weights, at most 512 are supported", m, D);
-        Dmax = std::max(Dmax, D);
-    }
-    if (n_failed) *n_failed = 0;
-    const int rp = set_rank_max(ctx, *us);
-    const int tile_rows = marginal_tile_rows(L);
-    std::vector<int64_t> tile_off((size_t)M + 1, 0);  // first row tile of each unit
-    for (int m = 0; m < M; ++m) tile_off[(size_t)m + 1] = tile_off[(size_t)m] + (us->off[m + 1] - us->off[m] + tile_rows - 1) / tile_rows;
-    const int64_t n_tiles = tile_off[(size_t)M];
-    // one device block of the call's own: the Newton workspace | stats | v | and for the draws, 64 at a time whatever
-    // n_samples is: eps | beta_k | c | tile partials | log_w | parts | tile_off
-    const int64_t o_stats = joint_work_doubles(ctx, *us, Dmax, nullptr), o_v = o_stats + 8 * (int64_t)M, o_eps = o_v + rows * L;
-    const int64_t o_beta = o_eps + (K ? tasks * R * 64 : 0), o_c = o_beta + (K ? tasks * R * 64 : 0), o_part = o_c + (K ? tasks * 64 : 0);
-    const int64_t o_lw = o_part + (K ? n_tiles * 64 : 0), o_parts = o_lw + (K ? (int64_t)M * 64 : 0);
-    const int64_t o_tab = o_parts + (K ? (int64_t)M * 128 : 0), need = o_tab + M + 1;
-    double* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
-    JointWork W;
-    W.base = d;
-    (void)joint_work_doubles(ctx, *us, Dmax, &W);
-    int64_t* d_tab = reinterpret_cast<int64_t*>(d + o_tab);
-    const size_t dbl = sizeof(double);
-    int rc = launch_joint_init(ctx, *us, rp, W);
-    hipError_t e = hipSuccess;
-    // every round finishes a unit, factors it (at most max_iter times) or halves its step (at most 30 times per factor)
-    for (int64_t round = 0, done = 0; rc == VLGP_OK && done < M && round <= 32 * ((int64_t)max_iter + 1); ++round) {
-        rc = launch_joint_round(ctx, *us, W, max_iter, tol);
-        if (rc != VLGP_OK) break;
-        int nd = 0;
-        e = hipMemcpyAsync(&nd, W.n_done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace: a Newton round failed: %s", hipGetErrorString(e));
-        done = nd;
-    }
-    if (rc == VLGP_OK) rc = launch_joint_finish(ctx, *us, rp, W, d + o_stats, mu || v ? W.g : nullptr, mu || v ? d + o_v : nullptr);
-    if (rc == VLGP_OK) {
-        e = hipMemcpyAsync(stats, d + o_stats, dbl * 8 * (size_t)M, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && beta) e = hipMemcpyAsync(beta, W.beta, dbl * (size_t)(tasks * R), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && mu) e = hipMemcpyAsync(mu, W.g, dbl * (size_t)(rows * L), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && v) e = hipMemcpyAsync(v, d + o_v, dbl * (size_t)(rows * L), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && K)
-            e = hipMemcpyAsync(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size(), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace copy-out failed: %s", hipGetErrorString(e));
-    }
-    if (rc == VLGP_OK && n_failed)
-        for (int m = 0; m < M; ++m) *n_failed += stats[8 * (size_t)m] != stats[8 * (size_t)m] ? 1 : 0;  // (NaN: the unit failed)
-    for (int64_t k0 = 0; k0 < K && rc == VLGP_OK; k0 += 64) {  // (the copies of a chunk and its kernels are stream-ordered)
-        const int kc = (int)std::min<int64_t>(64, K - k0);
-        e = hipMemcpy2DAsync(d + o_eps, 64 * dbl, eps + k0, (size_t)K * dbl, (size_t)kc * dbl, (size_t)(tasks * R),
-                             hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace copy-in failed: %s", hipGetErrorString(e));
-        if (rc == VLGP_OK) rc = launch_joint_draw(ctx, *us, W, kc, d + o_eps, d + o_beta, d + o_c);
-        if (rc == VLGP_OK)
-            rc = launch_marginal_rows(ctx, *us, "vlgp_joint_laplace", kc, d + o_beta, d + o_c, d + o_part, tile_rows, d_tab,
-                                      n_tiles, d + o_lw, d + o_parts);
-        if (rc != VLGP_OK) break;
-        e = hipMemcpy2DAsync(log_w + k0, (size_t)K * dbl, d + o_lw, 64 * dbl, (size_t)kc * dbl, (size_t)M, hipMemcpyDeviceToHost,
-                             ctx->stream);
-        if (e == hipSuccess && parts)
-            e = hipMemcpy2DAsync(parts + 2 * k0, (size_t)K * 2 * dbl, d + o_parts, 128 * dbl, (size_t)kc * 2 * dbl, (size_t)M,
-                                 hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_joint_laplace copy-out failed: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
-}
-
-// ---- posterior-predictive density ------------------------------------------------------
-// vlgp_loglik's shapes with a second per-entry output; the waits of a read-only call (no epoch bump) and a device block of
-// the call's own for the nodes, the outputs and the partials: d_work may belong to a prepared H-step
-extern "C" int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa,
-                               double* rate, double* lpd, double* sums) {
-    UnitSet* us = nullptr;
-    CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
-    if (n_nodes < 1 || n_nodes > 64)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: n_nodes = %d, need 1 <= n_nodes <= 64", n_nodes);
-    if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive needs z, lwa and sums");
-    CHK(admit(ctx, set, us, admit_vlgp_predictive));
-    const bool by_row = us->is(SET_BY_ROW);
-    if (by_row && (rate || lpd) && us->rep.overlap)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: the masks of set %d overlap (an entry is held out by more than "
-                         "one replica): no rate or lpd, sums only", set);
-    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
-    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
-    const LoglikShape S = vlgp_loglik_shape(ctx, *us);
-    const int64_t n_blk = (rows_of.rows + 255) / 256;
-    if (S.slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: too many (replica, channel) slots");
-    // nodes (2 x 64) | rate | lpd | sums | partials
-    const int64_t o_rate = 128, o_lpd = o_rate + (rate ? S.n_rate : 0), o_sums = o_lpd + (lpd ? S.n_rate : 0);
-    const int64_t o_part = o_sums + 4 * S.slots, need = o_part + S.slots * n_blk * 4;
-    double* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, sizeof(double) * (size_t)need));
-    double* d_rate = rate ? d + o_rate : nullptr;
-    double* d_lpd = lpd ? d + o_lpd : nullptr;
-    int rc = VLGP_OK;
-    hipError_t e = hipMemcpyAsync(d, z, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + n_nodes, lwa, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && by_row && o_sums > o_rate)  // NaN (every byte 0xff) where no replica holds the entry out
-        e = hipMemsetAsync(d + o_rate, 0xff, sizeof(double) * (size_t)(o_sums - o_rate), ctx->stream);
-    if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_predictive copy-in failed: %s", hipGetErrorString(e));
-    if (rc == VLGP_OK) rc = launch_predictive(ctx, *us, vb, n_nodes, d, d_rate, d_lpd, d + o_part, d + o_sums);
-    if (rc == VLGP_OK) {
-        e = hipMemcpyAsync(sums, d + o_sums, sizeof(double) * 4 * (size_t)S.slots, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && rate)
-            e = hipMemcpyAsync(rate, d_rate, sizeof(double) * (size_t)S.n_rate, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && lpd)
-            e = hipMemcpyAsync(lpd, d_lpd, sizeof(double) * (size_t)S.n_rate, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vlgp_fail(ctx, VLGP_ERR_HIP, "vlgp_predictive copy-out failed: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return rc;
 }
 
 // ---- parameters ------------------------------------------------------------

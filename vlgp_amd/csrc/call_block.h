@@ -1,0 +1,128 @@
+// The frame of a scoring entry point (eval_api.hip): the layout of the call's one device block, the block
+// itself and the copies in and out of it.  The layouts are plain integer arithmetic, so a host program without HIP can
+// include this header (tests/call_block_driver.cpp); the block and the copies exist under hipcc only.
+#pragma once
+#include <stdint.h>
+static_assert(sizeof(double) == 8, "offsets and pitches count 8-byte doubles");
+
+// Regions of a block of doubles, handed out front to back: each call returns the region's offset (in doubles) and advances.
+struct BlockLayout {
+    int64_t at = 0;
+    int64_t doubles(int64_t n) { const int64_t o = at; at += n; return o; }
+    int64_t ints(int64_t n) { return doubles((n + 1) / 2); }  // two int per double
+    int64_t i64(int64_t n) { return doubles(n); }             // (offsets count doubles: 8-byte aligned wherever it starts)
+    int64_t need() const { return at; }
+};
+
+// ---- the blocks of the six calls: integers in, named offsets and `need` out; the regions in the order of the block -------
+// (a braced list is evaluated left to right: the initialisers below ARE the order of the regions)
+// rate (n_rate, when wanted) | sums (slots, 4); the partials live in vlgp_ctx::d_work
+struct LoglikLayout { int64_t rate, sums, need; };
+inline LoglikLayout loglik_layout(int64_t slots, int64_t n_rate, bool want_rate) {
+    BlockLayout b;
+    return {b.doubles(want_rate ? n_rate : 0), b.doubles(4 * slots), b.need()};
+}
+
+// nodes (z | lwa, 2 x 64) | rate | lpd (n_rate each, when wanted) | sums (slots, 4) | partials (slots, n_blk, 4)
+struct PredictiveLayout { int64_t nodes, rate, lpd, sums, part, need; };
+inline PredictiveLayout predictive_layout(int64_t slots, int64_t n_rate, int64_t n_blk, bool want_rate, bool want_lpd) {
+    BlockLayout b;
+    return {b.doubles(128), b.doubles(want_rate ? n_rate : 0), b.doubles(want_lpd ? n_rate : 0), b.doubles(4 * slots),
+            b.doubles(slots * n_blk * 4), b.need()};
+}
+
+// partials (N, n_blk, 4) | sums (N, 4) | terms (tasks, 4) | row_ell (rows, when wanted) | flags (tasks)
+struct ElboLayout { int64_t part, sums, terms, rows, flag, need; };
+inline ElboLayout elbo_layout(int64_t rows, int64_t N, int64_t tasks, int64_t n_blk, bool want_rows) {
+    BlockLayout b;
+    return {b.doubles(N * n_blk * 4), b.doubles(4 * N), b.doubles(4 * tasks), b.doubles(want_rows ? rows : 0), b.ints(tasks),
+            b.need()};
+}
+
+// z (rows, L) | G_ext (g_len) | mu_ext | v_ext (n_out each) | terms (tasks, 2) | ext_off (M + 1), gx_off (M) | flags (tasks)
+struct ForecastLayout { int64_t z, g, mu, v, terms, tab, flag, need; };
+inline ForecastLayout forecast_layout(int64_t rows, int64_t L, int64_t M, int64_t g_len, int64_t n_out) {
+    BlockLayout b;
+    return {b.doubles(rows * L), b.doubles(g_len), b.doubles(n_out), b.doubles(n_out), b.doubles(2 * M * L), b.i64(2 * M + 1),
+            b.ints(M * L), b.need()};
+}
+
+// The sample stage of vlgp_marginal and vlgp_joint_laplace, for 64 draws at a time whatever n_samples is (tasks = M L):
+// eps | beta (tasks, R, 64 each) | c (tasks, 64) | tile partials (n_tiles, 64) | log_w (M, 64) | parts (M, 64, 2) |
+// tile_off (M + 1).  Without draws only the table is left.
+struct SampleLayout { int64_t eps, beta, c, part, lw, parts, tab; };
+inline SampleLayout sample_layout(BlockLayout& b, int64_t M, int64_t L, int64_t R, int64_t n_tiles, bool draws) {
+    const int64_t k = draws ? 64 : 0;
+    return {b.doubles(M * L * R * k), b.doubles(M * L * R * k), b.doubles(M * L * k), b.doubles(n_tiles * k), b.doubles(M * k),
+            b.doubles(M * 2 * k), b.i64(M + 1)};
+}
+
+// z (rows, L) | the sample stage | flags (tasks)
+struct MarginalLayout { int64_t z; SampleLayout s; int64_t flag, need; };
+inline MarginalLayout marginal_layout(int64_t rows, int64_t L, int64_t R, int64_t M, int64_t n_tiles) {
+    BlockLayout b;
+    return {b.doubles(rows * L), sample_layout(b, M, L, R, n_tiles, true), b.ints(M * L), b.need()};
+}
+
+// the Newton workspace (`work` doubles: joint_work_doubles) | stats (M, 8) | v (rows, L) | the sample stage, when K > 0
+struct JointLayout { int64_t work, stats, v; SampleLayout s; int64_t need; };
+inline JointLayout joint_layout(int64_t work, int64_t rows, int64_t L, int64_t R, int64_t M, int64_t n_tiles, int64_t K) {
+    BlockLayout b;
+    return {b.doubles(work), b.doubles(8 * M), b.doubles(rows * L), sample_layout(b, M, L, R, n_tiles, K > 0), b.need()};
+}
+
+#ifdef __HIPCC__
+#include "ctx.h"
+
+// The call's own device block.  Leaving the call, by whichever return, waits for what the call queued on the stream and
+// frees the block: early CHK / HIPCHK returns are safe.
+struct CallBlock {
+    vlgp_ctx* ctx;
+    double* d = nullptr;
+    explicit CallBlock(vlgp_ctx* c) : ctx(c) {}
+    CallBlock(const CallBlock&) = delete;
+    CallBlock& operator=(const CallBlock&) = delete;
+    ~CallBlock() {
+        if (!d) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d);
+    }
+    hipError_t alloc(int64_t need) { return hipMalloc(&d, sizeof(double) * (size_t)need); }
+    double* at(int64_t o) const { return d + o; }
+    double* opt(bool want, int64_t o) const { return want ? d + o : nullptr; }
+    int* ints(int64_t o) const { return reinterpret_cast<int*>(d + o); }
+    int64_t* i64(int64_t o) const { return reinterpret_cast<int64_t*>(d + o); }
+};
+
+// Copies on the context's stream that remember the first error: after one, the rest are skipped.
+struct Copies {
+    vlgp_ctx* ctx;
+    hipError_t e = hipSuccess;
+    explicit Copies(vlgp_ctx* c) : ctx(c) {}
+    void in(void* dev, const void* host, size_t bytes) {
+        if (e == hipSuccess) e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
+    void out(void* host, const void* dev, size_t bytes) {  // (an output the caller did not ask for is skipped)
+        if (host && e == hipSuccess) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    // `rows` rows of `width` doubles, `dpitch` and `spitch` doubles apart
+    void in2d(double* dev, size_t dpitch, const double* host, size_t spitch, size_t width, size_t rows) {
+        if (e == hipSuccess) e = hipMemcpy2DAsync(dev, dpitch * 8, host, spitch * 8, width * 8, rows, hipMemcpyHostToDevice, ctx->stream);
+    }
+    void out2d(double* host, size_t dpitch, const double* dev, size_t spitch, size_t width, size_t rows) {
+        if (host && e == hipSuccess)
+            e = hipMemcpy2DAsync(host, dpitch * 8, dev, spitch * 8, width * 8, rows, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    void nan_fill(double* dev, int64_t n) {  // NaN: every byte 0xff
+        if (n > 0 && e == hipSuccess) e = hipMemsetAsync(dev, 0xff, sizeof(double) * (size_t)n, ctx->stream);
+    }
+    // "<who> <what> failed: ..." if a copy did; finish() synchronises first
+    int status(const char* who, const char* what) {
+        return e == hipSuccess ? VLGP_OK : vlgp_fail(ctx, VLGP_ERR_HIP, "%s %s failed: %s", who, what, hipGetErrorString(e));
+    }
+    int finish(const char* who, const char* what) {
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        return status(who, what);
+    }
+};
+#endif

@@ -336,6 +336,23 @@ int vlgp_bind_priors(vlgp_ctx* ctx, UnitSet& us);             // (re)build d_uni
 int vlgp_refresh_xb(vlgp_ctx* ctx, UnitSet& us);              // xb = x.b when x is general
 UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid);
 
+// How a set-taking entry point opens (api.hip): what it waits for and invalidates, in this order, then the set and its
+// admission -- which kinds of set the entry point takes and what it says to the others (SET_ADMISSION, api.hip).
+enum : unsigned {
+    OPEN_COLLECT = 1,   // host-side ranks of a lazy prior build (vlgp_prior_collect)
+    OPEN_STALE = 2,     // unit state changes: the cached H-step moments are stale
+    OPEN_JOIN = 4,      // vlgp_join_m: the M-step lane and a queued norms pass, write_epoch bumped
+    OPEN_WAIT = 8,      // the same two waits without the bump: the call only reads (what vlgp_hstep_prepare built stays)
+    OPEN_PARAMS = 16,   // parameters must be set
+    OPEN_DEVICE = 32,   // hipSetDevice
+    OPEN_EMPTY = 64,    // the slot may be empty (upload, free)
+};
+struct Admission { const char* what; unsigned kinds; const char* refusal; };
+int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a);  // (a null: admit() is the caller's)
+int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a);
+extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
+    admit_vlgp_joint_laplace;  // the scoring entry points' rows of the table (eval_api.hip)
+
 // profiling brackets (HIP events on ctx->stream)
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st = nullptr);
 void vlgp_prof_end(vlgp_ctx* ctx, int kind, double units = 0.0, hipStream_t st = nullptr);

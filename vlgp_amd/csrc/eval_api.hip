@@ -1,0 +1,287 @@
+// The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_elbo, vlgp_forecast,
+// vlgp_marginal, vlgp_joint_laplace.  Every one is put together the same way: open the set, check the
+// arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
+#include <algorithm>
+
+#include "call_block.h"
+
+// ---- what the row scores (loglik, predictive) do once their own arguments are sound -----------------------------------
+// admission, no per-entry output from overlapping masks, xb of the rows' owner; then the shapes of vlgp_loglik
+struct RowScore { bool by_row; LoglikShape S; int64_t n_blk; };
+static int open_row_score(vlgp_ctx* ctx, int set, UnitSet* us, const Admission& a, bool per_entry, const char* outputs,
+                          RowScore* r) {
+    CHK(admit(ctx, set, us, a));
+    r->by_row = us->is(SET_BY_ROW);  // per-entry outputs of such a set: NaN where no replica holds the entry out
+    if (r->by_row && per_entry && us->rep.overlap)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: the masks of set %d overlap (an entry is held out by more than one "
+                         "replica): no %s, sums only", a.what, set, outputs);
+    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
+    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
+    r->S = vlgp_loglik_shape(ctx, *us);
+    r->n_blk = (rows_of.rows + 255) / 256;
+    return VLGP_OK;
+}
+
+extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double* sums) {
+    UnitSet* us = nullptr;
+    // OPEN_JOIN and its epoch bump, not the OPEN_WAIT of a read-only call: launch_loglik's partials live in ctx->d_work,
+    // which a prepared H-step may own
+    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
+    if (!sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_loglik needs sums");
+    RowScore r;
+    CHK(open_row_score(ctx, set, us, admit_vlgp_loglik, rate != nullptr, "rate", &r));
+    const LoglikLayout o = loglik_layout(r.S.slots, r.S.n_rate, rate != nullptr);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    Copies cp(ctx);
+    if (r.by_row && rate) cp.nan_fill(blk.at(o.rate), r.S.n_rate);
+    CHK(cp.status("vlgp_loglik:", "filling the rates"));
+    CHK(launch_loglik(ctx, *us, vb, blk.opt(rate, o.rate), blk.at(o.sums)));
+    cp.out(sums, blk.at(o.sums), sizeof(double) * 4 * (size_t)r.S.slots);
+    cp.out(rate, blk.at(o.rate), sizeof(double) * (size_t)r.S.n_rate);
+    return cp.finish("vlgp_loglik", "copy-out");
+}
+
+// vlgp_loglik's shapes with a second per-entry output; the waits of a read-only call (no epoch bump): the partials are in
+// the call's own block
+extern "C" int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa,
+                               double* rate, double* lpd, double* sums) {
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
+    if (n_nodes < 1 || n_nodes > 64)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: n_nodes = %d, need 1 <= n_nodes <= 64", n_nodes);
+    if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive needs z, lwa and sums");
+    RowScore r;
+    CHK(open_row_score(ctx, set, us, admit_vlgp_predictive, rate || lpd, "rate or lpd", &r));
+    if (r.S.slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: too many (replica, channel) slots");
+    const PredictiveLayout o = predictive_layout(r.S.slots, r.S.n_rate, r.n_blk, rate != nullptr, lpd != nullptr);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    Copies cp(ctx);
+    cp.in(blk.at(o.nodes), z, sizeof(double) * (size_t)n_nodes);
+    cp.in(blk.at(o.nodes) + n_nodes, lwa, sizeof(double) * (size_t)n_nodes);
+    if (r.by_row) cp.nan_fill(blk.at(o.rate), o.sums - o.rate);  // (rate and lpd lie side by side)
+    CHK(cp.status("vlgp_predictive", "copy-in"));
+    CHK(launch_predictive(ctx, *us, vb, n_nodes, blk.at(o.nodes), blk.opt(rate, o.rate), blk.opt(lpd, o.lpd), blk.at(o.part),
+                          blk.at(o.sums)));
+    cp.out(sums, blk.at(o.sums), sizeof(double) * 4 * (size_t)r.S.slots);
+    cp.out(rate, blk.at(o.rate), sizeof(double) * (size_t)r.S.n_rate);
+    cp.out(lpd, blk.at(o.lpd), sizeof(double) * (size_t)r.S.n_rate);
+    return cp.finish("vlgp_predictive", "copy-out");
+}
+
+// ---- the scores of a posterior (elbo, forecast, marginal, joint Laplace) --------------------------------------------------
+// What they do first: a plain set with parameters, xb and its priors bound, nothing pending.  The waits of vlgp_join_m
+// without its epoch bump: the calls only read, so what vlgp_hstep_prepare built stays valid.  Then the number of (unit,
+// latent) tasks, an int for the launches, and rp, the largest effective rank among the set's lengths: it sizes the LDS of
+// the (unit, latent) kernels.  *n_failed starts at 0.
+struct Posterior { UnitSet* us = nullptr; int64_t tasks = 0; int rp = 1; };
+static int open_posterior(vlgp_ctx* ctx, int set, const Admission& a, int* n_failed, Posterior* p) {
+    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &p->us, &a));
+    const UnitSet& us = *p->us;
+    if (!us.x_ones) CHK(vlgp_refresh_xb(ctx, *p->us));
+    CHK(vlgp_bind_priors(ctx, *p->us));
+    p->tasks = (int64_t)us.M * ctx->L;
+    if (p->tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (unit, latent) pairs", a.what);
+    int T_seen = -1;
+    for (int m = 0; m < us.M; ++m) {
+        const int T = (int)(us.off[m + 1] - us.off[m]);
+        if (T == T_seen) continue;
+        T_seen = T;
+        const Prior& pr = ctx->priors.find(T)->second;  // (vlgp_bind_priors found every length)
+        for (int l = 0; l < ctx->L; ++l) p->rp = std::max(p->rp, pr.rl[l]);
+    }
+    if (n_failed) *n_failed = 0;
+    return VLGP_OK;
+}
+
+// the flags of the (unit, latent) tasks, the last of a call's copies out: *n_failed = how many are set
+static int count_flags(Copies& cp, const char* who, const int* d_flag, int64_t tasks, int* n_failed) {
+    std::vector<int> flag((size_t)tasks);
+    cp.out(flag.data(), d_flag, sizeof(int) * (size_t)tasks);
+    CHK(cp.finish(who, "copy-out"));
+    if (n_failed) *n_failed = (int)(tasks - std::count(flag.begin(), flag.end(), 0));
+    return VLGP_OK;
+}
+
+extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, double* row_ell, double* kl_terms,
+                         int* n_failed) {
+    Posterior p;
+    CHK(open_posterior(ctx, set, admit_vlgp_elbo, n_failed, &p));
+    if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
+    const int64_t rows = p.us->rows;
+    const ElboLayout o = elbo_layout(rows, ctx->N, p.tasks, (rows + 255) / 256, row_ell != nullptr);
+    if (o.need > ctx->elbo_len) {  // the block is the context's and only grows: a fit under track_elbo calls once per iteration
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->d_elbo) HIPCHK(ctx, hipFree(ctx->d_elbo));
+        ctx->d_elbo = nullptr;
+        ctx->elbo_len = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->d_elbo, sizeof(double) * (size_t)(o.need + o.need / 4)));
+        ctx->elbo_len = o.need + o.need / 4;
+    }
+    double* d = ctx->d_elbo;
+    int* d_flag = reinterpret_cast<int*>(d + o.flag);
+    CHK(launch_elbo(ctx, *p.us, vb, p.rp, d + o.part, d + o.sums, row_ell ? d + o.rows : nullptr, d + o.terms, d_flag));
+    Copies cp(ctx);
+    cp.out(row_sums, d + o.sums, sizeof(double) * 4 * (size_t)ctx->N);
+    cp.out(kl_terms, d + o.terms, sizeof(double) * 4 * (size_t)p.tasks);
+    cp.out(row_ell, d + o.rows, sizeof(double) * (size_t)rows);
+    return count_flags(cp, "vlgp_elbo", d_flag, p.tasks, n_failed);
+}
+
+extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,
+                             const double* G_ext, double* mu_ext, double* v_ext, double* fit_terms, int* n_failed) {
+    Posterior p;
+    CHK(open_posterior(ctx, set, admit_vlgp_forecast, n_failed, &p));
+    UnitSet* us = p.us;
+    if (us->is(SET_TILING | SET_COPIED)) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_forecast refuses a cut set (set %d is cut from set %d)", set, us->parent);
+    if (n_lengths < 1 || !lengths || !n_ext || !G_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs lengths, n_ext and G_ext");
+    if (!mu_ext || !v_ext) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast needs mu_ext and v_ext");
+    const int L = ctx->L, R = ctx->R, M = us->M;
+    std::vector<int64_t> blk_off((size_t)n_lengths + 1, 0);  // offsets of the (L, n_ext[k], R) blocks inside G_ext
+    for (int k = 0; k < n_lengths; ++k) {
+        if (k > 0 && lengths[k] <= lengths[k - 1])
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: lengths must be strictly increasing (lengths[%d] = %d)", k, lengths[k]);
+        if (n_ext[k] < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: n_ext[%d] = %d for length %d, need >= 1", k, n_ext[k], lengths[k]);
+        blk_off[(size_t)k + 1] = blk_off[(size_t)k] + (int64_t)L * n_ext[k] * R;
+    }
+    std::vector<int64_t> tab((size_t)2 * M + 1);  // ext_off (M + 1) | gx_off (M)
+    int64_t* ext_off = tab.data();
+    int64_t* gx_off = ext_off + M + 1;
+    ext_off[0] = 0;
+    for (int m = 0; m < M; ++m) {
+        const int T = (int)(us->off[m + 1] - us->off[m]);
+        const int* at = std::lower_bound(lengths, lengths + n_lengths, T);
+        if (at == lengths + n_lengths || *at != T)
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_forecast: unit %d has length %d, which is not listed", m, T);
+        ext_off[m + 1] = ext_off[m] + n_ext[at - lengths];
+        gx_off[m] = blk_off[(size_t)(at - lengths)];
+    }
+    const int64_t g_len = blk_off[(size_t)n_lengths], n_out = ext_off[M] * L;
+    const ForecastLayout o = forecast_layout(us->rows, L, M, g_len, n_out);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    int64_t* d_tab = blk.i64(o.tab);
+    Copies cp(ctx);
+    cp.in(blk.at(o.g), G_ext, sizeof(double) * (size_t)g_len);
+    cp.in(d_tab, tab.data(), sizeof(int64_t) * tab.size());
+    CHK(cp.status("vlgp_forecast", "copy-in"));
+    CHK(launch_forecast(ctx, *us, vb, p.rp, blk.at(o.z), d_tab, d_tab + M + 1, blk.at(o.g), blk.at(o.mu), blk.at(o.v),
+                        blk.at(o.terms), blk.ints(o.flag)));
+    cp.out(mu_ext, blk.at(o.mu), sizeof(double) * (size_t)n_out);
+    cp.out(v_ext, blk.at(o.v), sizeof(double) * (size_t)n_out);
+    cp.out(fit_terms, blk.at(o.terms), sizeof(double) * 2 * (size_t)p.tasks);
+    return count_flags(cp, "vlgp_forecast", blk.ints(o.flag), p.tasks, n_failed);
+}
+
+// ---- the sample stage of vlgp_marginal and vlgp_joint_laplace ----------------------------------------------------------
+// first row tile of each unit (M + 1), built once per call
+static std::vector<int64_t> tile_table(const UnitSet& us, int tile_rows) {
+    std::vector<int64_t> tile_off((size_t)us.M + 1, 0);
+    for (int m = 0; m < us.M; ++m)
+        tile_off[(size_t)m + 1] = tile_off[(size_t)m] + (us.off[m + 1] - us.off[m] + tile_rows - 1) / tile_rows;
+    return tile_off;
+}
+
+// K draws, 64 at a time: the chunk of eps (tasks R, K) in, sample contiguous on the device with stride 64; step(kc), the
+// caller's launches that turn it into log_w (M, 64) and parts (M, 64, 2); these out into log_w (M, K) and, when wanted,
+// parts (M, K, 2).  The copies of a chunk and its kernels are stream-ordered.
+template <class Step>
+static int sample_stage(Copies& cp, const char* who, const CallBlock& blk, const SampleLayout& s, int64_t tasks_R, int M,
+                        int64_t K, const double* eps, double* log_w, double* parts, Step step) {
+    for (int64_t k0 = 0; k0 < K; k0 += 64) {
+        const int kc = (int)std::min<int64_t>(64, K - k0);
+        cp.in2d(blk.at(s.eps), 64, eps + k0, (size_t)K, (size_t)kc, (size_t)tasks_R);
+        CHK(cp.status(who, "copy-in"));
+        CHK(step(kc));
+        cp.out2d(log_w + k0, (size_t)K, blk.at(s.lw), 64, (size_t)kc, (size_t)M);
+        cp.out2d(parts ? parts + 2 * k0 : nullptr, (size_t)K * 2, blk.at(s.parts), 128, (size_t)kc * 2, (size_t)M);
+        CHK(cp.finish(who, "copy-out"));
+    }
+    return VLGP_OK;
+}
+
+extern "C" int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* eps, double* log_w,
+                             double* parts, int* n_failed) {
+    static const char* who = "vlgp_marginal";
+    Posterior p;
+    CHK(open_posterior(ctx, set, admit_vlgp_marginal, n_failed, &p));
+    if (n_samples < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal: n_samples = %d, need >= 1", n_samples);
+    if (!eps || !log_w) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_marginal needs eps and log_w");
+    UnitSet* us = p.us;
+    const int L = ctx->L, R = ctx->R, M = us->M, tile_rows = marginal_tile_rows(L);
+    const std::vector<int64_t> tile_off = tile_table(*us, tile_rows);
+    const int64_t n_tiles = tile_off[(size_t)M];
+    const MarginalLayout o = marginal_layout(us->rows, L, R, M, n_tiles);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    int64_t* d_tab = blk.i64(o.s.tab);
+    Copies cp(ctx);
+    cp.in(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size());
+    CHK(cp.status(who, "copy-in"));
+    CHK(launch_forecast_z(ctx, *us, vb, blk.at(o.z)));
+    CHK(sample_stage(cp, who, blk, o.s, p.tasks * R, M, n_samples, eps, log_w, parts, [&](int kc) {
+        return launch_marginal(ctx, *us, p.rp, kc, blk.at(o.z), blk.at(o.s.eps), blk.at(o.s.beta), blk.at(o.s.c),
+                               blk.at(o.s.part), tile_rows, d_tab, n_tiles, blk.at(o.s.lw), blk.at(o.s.parts), blk.ints(o.flag));
+    }));
+    return count_flags(cp, who, blk.ints(o.flag), p.tasks, n_failed);
+}
+
+extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_samples, const double* eps,
+                                  double* beta, double* stats, double* mu, double* v, double* log_w, double* parts,
+                                  int* n_failed) {
+    static const char* who = "vlgp_joint_laplace";
+    Posterior p;
+    CHK(open_posterior(ctx, set, admit_vlgp_joint_laplace, n_failed, &p));
+    if (max_iter < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: max_iter = %d, need >= 1", max_iter);
+    if (!(tol > 0.0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: tol = %g, need > 0", tol);
+    if (n_samples < 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples = %d, need >= 0", n_samples);
+    if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace needs stats");
+    if (n_samples > 0 && (!eps || !log_w)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples > 0 needs eps and log_w");
+    UnitSet* us = p.us;
+    const int L = ctx->L, R = ctx->R, M = us->M, tile_rows = marginal_tile_rows(L);
+    const int64_t K = n_samples, rows = us->rows;
+    int Dmax = 1;
+    for (int m = 0; m < M; ++m) {  // D = sum_l r_l of the unit's length
+        const Prior& pr = ctx->priors.find((int)(us->off[m + 1] - us->off[m]))->second;  // (vlgp_bind_priors found every length)
+        int D = 0;
+        for (int l = 0; l < L; ++l) D += pr.rl[l];
+        if (D > 512)
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_joint_laplace: unit %d has D = %d weights, at most 512 are supported", m, D);
+        Dmax = std::max(Dmax, D);
+    }
+    const std::vector<int64_t> tile_off = tile_table(*us, tile_rows);
+    const int64_t n_tiles = tile_off[(size_t)M];
+    const JointLayout o = joint_layout(joint_work_doubles(ctx, *us, Dmax, nullptr), rows, L, R, M, n_tiles, K);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    JointWork W;
+    W.base = blk.at(o.work);
+    (void)joint_work_doubles(ctx, *us, Dmax, &W);
+    int64_t* d_tab = blk.i64(o.s.tab);
+    Copies cp(ctx);
+    CHK(launch_joint_init(ctx, *us, p.rp, W));
+    // every round finishes a unit, factors it (at most max_iter times) or halves its step (at most 30 times per factor)
+    for (int64_t round = 0, done = 0; done < M && round <= 32 * ((int64_t)max_iter + 1); ++round) {
+        CHK(launch_joint_round(ctx, *us, W, max_iter, tol));
+        int nd = 0;
+        cp.out(&nd, W.n_done, sizeof(int));
+        CHK(cp.finish("vlgp_joint_laplace:", "a Newton round"));
+        done = nd;
+    }
+    const bool path = mu || v;
+    CHK(launch_joint_finish(ctx, *us, p.rp, W, blk.at(o.stats), path ? W.g : nullptr, blk.opt(path, o.v)));
+    cp.out(stats, blk.at(o.stats), sizeof(double) * 8 * (size_t)M);
+    cp.out(beta, W.beta, sizeof(double) * (size_t)(p.tasks * R));
+    cp.out(mu, W.g, sizeof(double) * (size_t)(rows * L));
+    cp.out(v, blk.at(o.v), sizeof(double) * (size_t)(rows * L));
+    if (K) cp.in(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size());
+    CHK(cp.finish(who, "copy-out"));
+    if (n_failed)
+        for (int m = 0; m < M; ++m) *n_failed += stats[8 * (size_t)m] != stats[8 * (size_t)m] ? 1 : 0;  // (NaN: the unit failed)
+    return sample_stage(cp, who, blk, o.s, p.tasks * R, M, K, eps, log_w, parts, [&](int kc) {
+        CHK(launch_joint_draw(ctx, *us, W, kc, blk.at(o.s.eps), blk.at(o.s.beta), blk.at(o.s.c)));
+        return launch_marginal_rows(ctx, *us, who, kc, blk.at(o.s.beta), blk.at(o.s.c), blk.at(o.s.part), tile_rows, d_tab,
+                                    n_tiles, blk.at(o.s.lw), blk.at(o.s.parts));
+    });
+}

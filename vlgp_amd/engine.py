@@ -268,22 +268,31 @@ class Engine:
         self.sets[dst] = (k * m, k * rows, roff)
         self.replicas[dst] = Replicas(k, ch, held_out is not None)
 
+    def _score_shapes(self, set_id):
+        """``(sums, per-entry)`` shapes of a row score (``loglik``, ``predictive``) of a plain, replicated or masked set."""
+        _, rows, _ = self.sets[set_id]
+        rep = self.replicas.get(set_id)
+        if rep is None:
+            return (self.N, 4), (rows, self.N)
+        if rep.by_entry:
+            return (rep.n, self.N, 4), (rows // max(rep.n, 1), self.N)
+        return (len(rep.channels), 4), (rows // max(rep.n, 1), len(rep.channels))
+
+    def _check_eps(self, set_id, eps):
+        """The normals of ``marginal`` and ``joint_laplace`` as float64, (units, L, R, n_samples >= 1), and n_samples."""
+        units, eps = self.sets[set_id][0], _f64(eps)
+        if eps.ndim != 4 or eps.shape[:3] != (units, self.L, self.R) or eps.shape[3] < 1:
+            raise ValueError("eps must be (%d, %d, %d, n_samples >= 1), got %r" % (units, self.L, self.R, eps.shape))
+        return eps, eps.shape[3]
+
     def loglik(self, set_id, vb=True, want_rate=False):
         """Plug-in rates and per-channel log-likelihood sums of a set (vlgp_loglik): ``(sums, rate)``, sums
         (slots, 4) and rate (rows, slots) or None; slots = N for a plain set, the (replica, left-out channel) pairs in
         the order of the channel list for a replicated one (rows: the source set's).  A set replicated with
         ``held_out``: sums (n_rep, N, 4) over the entries each replica holds out, rate (rows of the source, N), NaN
         where no replica holds the entry out."""
-        _, rows, _ = self.sets[set_id]
-        rep = self.replicas.get(set_id)
-        rows_out = rows if rep is None else rows // max(rep.n, 1)
-        if rep is not None and rep.by_entry:
-            sums = np.empty((rep.n, self.N, 4))
-            rate = np.empty((rows_out, self.N)) if want_rate else None
-        else:
-            slots = self.N if rep is None else len(rep.channels)
-            sums = np.empty((slots, 4))
-            rate = np.empty((rows_out, slots)) if want_rate else None
+        sums, entry = self._score_shapes(set_id)
+        sums, rate = np.empty(sums), np.empty(entry) if want_rate else None
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
         return sums, rate
 
@@ -293,16 +302,8 @@ class Engine:
         ``lpd`` have the shape of ``loglik``'s rate, or are None.  ``n_nodes``: points of the mode-centred Gauss-Hermite
         rule of the Poisson channels (``hermite_nodes``).  Changes no state."""
         z, lwa = hermite_nodes(n_nodes)
-        _, rows, _ = self.sets[set_id]
-        rep = self.replicas.get(set_id)
-        rows_out = rows if rep is None else rows // max(rep.n, 1)
-        if rep is not None and rep.by_entry:
-            sums, slots = np.empty((rep.n, self.N, 4)), self.N
-        else:
-            slots = self.N if rep is None else len(rep.channels)
-            sums = np.empty((slots, 4))
-        rate = np.empty((rows_out, slots)) if want_rate else None
-        lpd = np.empty((rows_out, slots)) if want_lpd else None
+        sums, entry = self._score_shapes(set_id)
+        sums, rate, lpd = np.empty(sums), np.empty(entry) if want_rate else None, np.empty(entry) if want_lpd else None
         self._ck(self.lib.vlgp_predictive(self.h, int(set_id), int(bool(vb)), len(z), dptr(z), dptr(lwa), dptr(rate),
                                           dptr(lpd), dptr(sums)))
         return sums, rate, lpd
@@ -353,10 +354,7 @@ class Engine:
         with ``want_parts`` (units, n_samples, 2) = the log-likelihood of the draw and the prior-over-proposal term, which
         add to log_w (else None).  Changes no state."""
         units, _, _ = self.sets[set_id]
-        eps = _f64(eps)
-        if eps.ndim != 4 or eps.shape[:3] != (units, self.L, self.R) or eps.shape[3] < 1:
-            raise ValueError("eps must be (%d, %d, %d, n_samples >= 1), got %r" % (units, self.L, self.R, eps.shape))
-        K = eps.shape[3]
+        eps, K = self._check_eps(set_id, eps)
         log_w = np.empty((units, K))
         parts = np.empty((units, K, 2)) if want_parts else None
         n = C.c_int(0)
@@ -376,10 +374,7 @@ class Engine:
         units, rows, _ = self.sets[set_id]
         K, log_w, parts = 0, None, None
         if eps is not None:
-            eps = _f64(eps)
-            if eps.ndim != 4 or eps.shape[:3] != (units, self.L, self.R) or eps.shape[3] < 1:
-                raise ValueError("eps must be (%d, %d, %d, n_samples >= 1), got %r" % (units, self.L, self.R, eps.shape))
-            K = eps.shape[3]
+            eps, K = self._check_eps(set_id, eps)
             log_w, parts = np.empty((units, K)), np.empty((units, K, 2))
         beta = np.empty((units, self.L, self.R))
         stats = np.empty((units, 8))

@@ -729,6 +729,32 @@ def weights_summary(log_w):
     return np.where(bad, np.nan, iwae), np.where(bad, np.nan, np.mean(log_w, axis=-1)), np.where(bad, np.nan, ess)
 
 
+@contextlib.contextmanager
+def _posterior(trials, params, config, infer, n_iter, device):
+    """``(eng, n_failed)``: a ``_resident`` engine whose ``SET_TEST`` holds the trials' posterior -- with ``infer`` from a
+    zero start and ``n_iter`` E-step iterations (default ``config["max_iter"]``; ``n_failed`` its failed updates), else the
+    trials' stored ``mu, v, w`` (``n_failed = 0``)."""
+    L = int(params["zdim"])
+    if infer:
+        units = _zero_start(trials, L)
+    else:
+        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
+                  **{k: tr[k] if tr.get(k) is not None else np.zeros((tr["y"].shape[0], L)) for k in ("v", "w")}}
+                 for tr in trials]
+    n_iter = int(config["max_iter"] if n_iter is None else n_iter)
+    with _resident(trials, params, units, device) as eng:
+        yield eng, eng.estep(SET_TEST, n_iter, config["dmu_bound"], config["method"] == "VB") if infer else 0
+
+
+def _evidence_bps(total, sums, rows, gauss):
+    """``(total - LL_null) / (n_spikes ln 2)`` of an evidence ``total`` over ``rows`` rows, ``LL_null`` the constant-rate
+    null of ``bits_per_spike`` from ``vlgp_loglik``'s ``sums``; NaN unless every channel is Poisson and there is a spike."""
+    _, ll_null, ny, _ = bits_per_spike(sums, rows, gauss)
+    if gauss.any() or not np.sum(ny) > 0:
+        return float("nan")
+    return float((total - np.sum(ll_null)) / (np.sum(ny) * math.log(2.0)))
+
+
 def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infer=True, n_iter=None, device=0,
                     proposal="posterior", max_iter=50, tol=1e-10):
     """Importance-weighted estimate of the marginal log-likelihood ``log p(y_trial)`` of every trial, the fitted
@@ -763,17 +789,8 @@ def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infe
     vb = config["method"] == "VB"
     rng = np.random.default_rng(seed) if rng is None else rng
     lengths = [int(tr["y"].shape[0]) for tr in trials]
-    if infer:
-        units = _zero_start(trials, L)
-    else:
-        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
-                  **{k: tr[k] if tr.get(k) is not None else np.zeros((T, L)) for k in ("v", "w")}}
-                 for tr, T in zip(trials, lengths)]
     log_w = np.empty((len(trials), K))
-    with _resident(trials, params, units, device) as eng:
-        n_failed = 0
-        if infer:
-            n_failed = eng.estep(SET_TEST, int(config["max_iter"] if n_iter is None else n_iter), config["dmu_bound"], vb)
+    with _posterior(trials, params, config, infer, n_iter, device) as (eng, n_failed):
         chunks = []
         for k0 in range(0, K, SAMPLE_CHUNK):
             kc = min(SAMPLE_CHUNK, K - k0)
@@ -790,13 +807,9 @@ def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infe
         gauss = eng.gauss.copy()
     iwae, elbo_mc, ess = weights_summary(log_w)
     total = float(np.sum(iwae))
-    _, ll_null, ny, _ = bits_per_spike(sums, sum(lengths), gauss)
-    if gauss.any() or not np.sum(ny) > 0:
-        bps = float("nan")
-    else:
-        bps = float((total - np.sum(ll_null)) / (np.sum(ny) * math.log(2.0)))
     out = {"log_w": log_w, "iwae": iwae, "elbo_mc": elbo_mc, "ess": ess, "total": total, "elbo": bound,
-           "gap": total - bound, "marginal_bps": bps, "n_failed": int(n_failed) + int(bad)}
+           "gap": total - bound, "marginal_bps": _evidence_bps(total, sums, sum(lengths), gauss),
+           "n_failed": int(n_failed) + int(bad)}
     if proposal == "joint":
         out.update(laplace=joint["laplace"], converged=joint["converged"])
     return out
@@ -818,28 +831,14 @@ def joint_posterior(trials, params, config, infer=True, n_iter=None, max_iter=50
     ``marginal_loglik``'s null model, NaN unless every channel is Poisson; ``n_failed`` (failed E-step updates plus trials
     whose ``H`` could not be factored: their numbers are NaN, and so is ``total``)."""
     _no_missing(trials, "joint_posterior")
-    L = int(params["zdim"])
     vb = config["method"] == "VB"
     lengths = [int(tr["y"].shape[0]) for tr in trials]
-    if infer:
-        units = _zero_start(trials, L)
-    else:
-        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"],
-                  **{k: tr[k] if tr.get(k) is not None else np.zeros((T, L)) for k in ("v", "w")}}
-                 for tr, T in zip(trials, lengths)]
-    with _resident(trials, params, units, device) as eng:
-        n_failed = 0
-        if infer:
-            n_failed = eng.estep(SET_TEST, int(config["max_iter"] if n_iter is None else n_iter), config["dmu_bound"], vb)
+    with _posterior(trials, params, config, infer, n_iter, device) as (eng, n_failed):
         joint = eng.joint_laplace(SET_TEST, max_iter=max_iter, tol=tol)
         sums, _ = eng.loglik(SET_TEST, vb=vb)
         gauss = eng.gauss.copy()
     total = float(np.sum(joint["laplace"]))
-    _, ll_null, ny, _ = bits_per_spike(sums, sum(lengths), gauss)
-    if gauss.any() or not np.sum(ny) > 0:
-        bps = float("nan")
-    else:
-        bps = float((total - np.sum(ll_null)) / (np.sum(ny) * math.log(2.0)))
     return {"mu": _per_trial(joint["mu"], lengths), "v": _per_trial(joint["v"], lengths), "laplace": joint["laplace"],
-            "converged": joint["converged"], "n_newton": joint["n_newton"], "total": total, "laplace_bps": bps,
+            "converged": joint["converged"], "n_newton": joint["n_newton"], "total": total,
+            "laplace_bps": _evidence_bps(total, sums, sum(lengths), gauss),
             "n_failed": int(n_failed) + int(joint["n_failed"])}
