@@ -286,6 +286,34 @@ int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_s
  * only; fixed-order sums, no atomics: the same bits on every run. */
 int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, double* rate,
                     double* lpd, double* sums);
+/* Calibration of the predictive distribution of vlgp_predictive: is the distribution the model reports the one the counts
+ * follow?  Per entry, with m, s2 and rate as vlgp_predictive has them:
+ *   Poisson   k = y;  p(j) = exp(lpd of the count j), exactly vlgp_predictive's value for y = j (the mode-centred n_nodes-point
+ *             rule, or the plug-in Poisson mass when s2 < 1e-30);  lo = F(k - 1) = sum_{j < k} p(j), added in the order
+ *             j = 0, 1, ... (0 at k = 0);  hi = lo + p(k);  then both are clipped to <= 1.
+ *             mean = rate = trunc_exp(m + s2 / 2),  var = mean + mean^2 expm1(s2): the clamp of trunc_exp enters var only
+ *             through mean.
+ *             An entry with y negative, not an integer, not finite or > max_count is skipped: it adds 1 to `skipped` and
+ *             nothing else, its cdf is NaN.  The device's loop over counts is bounded by max_count whatever memory holds.
+ *   Gaussian  lo = hi = erfc(-(y - m) / sqrt(2 (noise_n + s2))) / 2;  mean = m,  var = noise_n + s2.
+ * Per slot of vlgp_loglik (the same slots for every kind of set) sums holds W = n_bins + n_levels + 3 columns,
+ *   pit_0 ... pit_{n_bins - 1} | covered_0 ... covered_{n_levels - 1} | pearson | entries | skipped:
+ *   pit      the non-randomised PIT histogram (Czado, Gneiting & Held 2009) with edges e_j = j / n_bins: an entry with
+ *            hi > lo adds clip((e_{j+1} - lo) / (hi - lo), 0, 1) - clip((e_j - lo) / (hi - lo), 0, 1) to bin j, one with
+ *            hi == lo adds 1 to bin min(n_bins - 1, floor(lo n_bins)); every entry adds total mass 1.
+ *   covered  entries inside the central interval of level c = levels[i]: hi >= a and lo < 1 - a, a = (1 - c) / 2; for counts
+ *            exactly q_a <= y <= q_{1-a} with q_p = min{k : F(k) >= p}.
+ *   pearson  sum (y - mean)^2 / var;  entries, skipped: counts.
+ * cdf (entries, 2) = lo | hi in the per-entry layout of vlgp_predictive's rate, or NULL; on a set made by
+ * vlgp_replicate_masked NaN where no replica holds the entry out, and asking for it when two replicas hold the same entry
+ * out is VLGP_ERR_ARG (the sums alone are fine).  z, lwa: the node tables of vlgp_predictive.  Limits: 1 <= n_nodes <= 64,
+ * 1 <= n_bins <= 32, 0 <= n_levels <= 4 with every level in (0, 1), 1 <= max_count <= 65536; outside them, or with a null
+ * z, lwa or sums: VLGP_ERR_ARG, the message naming the argument, nothing changed.  The cost of an entry is 1 + y masses.
+ * Takes the sets vlgp_loglik takes.  Waits for a pending M-step and norms pass; changes no unit state, no
+ * parameter and nothing vlgp_hstep_prepare built.  This handle's units only; fixed-order sums, no atomics: the same bits on
+ * every run. */
+int vlgp_calibration(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, int n_bins,
+                     int n_levels, const double* levels, int max_count, double* cdf, double* sums);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

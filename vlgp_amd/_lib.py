@@ -124,6 +124,7 @@ _SIGNATURES = {
     "vlgp_forecast": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
     "vlgp_marginal": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
     "vlgp_predictive": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "vlgp_calibration": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "vlgp_joint_laplace": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
 }
 EXPORTS = tuple(_SIGNATURES)

@@ -127,6 +127,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_upload_units, SET_ANY & ~SET_SOURCE, nullptr)                                                              \
     X(vlgp_loglik, SET_ANY & ~SET_COPIED, "vlgp_loglik on a copied cut: merge it and score the source set")           \
     X(vlgp_predictive, SET_ANY & ~SET_COPIED, "vlgp_predictive on a copied cut: merge it and score the source set")   \
+    X(vlgp_calibration, SET_ANY & ~SET_COPIED, "vlgp_calibration on a copied cut: merge it and score the source set") \
     X(vlgp_update_w, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_update_v, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_mstep_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \

@@ -14,7 +14,7 @@ struct BlockLayout {
     int64_t need() const { return at; }
 };
 
-// ---- the blocks of the six calls: integers in, named offsets and `need` out; the regions in the order of the block -------
+// ---- the blocks of the seven calls: integers in, named offsets and `need` out; the regions in the order of the block -------
 // (a braced list is evaluated left to right: the initialisers below ARE the order of the regions)
 // rate (n_rate, when wanted) | sums (slots, 4); the partials live in vlgp_ctx::d_work
 struct LoglikLayout { int64_t rate, sums, need; };
@@ -29,6 +29,17 @@ inline PredictiveLayout predictive_layout(int64_t slots, int64_t n_rate, int64_t
     BlockLayout b;
     return {b.doubles(128), b.doubles(want_rate ? n_rate : 0), b.doubles(want_lpd ? n_rate : 0), b.doubles(4 * slots),
             b.doubles(slots * n_blk * 4), b.need()};
+}
+
+// nodes (z | lwa, 2 x 64) | levels (4) | cdf (n_rate, 2: lo | hi, when wanted) | sums (slots, 4 G) | partials (slots, G,
+// n_blk, 4), G = ceil(W / 4) groups of four for the W = n_bins + n_levels + 3 columns of a slot
+struct CalibrationLayout { int64_t nodes, levels, cdf, sums, part, groups, need; };
+inline CalibrationLayout calibration_layout(int64_t slots, int64_t n_rate, int64_t n_blk, int64_t n_bins, int64_t n_levels,
+                                            bool want_cdf) {
+    BlockLayout b;
+    const int64_t G = (n_bins + n_levels + 3 + 3) / 4;
+    return {b.doubles(128), b.doubles(4), b.doubles(want_cdf ? 2 * n_rate : 0), b.doubles(4 * G * slots),
+            b.doubles(slots * G * n_blk * 4), G, b.need()};
 }
 
 // partials (N, n_blk, 4) | sums (N, 4) | terms (tasks, 4) | row_ell (rows, when wanted) | flags (tasks)

@@ -350,7 +350,7 @@ enum : unsigned {
 struct Admission { const char* what; unsigned kinds; const char* refusal; };
 int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a);  // (a null: admit() is the caller's)
 int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a);
-extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
+extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_calibration, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
     admit_vlgp_joint_laplace;  // the scoring entry points' rows of the table (eval_api.hip)
 
 // profiling brackets (HIP events on ctx->stream)
@@ -413,6 +413,11 @@ int launch_sums_finish(vlgp_ctx* ctx, int slots, int n_blk, const double* d_part
 // d_part: (slots, ceil(source rows / 256), 4) doubles of the caller's workspace; d_sums (slots, 4)
 int launch_predictive(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const double* d_nodes, double* d_rate, double* d_lpd,
                       double* d_part, double* d_sums);
+// calibration sums of a set's predictive distribution (calibrate.hip), shaped as launch_predictive: W = n_bins + n_levels + 3
+// columns per slot in G = ceil(W / 4) groups of four; d_levels (n_levels) on the device; d_cdf (n_rate, 2) = lo | hi or
+// null; d_part: (slots, G, ceil(source rows / 256), 4) doubles of the caller's workspace; d_sums (slots, 4 G)
+int launch_calibration(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const double* d_nodes, int n_bins, int n_levels,
+                       const double* d_levels, int max_count, double* d_cdf, double* d_part, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace

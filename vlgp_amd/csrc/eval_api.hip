@@ -1,11 +1,11 @@
-// The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_elbo, vlgp_forecast,
-// vlgp_marginal, vlgp_joint_laplace.  Every one is put together the same way: open the set, check the
-// arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
+// The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_calibration, vlgp_elbo,
+// vlgp_forecast, vlgp_marginal, vlgp_joint_laplace.  Every one is put together the same way: open the set,
+// check the arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
 #include <algorithm>
 
 #include "call_block.h"
 
-// ---- what the row scores (loglik, predictive) do once their own arguments are sound -----------------------------------
+// ---- what the row scores (loglik, predictive, calibration) do once their own arguments are sound ----------------------
 // admission, no per-entry output from overlapping masks, xb of the rows' owner; then the shapes of vlgp_loglik
 struct RowScore { bool by_row; LoglikShape S; int64_t n_blk; };
 static int open_row_score(vlgp_ctx* ctx, int set, UnitSet* us, const Admission& a, bool per_entry, const char* outputs,
@@ -68,6 +68,43 @@ extern "C" int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, cons
     cp.out(rate, blk.at(o.rate), sizeof(double) * (size_t)r.S.n_rate);
     cp.out(lpd, blk.at(o.lpd), sizeof(double) * (size_t)r.S.n_rate);
     return cp.finish("vlgp_predictive", "copy-out");
+}
+
+// vlgp_predictive's frame with W columns per slot: the device sums are (slots, 4 G) for the G groups of four that
+// launch_sums_finish adds, and the first W of every row go out
+extern "C" int vlgp_calibration(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, int n_bins,
+                                int n_levels, const double* levels, int max_count, double* cdf, double* sums) {
+    static const char* who = "vlgp_calibration";
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
+    if (n_nodes < 1 || n_nodes > 64) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_nodes = %d, need 1 <= n_nodes <= 64", who, n_nodes);
+    if (n_bins < 1 || n_bins > 32) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_bins = %d, need 1 <= n_bins <= 32", who, n_bins);
+    if (n_levels < 0 || n_levels > 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_levels = %d, need 0 <= n_levels <= 4", who, n_levels);
+    if (max_count < 1 || max_count > 65536)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: max_count = %d, need 1 <= max_count <= 65536", who, max_count);
+    if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs z, lwa and sums", who);
+    if (n_levels > 0 && !levels) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_levels = %d needs levels", who, n_levels);
+    for (int c = 0; c < n_levels; ++c)
+        if (!(levels[c] > 0.0 && levels[c] < 1.0))
+            return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: levels[%d] = %g, need 0 < level < 1", who, c, levels[c]);
+    RowScore r;
+    CHK(open_row_score(ctx, set, us, admit_vlgp_calibration, cdf != nullptr, "cdf", &r));
+    const int W = n_bins + n_levels + 3;
+    const CalibrationLayout o = calibration_layout(r.S.slots, r.S.n_rate, r.n_blk, n_bins, n_levels, cdf != nullptr);
+    if (r.S.slots > 0x7fffffffLL / (4 * o.groups)) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (replica, channel) slots", who);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    Copies cp(ctx);
+    cp.in(blk.at(o.nodes), z, sizeof(double) * (size_t)n_nodes);
+    cp.in(blk.at(o.nodes) + n_nodes, lwa, sizeof(double) * (size_t)n_nodes);
+    if (n_levels) cp.in(blk.at(o.levels), levels, sizeof(double) * (size_t)n_levels);
+    if (r.by_row) cp.nan_fill(blk.at(o.cdf), o.sums - o.cdf);
+    CHK(cp.status(who, "copy-in"));
+    CHK(launch_calibration(ctx, *us, vb, n_nodes, blk.at(o.nodes), n_bins, n_levels, blk.at(o.levels), max_count,
+                           blk.opt(cdf, o.cdf), blk.at(o.part), blk.at(o.sums)));
+    cp.out2d(sums, (size_t)W, blk.at(o.sums), (size_t)(4 * o.groups), (size_t)W, (size_t)r.S.slots);
+    cp.out(cdf, blk.at(o.cdf), sizeof(double) * 2 * (size_t)r.S.n_rate);
+    return cp.finish(who, "copy-out");
 }
 
 // ---- the scores of a posterior (elbo, forecast, marginal, joint Laplace) --------------------------------------------------

@@ -82,6 +82,23 @@ def hermite_nodes(n):
     return _f64(np.sqrt(2.0) * x), _f64(np.log(w / np.sqrt(np.pi)) + x * x)
 
 
+MAX_BINS, MAX_LEVELS, MAX_COUNT = 32, 4, 65536  # the limits of vlgp_calibration
+
+
+def check_calibration_args(n_bins, levels, max_count):
+    """``(n_bins, levels, max_count)`` as vlgp_calibration takes them -- two ints and a float64 array -- or ValueError:
+    ``1 <= n_bins <= 32``, at most 4 levels, every one in (0, 1), ``1 <= max_count <= 65536``."""
+    for name, val, top in (("n_bins", n_bins, MAX_BINS), ("max_count", max_count, MAX_COUNT)):
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or not 1 <= val <= top:
+            raise ValueError("%s must be an integer in [1, %d], got %r" % (name, top, val))
+    lev = _f64(np.asarray(levels, dtype=float).reshape(-1) if np.ndim(levels) <= 1 else levels)
+    if lev.ndim != 1 or len(lev) > MAX_LEVELS:
+        raise ValueError("levels must be a list of at most %d numbers, got %r" % (MAX_LEVELS, levels))
+    if not np.all((lev > 0.0) & (lev < 1.0)):
+        raise ValueError("every level must lie in (0, 1), got %r" % (levels,))
+    return int(n_bins), lev, int(max_count)
+
+
 class Replicas(collections.namedtuple("Replicas", "n channels by_entry")):
     """What ``Engine.replicate`` made of a set: ``n`` replicas; ``channels``, the left-out channel of every (replica,
     channel) pair in the caller's order, or None when the replicas leave single entries out (``by_entry``)."""
@@ -307,6 +324,23 @@ class Engine:
         self._ck(self.lib.vlgp_predictive(self.h, int(set_id), int(bool(vb)), len(z), dptr(z), dptr(lwa), dptr(rate),
                                           dptr(lpd), dptr(sums)))
         return sums, rate, lpd
+
+    def calibration(self, set_id, n_bins=10, levels=(0.5, 0.9), n_nodes=12, vb=True, max_count=4096, want_cdf=False):
+        """Calibration sums of a set's predictive distribution (vlgp_calibration): ``(sums, cdf)``.  ``sums`` has the
+        leading shape of ``predictive``'s sums and ``W = n_bins + len(levels) + 3`` columns per slot,
+        ``pit_0 ... | covered_0 ... | pearson | entries | skipped`` (``evaluation.calibration_from_sums`` reads them);
+        ``cdf``, with ``want_cdf``, has the per-entry shape of ``predictive``'s ``lpd`` plus ``(2,)``: ``F(y - 1), F(y)``,
+        NaN for a skipped entry (a Poisson count that is negative, no integer, not finite or above ``max_count``), else
+        None.  The arguments are checked before any device call.  Changes no state."""
+        n_bins, levels, max_count = check_calibration_args(n_bins, levels, max_count)
+        z, lwa = hermite_nodes(n_nodes)
+        sums, entry = self._score_shapes(set_id)
+        sums = np.empty(sums[:-1] + (n_bins + len(levels) + 3,))
+        cdf = np.empty(entry + (2,)) if want_cdf else None
+        self._ck(self.lib.vlgp_calibration(self.h, int(set_id), int(bool(vb)), len(z), dptr(z), dptr(lwa), n_bins,
+                                           len(levels), dptr(levels) if len(levels) else None, max_count, dptr(cdf),
+                                           dptr(sums)))
+        return sums, cdf
 
     def elbo(self, set_id, vb=True, want_rows=False):
         """Terms of the variational lower bound of a plain set (vlgp_elbo): ``(row_sums, kl_terms, n_failed, row_ell)``

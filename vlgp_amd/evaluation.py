@@ -154,8 +154,30 @@ the posterior of the linear predictor instead,
   way carries ``"density": "predictive"``.  By Jensen's inequality ``lpd`` of a Poisson entry is never below its
   expected log-likelihood (``elbo``'s per-entry term).
 
+Calibration of the predictive distribution (``calibration``, ``calibration_from_sums``, ``Engine.calibration``,
+``vlgp_calibration``).  A log score ranks models; it does not say whether the predictive distribution is the right one.
+Per scored entry, with ``m``, ``s2`` and ``rate`` as above:
+
+- Poisson channel, ``k = y``: ``p(j) = exp(lpd)`` of the count ``j``, exactly the predictive mass above (the mode-centred
+  ``n_nodes``-point rule, or the plug-in Poisson mass when ``s2 < 1e-30``); ``lo = F(k - 1) = sum_{j < k} p(j)`` added in the
+  order ``j = 0, 1, ...``, ``hi = lo + p(k)``, then both clipped to ``<= 1``.  One Gauss-Hermite rule centred at ``m`` on
+  the Poisson distribution function is NOT used: at 12 nodes it is off by 2e-2 at ``sqrt(s2) = 0.3``.  The sum of masses
+  is within 8e-9 of a dense trapezoid for ``sqrt(s2) <= 0.5`` at 12 nodes, 1.2e-6 at 1.0 (4e-11 at 32 nodes).
+- Gaussian channel: ``lo = hi = 1/2 erfc(-(y - m) / sqrt(2 (noise[n] + s2)))``.
+- PIT histogram, ``n_bins = J``, edges ``e_j = j / J`` (the non-randomised PIT of Czado, Gneiting & Held 2009): an entry
+  with ``hi > lo`` adds ``clip((e_{j+1} - lo) / (hi - lo), 0, 1) - clip((e_j - lo) / (hi - lo), 0, 1)`` to bin ``j``, one with
+  ``hi == lo`` adds 1 to bin ``min(J - 1, floor(lo J))``: every entry adds total mass 1.
+- coverage of the central interval of level ``c``, ``a = (1 - c) / 2``: covered iff ``hi >= a`` and ``lo < 1 - a`` -- for
+  counts exactly ``q_a <= y <= q_{1-a}`` with ``q_p = min{k : F(k) >= p}``.
+- Pearson term ``(y - mean) ** 2 / var``: Poisson ``mean = rate``, ``var = mean + mean ** 2 expm1(s2)`` (the clamp of
+  ``trunc_exp`` enters ``var`` only through ``mean``); Gaussian ``mean = m``, ``var = noise[n] + s2``.
+- a Poisson entry with ``y`` negative, not an integer, not finite or ``> max_count`` is skipped: it adds 1 to ``skipped``
+  and nothing else, and its ``lo, hi`` are NaN.
+- per slot the device sums ``W = n_bins + n_levels + 3`` columns, ``pit_0 ... | covered_0 ... | pearson | entries |
+  skipped``; ``calibration_from_sums`` turns them into frequencies.
+
 Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``, ``vlgp_marginal``,
-``vlgp_predictive``, ``vlgp_joint_laplace``): the results are the same bits on every run.
+``vlgp_predictive``, ``vlgp_calibration``, ``vlgp_joint_laplace``): the results are the same bits on every run.
 """
 import contextlib
 import math
@@ -171,7 +193,7 @@ from .util import _per_trial_entries
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
            "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
            "entry_scores", "leave_entries_out", "impute", "marginal_loglik", "weights_summary", "hermite_nodes",
-           "joint_posterior"]
+           "joint_posterior", "calibration", "calibration_from_sums"]
 
 SAMPLE_CHUNK = 64  # draws per device call: one lane per sample (csrc/marginal.hip)
 
@@ -253,13 +275,35 @@ def _density(predictive, n_nodes):
     return int(n_nodes)
 
 
-def _replica_chunk(eng, n_iter, dmu_bound, vb, posterior=False, density=None, **which):
+def _log_scorer(density=None):
+    """The scorer of the log scores, as the chunk loops take it: ``scorer(eng, set_id, vb) -> (sums, rate)`` by ``_score``
+    under ``density``; ``width`` columns of sums per slot; ``predictive``: which ``_PREDICTIVE_KEY`` its results carry."""
+    def scorer(eng, set_id, vb):
+        return _score(eng, set_id, vb, density)
+    scorer.width, scorer.predictive = 4, density is not None
+    return scorer
+
+
+def _calibration_scorer(n_bins, levels, n_nodes, max_count):
+    """The scorer of ``calibration``: ``Engine.calibration``'s sums, ``width = n_bins + len(levels) + 3`` columns per slot,
+    and no per-entry output (None where the log scorer returns the rates).  The arguments are checked here."""
+    n_bins, levels, max_count = E.check_calibration_args(n_bins, levels, max_count)
+    E.hermite_nodes(n_nodes)
+
+    def scorer(eng, set_id, vb):
+        sums, _ = eng.calibration(set_id, n_bins=n_bins, levels=levels, n_nodes=int(n_nodes), vb=vb, max_count=max_count)
+        return sums, None
+    scorer.width, scorer.predictive = n_bins + len(levels) + 3, True
+    return scorer
+
+
+def _replica_chunk(eng, n_iter, dmu_bound, vb, posterior=False, scorer=None, **which):
     """One chunk of replicas of ``SET_TEST`` (``which``: ``Engine.replicate``'s ``groups=`` or ``held_out=``): made,
-    inferred, scored (``_score``) and freed.  Returns ``(sums, rate, n_failed, posterior)``, the posterior (``mu, v, w``
-    of the replicas' rows) only on request."""
+    inferred, scored (``scorer``, default ``_log_scorer()``) and freed.  Returns ``(sums, rate, n_failed, posterior)``, the
+    posterior (``mu, v, w`` of the replicas' rows) only on request."""
     eng.replicate(SET_TEST, SET_REPLICAS, **which)
     n_failed = eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
-    sums, rate = _score(eng, SET_REPLICAS, vb, density)
+    sums, rate = (scorer or _log_scorer())(eng, SET_REPLICAS, vb)
     post = eng.download(SET_REPLICAS, ("mu", "v", "w")) if posterior else None
     eng.free_units(SET_REPLICAS)
     return sums, rate, n_failed, post
@@ -379,11 +423,11 @@ def _is_refusal(err):
     return err.status == ERR_STATE and "replicated set" in err.detail
 
 
-def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device, density=None):
-    """What ``leave_one_out`` and ``leave_group_out`` share, for validated ``groups``: for every group one inference
-    without it from a zero start, then its channels scored with their original loadings.  Returns ``channels`` (the
-    groups concatenated), ``rate`` per trial, ``ll``, ``ll_null``, ``n_spikes``, ``bits_per_spike``, ``n_failed``,
-    ``path``."""
+def _leave_out_sums(trials, params, config, groups, n_iter, path, max_replicas, device, scorer):
+    """For every group of validated ``groups`` one inference without it from a zero start, then its channels scored by
+    ``scorer`` with their original loadings: ``(sums (channels, scorer.width), rate (rows, channels), n_failed, path,
+    gauss)``, the channels those of the groups concatenated; ``rate`` is left unwritten by a scorer without per-entry
+    output."""
     L = int(params["zdim"])
     channels = [c for g in groups for c in g]
     n_iter = int(config["max_iter"] if n_iter is None else n_iter)
@@ -396,7 +440,7 @@ def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, devic
     rows = int(sum(lengths))
     units = _zero_start(trials, L)
     rate = np.empty((rows, len(channels)))
-    sums = np.empty((len(channels), 4))
+    sums = np.empty((len(channels), scorer.width))
     n_failed = 0
     used = "batched" if path != "sequential" else "sequential"
     with _resident(trials, params, units, device) as eng:
@@ -406,8 +450,9 @@ def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, devic
             try:
                 for chunk in plan_chunks(groups, cap):
                     n = sum(len(g) for g in chunk)
-                    sums[done:done + n], rate[:, done:done + n], bad, _ = \
-                        _replica_chunk(eng, n_iter, dmu_bound, vb, density=density, groups=chunk)
+                    sums[done:done + n], r, bad, _ = _replica_chunk(eng, n_iter, dmu_bound, vb, scorer=scorer, groups=chunk)
+                    if r is not None:
+                        rate[:, done:done + n] = r
                     n_failed += bad
                     done += n
             except VlgpError as err:
@@ -425,16 +470,27 @@ def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, devic
                 eng.upload(SET_TEST, units)  # (mu = v = w = 0 again)
                 n_failed += eng.estep(SET_TEST, n_iter, dmu_bound, vb)
                 eng.set_params(a, b, noise)
-                s, r = _score(eng, SET_TEST, vb, density)
+                s, r = scorer(eng, SET_TEST, vb)
                 sums[done:done + len(g)] = s[g]
-                rate[:, done:done + len(g)] = r[:, g]
+                if r is not None:
+                    rate[:, done:done + len(g)] = r[:, g]
                 done += len(g)
-    ll, ll_null, ny, bps = bits_per_spike(sums, rows, eng.gauss[channels])
+    return sums, rate, int(n_failed), used, eng.gauss[channels]
+
+
+def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device, scorer):
+    """What ``leave_one_out`` and ``leave_group_out`` share, for validated ``groups`` and a log scorer
+    (``_leave_out_sums``).  Returns ``channels`` (the groups concatenated), ``rate`` per trial, ``ll``, ``ll_null``,
+    ``n_spikes``, ``bits_per_spike``, ``n_failed``, ``path``."""
+    sums, rate, n_failed, used, gauss = _leave_out_sums(trials, params, config, groups, n_iter, path, max_replicas, device,
+                                                        scorer)
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    ll, ll_null, ny, bps = bits_per_spike(sums, int(sum(lengths)), gauss)
     return {
-        "channels": channels,
+        "channels": [c for g in groups for c in g],
         "rate": _per_trial(rate, lengths),
         "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
-        "n_failed": int(n_failed), "path": used, **_PREDICTIVE_KEY[density is not None],
+        "n_failed": n_failed, "path": used, **_PREDICTIVE_KEY[scorer.predictive],
     }
 
 
@@ -462,7 +518,7 @@ def leave_one_out(trials, params, config, channels=None, n_iter=None, path="auto
     if not channels or len(set(channels)) != len(channels) or min(channels) < 0 or max(channels) >= N:
         raise ValueError("channels must be distinct indices in [0, %d)" % N)
     return _leave_out(trials, params, config, [[c] for c in channels], n_iter, path, max_replicas, device,
-                      _density(predictive, n_nodes))
+                      _log_scorer(_density(predictive, n_nodes)))
 
 
 def channel_folds(n_channels, n_folds, seed=0):
@@ -518,7 +574,8 @@ def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_it
         raise ValueError("path must be 'auto', 'batched' or 'sequential'")
     N = int(params["ydim"])
     groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
-    out = _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device, _density(predictive, n_nodes))
+    out = _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device,
+                     _log_scorer(_density(predictive, n_nodes)))
     out.update(groups=groups, group_of=[k for k, g in enumerate(groups) for _ in g],
                co_bps=co_bits_per_spike(out["ll"], out["ll_null"], out["n_spikes"]))
     return out
@@ -564,10 +621,12 @@ def entry_scores(sums, n_entries, gauss=None):
             "speckled_bps": co_bits_per_spike(ll, ll_null, ny)}
 
 
-def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device, posterior=False, density=None):
-    """One replica per mask of ``held_out`` (bool (n_rep, rows, N)) from a zero start, ``max_replicas`` at a time:
-    ``(sums (n_rep, N, 4), rate (rows, N), n_failed, posterior)``, the posterior (mu, v, w of every replica, (n_rep, rows,
-    L) each) only on request.  The masks of one call are pairwise disjoint, so the rate of every entry has one source."""
+def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device, posterior=False, scorer=None):
+    """One replica per mask of ``held_out`` (bool (n_rep, rows, N)) from a zero start, ``max_replicas`` at a time, scored by
+    ``scorer`` (default ``_log_scorer()``; without per-entry output ``rate`` stays NaN):
+    ``(sums (n_rep, N, scorer.width), rate (rows, N), n_failed, posterior, gauss)``, the posterior (mu, v, w of every
+    replica, (n_rep, rows, L) each) only on request.  The masks of one call are pairwise disjoint, so the rate of every
+    entry has one source."""
     L = int(params["zdim"])
     n_iter = int(config["max_iter"] if n_iter is None else n_iter)
     vb = config["method"] == "VB"
@@ -575,7 +634,8 @@ def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device,
     rows, N = int(sum(lengths)), int(params["ydim"])
     units = _zero_start(trials, L)
     n_rep = held_out.shape[0]
-    sums = np.empty((n_rep, N, 4))
+    scorer = scorer or _log_scorer()
+    sums = np.empty((n_rep, N, scorer.width))
     rate = np.full((rows, N), np.nan)
     post = {k: np.empty((n_rep, rows, L)) for k in ("mu", "v", "w")} if posterior else None
     n_failed = 0
@@ -586,17 +646,35 @@ def _entries_out(trials, params, config, held_out, n_iter, max_replicas, device,
         cap = max(int(cap), 1)
         for k0 in range(0, n_rep, cap):
             chunk = held_out[k0:k0 + cap]
-            s, r, bad, got = _replica_chunk(eng, n_iter, config["dmu_bound"], vb, posterior=posterior, density=density,
+            s, r, bad, got = _replica_chunk(eng, n_iter, config["dmu_bound"], vb, posterior=posterior, scorer=scorer,
                                             held_out=chunk)
             n_failed += bad
             if posterior:
                 for key in post:
                     post[key][k0:k0 + len(chunk)] = got[key].reshape(len(chunk), rows, L)
             sums[k0:k0 + len(chunk)] = s
-            mine = chunk.any(axis=0)
-            rate[mine] = r[mine]
+            if r is not None:
+                mine = chunk.any(axis=0)
+                rate[mine] = r[mine]
         gauss = eng.gauss.copy()
     return sums, rate, int(n_failed), post, gauss
+
+
+def _entry_masks(trials, params, folds, n_folds, seed):
+    """``(F, held)`` of a speckled hold-out: the fold of every entry over the concatenated rows (``folds`` per trial, -1
+    for an entry never held out; default ``entry_folds``) and the bool masks (n_folds, rows, N) of the folds."""
+    rows, N = int(sum(int(tr["y"].shape[0]) for tr in trials)), int(params["ydim"])
+    if folds is None:
+        F = entry_folds(rows, N, n_folds, seed)
+        n_folds = int(n_folds)
+    else:
+        F = np.concatenate(_per_trial_entries(folds, trials, "folds", int), axis=0)
+        if F.min() < -1:
+            raise ValueError("fold indices are >= 0, or -1 for an entry that is never held out")
+        n_folds = int(F.max()) + 1
+        if n_folds < 1:
+            raise ValueError("folds hold no entry out")
+    return F, np.stack([F == k for k in range(n_folds)])
 
 
 def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_iter=None, max_replicas=None, device=0,
@@ -617,20 +695,9 @@ def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_i
     ``speckled_bps``; ``n_failed``.  ``predictive``, ``n_nodes``: as ``leave_one_out``."""
     density = _density(predictive, n_nodes)
     lengths = [int(tr["y"].shape[0]) for tr in trials]
-    rows, N = int(sum(lengths)), int(params["ydim"])
-    if folds is None:
-        F = entry_folds(rows, N, n_folds, seed)
-        n_folds = int(n_folds)
-    else:
-        F = np.concatenate(_per_trial_entries(folds, trials, "folds", int), axis=0)
-        if F.min() < -1:
-            raise ValueError("fold indices are >= 0, or -1 for an entry that is never held out")
-        n_folds = int(F.max()) + 1
-        if n_folds < 1:
-            raise ValueError("folds hold no entry out")
-    held = np.stack([F == k for k in range(n_folds)])
+    F, held = _entry_masks(trials, params, folds, n_folds, seed)
     sums, rate, n_failed, _, gauss = _entries_out(trials, params, config, held, n_iter, max_replicas, device,
-                                                  density=density)
+                                                  scorer=_log_scorer(density))
     out = entry_scores(sums, (F >= 0).sum(axis=0), gauss)
     out.update(folds=_per_trial(F, lengths), rate=_per_trial(rate, lengths), n_failed=n_failed,
                **_PREDICTIVE_KEY[density is not None])
@@ -651,6 +718,78 @@ def impute(trials, params, config, missing, n_iter=None, device=0):
     _, rate, n_failed, post, _ = _entries_out(trials, params, config, held, n_iter, 1, device, posterior=True)
     return {"mu": _per_trial(post["mu"][0], lengths), "v": _per_trial(post["v"][0], lengths),
             "w": _per_trial(post["w"][0], lengths), "rate": _per_trial(rate, lengths), "n_failed": n_failed}
+
+
+def calibration_from_sums(sums, n_bins, levels):
+    """Calibration summaries from ``vlgp_calibration``'s sums (pure host code).  ``sums`` (..., W) with
+    ``W = n_bins + len(levels) + 3`` columns ``pit_0 ... | covered_0 ... | pearson | entries | skipped`` per slot; the
+    leading axes are the slots and are kept.
+
+    Returns a dict: ``pit`` (..., n_bins), each slot's histogram divided by its ``entries`` (a calibrated slot is flat at
+    ``1 / n_bins``); ``coverage`` (..., len(levels)), the share of entries inside each central interval; ``dispersion``,
+    ``pearson / entries`` (1 when the predictive variance is right, above it when the counts are over-dispersed against the
+    model); ``entries`` and ``skipped`` per slot (integers); ``levels``; and ``pit_all``, ``coverage_all``,
+    ``dispersion_all``, the same from the columns summed over every slot.  A slot without an entry gives NaN."""
+    sums = np.asarray(sums, dtype=float)
+    levels = np.asarray(levels, dtype=float).reshape(-1)
+    J, C = int(n_bins), len(levels)
+    if sums.ndim < 1 or sums.shape[-1] != J + C + 3:
+        raise ValueError("sums must have n_bins + len(levels) + 3 = %d columns, got shape %r" % (J + C + 3, sums.shape))
+    tot = sums.reshape(-1, J + C + 3).sum(axis=0)
+
+    def ratio(x, n):
+        n = np.asarray(n, dtype=float)[..., None]
+        return np.where(n > 0, x / np.where(n > 0, n, 1.0), np.nan)
+
+    pit, cov, pearson, entries = sums[..., :J], sums[..., J:J + C], sums[..., J + C:J + C + 1], sums[..., J + C + 1]
+    return {"pit": ratio(pit, entries), "pit_all": ratio(tot[:J], tot[J + C + 1]),
+            "coverage": ratio(cov, entries), "coverage_all": ratio(tot[J:J + C], tot[J + C + 1]), "levels": levels.copy(),
+            "dispersion": ratio(pearson, entries)[..., 0],
+            "dispersion_all": float(ratio(tot[J + C:J + C + 1], tot[J + C + 1])[0]),
+            "entries": np.rint(entries).astype(np.int64), "skipped": np.rint(sums[..., J + C + 2]).astype(np.int64)}
+
+
+def calibration(trials, params, config, how="in_sample", groups=None, folds=None, n_folds=5, seed=0, n_bins=10,
+                levels=(0.5, 0.9), n_nodes=12, max_count=4096, n_iter=None, max_replicas=None, device=0):
+    """Calibration of the predictive distribution, per channel (module docstring for the definitions): PIT histogram,
+    coverage of the central intervals ``levels`` and Pearson dispersion.
+
+    ``how="in_sample"``: the trials' own posterior ``mu, v``, as ``loglik`` scores it.  ``how="channels"``: co-smoothing --
+    ``leave_group_out``'s inference (``groups``, default ``channel_folds(N, min(n_folds, N), seed)``; batched unless the
+    device refuses the replicas), every channel scored under the posterior inferred without its group.
+    ``how="entries"``: speckled -- ``leave_entries_out``'s inference (``folds``, default ``entry_folds`` with ``n_folds``
+    and ``seed``), every entry scored under the posterior of the fold that holds it out.  ``n_iter``, ``max_replicas``: as
+    there.  ``n_nodes``: quadrature nodes per Poisson mass; ``max_count``: Poisson entries above it are skipped, not
+    scored.  Trials that carry ``missing`` raise ``ValueError``.
+
+    Returns ``calibration_from_sums``' dict with one slot per channel, the replicas or folds added in order, plus
+    ``n_failed`` (failed E-step updates; 0 in sample).  A channel no group holds has no entry: NaN."""
+    if how not in ("in_sample", "channels", "entries"):
+        raise ValueError("how must be 'in_sample', 'channels' or 'entries', got %r" % (how,))
+    _no_missing(trials, "calibration")
+    scorer = _calibration_scorer(n_bins, levels, n_nodes, max_count)
+    N, L = int(params["ydim"]), int(params["zdim"])
+    n_failed = 0
+    if how == "in_sample":
+        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "v": tr.get("v", np.zeros((tr["y"].shape[0], L))),
+                  "w": None} for tr in trials]
+        with _resident(trials, params, units, device, priors=False) as eng:
+            sums, _ = scorer(eng, SET_TEST, config.get("method", "VB") == "VB")
+    elif how == "channels":
+        groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
+        got, _, n_failed, _, _ = _leave_out_sums(trials, params, config, groups, n_iter, "auto", max_replicas, device,
+                                                 scorer)
+        sums = np.zeros((N, scorer.width))
+        sums[[c for g in groups for c in g]] = got
+    else:
+        _, held = _entry_masks(trials, params, folds, n_folds, seed)
+        got, _, n_failed, _, _ = _entries_out(trials, params, config, held, n_iter, max_replicas, device, scorer=scorer)
+        sums = np.zeros((N, scorer.width))
+        for k in range(got.shape[0]):
+            sums += got[k]
+    out = calibration_from_sums(sums, n_bins, levels)
+    out["n_failed"] = int(n_failed)
+    return out
 
 
 def forward_prediction(trials, params, config, n_forward, n_iter=None, device=0, predictive=False, n_nodes=12):
