@@ -1,7 +1,9 @@
-"""Every output of the six scoring entry points on one seeded set, saved for a bit-for-bit comparison of two builds.
+"""Every output of the seven scoring entry points on one seeded set, saved for a bit-for-bit comparison of two builds.
 
-    python tools/eval_bits.py OUT.npz              one E-step on a ragged set, then loglik, predictive, elbo, forecast,
-                                                   marginal, joint_laplace and both marginal_loglik proposals (130 draws)
+    python tools/eval_bits.py OUT.npz              one E-step on a ragged set, then loglik, predictive, calibration, elbo,
+                                                   forecast, marginal, joint_laplace and both marginal_loglik proposals
+                                                   (130 draws); then the three row scores with every per-entry output on
+                                                   group replicas and on a speckled masked set of it, one E-step each
     python tools/eval_bits.py --compare A.npz B.npz   np.array_equal(..., equal_nan=True) on every array; exit status 1
                                                    if the files differ in their names or in any array
 Nothing is fitted: the parameters are seeded, the prior factors come from the device for fixed time scales.  Run it from
@@ -17,6 +19,16 @@ LENGTHS = [1, 7, 64, 65, 130, 130]
 N, L, RANK, K, SET = 14, 3, 20, 130, 0
 OMEGA = [2e-2, 5e-3, 1e-3]
 N_EXT = 5
+GROUPS = [[0, 5, 13], [2], [7, 8]]  # the group replicas; N_FOLDS speckled folds make the masked set
+N_FOLDS = 3
+
+
+def row_scores(eng, set_id, prefix):
+    out = {}
+    out["loglik_sums"], out["loglik_rate"] = eng.loglik(set_id, want_rate=True)
+    out["pred_sums"], out["pred_rate"], out["pred_lpd"] = eng.predictive(set_id, want_rate=True, want_lpd=True)
+    out["cal_sums"], out["cal_cdf"] = eng.calibration(set_id, want_cdf=True)
+    return {prefix + k: v for k, v in out.items()}
 
 
 def outputs():
@@ -46,8 +58,7 @@ def outputs():
         out["estep_failed"] = np.array([eng.estep(SET, 1, 5.0, True)])
         state = eng.download(SET, ("mu", "v", "w"))
         out.update({"state_" + k: v for k, v in state.items()})
-        out["loglik_sums"], out["loglik_rate"] = eng.loglik(SET, want_rate=True)
-        out["pred_sums"], out["pred_rate"], out["pred_lpd"] = eng.predictive(SET, want_rate=True, want_lpd=True)
+        out.update(row_scores(eng, SET, ""))
         out["elbo_sums"], out["elbo_terms"], n, out["elbo_rows"] = eng.elbo(SET, want_rows=True)
         out["elbo_failed"] = np.array([n])
         out["fc_mu"], out["fc_v"], out["fc_terms"], n = eng.forecast(SET, ext)
@@ -56,6 +67,13 @@ def outputs():
         out["mg_failed"] = np.array([n])
         joint = eng.joint_laplace(SET, eps=eps)
         out.update({"jl_" + k: np.asarray(v) for k, v in joint.items()})
+        folds = evaluation.entry_folds(sum(LENGTHS), N, N_FOLDS, 5)
+        held = np.stack([folds == k for k in range(N_FOLDS)])
+        for name, how in (("grp_", {"groups": GROUPS}), ("msk_", {"held_out": held})):
+            eng.replicate(SET, 2, **how)
+            out[name + "estep_failed"] = np.array([eng.estep(2, 1, 5.0, True)])
+            out.update(row_scores(eng, 2, name))
+            eng.free_units(2)
     off = np.concatenate([[0], np.cumsum(LENGTHS)])
     fitted = [dict(tr, **{k: state[k][off[i]:off[i + 1]] for k in ("mu", "v", "w")}) for i, tr in enumerate(trials)]
     for proposal in ("posterior", "joint"):

@@ -294,16 +294,13 @@ struct vlgp_ctx {
 // the set that owns this set's y / x / xb rows: the set itself, or the source of its replicas
 inline UnitSet& vlgp_rows_owner(vlgp_ctx* ctx, UnitSet& us) { return us.rep.src >= 0 ? ctx->sets[us.rep.src] : us; }
 
-// What vlgp_loglik writes for a set, and how its row pass is launched: `slots` rows of four sums, `n_rate` rates,
-// grid.y of the launch and what to say when that exceeds the grid's limit of 65535.
-struct LoglikShape { int64_t slots, n_rate; int grid_y; const char* limit; };
+// What vlgp_loglik writes for a set, and how its row pass is launched: `slots` rows of four sums, `n_rate` rates and
+// grid.y of the launch.
+struct LoglikShape { int64_t slots, n_rate; int grid_y; };
 inline LoglikShape vlgp_loglik_shape(const vlgp_ctx* ctx, const UnitSet& us) {
-    if (us.is(SET_BY_ROW))
-        return {(int64_t)us.rep.n * ctx->N, us.rep.rows_src * ctx->N, us.rep.n, "vlgp_loglik: at most 65535 replicas per masked set"};
-    if (us.is(SET_GROUPS))
-        return {us.rep.n_pairs, us.rep.rows_src * us.rep.n_pairs, us.rep.n_pairs,
-                "vlgp_loglik: at most 65535 (replica, channel) pairs per set"};
-    return {ctx->N, us.rows * ctx->N, 1, ""};
+    if (us.is(SET_BY_ROW)) return {(int64_t)us.rep.n * ctx->N, us.rep.rows_src * ctx->N, us.rep.n};
+    if (us.is(SET_GROUPS)) return {us.rep.n_pairs, us.rep.rows_src * us.rep.n_pairs, us.rep.n_pairs};
+    return {ctx->N, us.rows * ctx->N, 1};
 }
 
 // ---- error plumbing ------------------------------------------------------

@@ -1,8 +1,7 @@
 // What the kernels of the predictive distribution share (predictive.hip, calibrate.hip): the node tables of the
 // Gauss-Hermite rule in LDS and the Poisson-lognormal integral by the mode-centred rule.  Device helpers only; no kernels.
 #pragma once
-#include "eval_wave.h"
-#include "fast_exp.h"
+#include "row_walk.h"
 
 #define PRED_NODES 64  // most nodes of a rule (the host checks)
 
@@ -11,11 +10,12 @@ struct Nodes {
     const double* tab;  // global: z (n) | lwa (n)
 };
 
-// the tables into LDS: z at lds[0 ..], lwa at lds[PRED_NODES ..]; the caller synchronises
-__device__ __forceinline__ void nodes_stage(const Nodes& Q, double* lds) {
+// the tables in LDS; the caller synchronises
+struct NodeTables { double z[PRED_NODES], lwa[PRED_NODES]; };
+__device__ __forceinline__ void nodes_stage(const Nodes& Q, NodeTables& t) {
     if ((int)threadIdx.x < Q.n) {
-        lds[threadIdx.x] = Q.tab[threadIdx.x];
-        lds[PRED_NODES + threadIdx.x] = Q.tab[Q.n + threadIdx.x];
+        t.z[threadIdx.x] = Q.tab[threadIdx.x];
+        t.lwa[threadIdx.x] = Q.tab[Q.n + threadIdx.x];
     }
 }
 
