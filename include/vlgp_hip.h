@@ -256,6 +256,23 @@ int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, const double* e
  * on doubles: the same bits on every run. */
 int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_samples, const double* eps, double* beta,
                        double* stats, double* mu, double* v, double* log_w, double* parts, int* n_failed);
+/* The joint Laplace posterior of vlgp_joint_laplace with the covariance of every row, also with entries held out
+ * (DESIGN.md 4.14).  The model, the objective, the Newton iteration and its acceptance rule, beta (units, L, R), stats
+ * (units, 8) and mu (rows, L) are vlgp_joint_laplace's; there are no draws.
+ *   cov[t; l, l'] = G_l[t, :] (H^-1)_{l l'} G_l'[t, :]'   at the mode,
+ * cov (rows, L (L + 1) / 2), the pair (l, l'), l' <= l, at l (l + 1) / 2 + l'; the pairs (l, l) are vlgp_joint_laplace's v.
+ * Takes what vlgp_joint_laplace takes and a masked set of ONE replica (vlgp_replicate_masked with n_rep == 1); group
+ * replicas and masked sets of several replicas are VLGP_ERR_STATE.  On a masked set a held-out entry (t, n)
+ * contributes nothing: its term is left out of ll and of the sum of absolute terms, its res = cur = 0, so it is absent from
+ * g, c, H and laplace, and what y holds there (NaN included) reaches no sum; with no bit set every output is the plain
+ * set's, bit for bit, given the same start.  Start: a plain set as vlgp_joint_laplace; a masked set at beta = 0 (the
+ * mean-field centres would read every y; the mode does not depend on the start, the count of factorisations does).
+ * A unit with a pivot that is not positive and finite: stats[0 .. 4] NaN, its rows of mu and cov NaN, counted in *n_failed.
+ * beta, mu, cov and n_failed may be NULL; a null stats, max_iter < 1 or tol not > 0: VLGP_ERR_ARG naming the argument;
+ * D > 512: VLGP_ERR_STATE.  Waits and state as vlgp_joint_laplace: nothing changes.  Fixed-order sums, no atomics on
+ * doubles: the same bits on every run. */
+int vlgp_joint_posterior(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats, double* mu,
+                         double* cov, int* n_failed);
 /* Posterior-predictive log density of every observation under the set's current posterior: where vlgp_loglik scores an
  * entry with the plug-in density p(y | E_q[rate]), this integrates the likelihood over the posterior of its linear
  * predictor,
@@ -314,6 +331,27 @@ int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z
  * every run. */
 int vlgp_calibration(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, int n_bins,
                      int n_levels, const double* levels, int max_count, double* cdf, double* sums);
+/* vlgp_predictive and vlgp_calibration under a posterior of the latents the CALLER supplies, a mean and a full L x L
+ * covariance per row (vlgp_joint_posterior's mu, cov; any other Gaussian will do): the siblings with vb = 1 and, for the
+ * entry (t, n) scored under row `mrow` of the posterior's set (DESIGN.md 4.12's table: the row itself for a plain set,
+ * replica k's copy of it, k rows + t, for group replicas and masked sets),
+ *   m  = a_n . mu[mrow] + (b x)_tn                      the chain of vlgp_predictive's m
+ *   q  = sum_l a_ln (sum_l' C[mrow; l, l'] a_l'n)       the inner sums first, each a chain of fused multiply-adds from 0
+ *                                                       over l' = 0 ... L - 1; then the outer one over l = 0 ... L - 1
+ *   s2 = max(0, q),   rate = trunc_exp(fma(1/2, s2, m)) Poisson, m Gaussian.
+ * mu (rows of the posterior's set, L) and cov (the same rows, L (L + 1) / 2), the pair (l, l'), l' <= l, at
+ * l (l + 1) / 2 + l' as vlgp_joint_posterior packs it, are host arrays; both are required (a null one: VLGP_ERR_ARG naming
+ * it).  The calls are stateless: nothing is attached to the set and no set state changes; the set's own mu, v are not read.
+ * Everything else is the sibling's: the node tables, slots, layouts, limits, the sets taken, the refusal of
+ * per-entry output from overlapping masks, the s2 < 1e-30 plug-in branch, the waits, the fixed-order sums.
+ * An entry whose m or q is not finite (the rows of a unit vlgp_joint_posterior failed on): vlgp_predictive_cov writes NaN
+ * to its lpd and rate and lets the NaN into sums[., 0] and sums[., 2] (sum y and the fourth column stay); vlgp_calibration_cov
+ * skips it as it skips a count it cannot score -- cdf NaN, 1 added to `skipped`, nothing else; no bin is computed from it. */
+int vlgp_predictive_cov(vlgp_ctx* ctx, int set, int n_nodes, const double* z, const double* lwa, const double* mu,
+                        const double* cov, double* rate, double* lpd, double* sums);
+int vlgp_calibration_cov(vlgp_ctx* ctx, int set, int n_nodes, const double* z, const double* lwa, const double* mu,
+                         const double* cov, int n_bins, int n_levels, const double* levels, int max_count, double* cdf,
+                         double* sums);
 
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);

@@ -126,6 +126,9 @@ _SIGNATURES = {
     "vlgp_predictive": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "vlgp_calibration": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "vlgp_joint_laplace": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "vlgp_joint_posterior": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
+    "vlgp_predictive_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "vlgp_calibration_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

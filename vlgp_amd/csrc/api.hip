@@ -128,6 +128,10 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_loglik, SET_ANY & ~SET_COPIED, "vlgp_loglik on a copied cut: merge it and score the source set")           \
     X(vlgp_predictive, SET_ANY & ~SET_COPIED, "vlgp_predictive on a copied cut: merge it and score the source set")   \
     X(vlgp_calibration, SET_ANY & ~SET_COPIED, "vlgp_calibration on a copied cut: merge it and score the source set") \
+    X(vlgp_predictive_cov, SET_ANY & ~SET_COPIED,                                                                     \
+      "vlgp_predictive_cov on a copied cut: merge it and score the source set")                                       \
+    X(vlgp_calibration_cov, SET_ANY & ~SET_COPIED,                                                                    \
+      "vlgp_calibration_cov on a copied cut: merge it and score the source set")                                      \
     X(vlgp_update_w, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_update_v, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_mstep_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \
@@ -142,6 +146,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_forecast, NOT_REPLICATED, nullptr) /* (a cut is refused once its priors are bound: see there) */           \
     X(vlgp_marginal, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_joint_laplace, NOT_REPLICATED, nullptr)                                                                    \
+    X(vlgp_joint_posterior, NOT_REPLICATED | SET_MASKED_FIT, nullptr)                                                 \
     X(vlgp_stash_mu, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_set_overlaps, NOT_REPLICATED, nullptr) /* (and equal-length units that are no tiling cut: see there) */    \
     X(vlgp_unshare_mu, NOT_REPLICATED, nullptr)                                                                       \

@@ -20,6 +20,8 @@
 // block_sums4: a slot's partials are G = ceil(W / 4) groups of (n_blk, 4), which launch_sums_finish adds in workgroup
 // order into (slots, 4 G) -- the host copies the first W of a row out.  The columns of a group are computed from lo, hi
 // as they are needed, so nothing is indexed dynamically in registers.  No atomics: the same bits on every run.
+// vlgp_calibration_cov is the same entry with m and s2 from a supplied mean and covariance of the latents (CovMoments,
+// row_walk.h), vb = 1; an entry whose m or s2 is not finite is skipped like a count that cannot be scored.
 #include "pred_entry.h"
 
 namespace {
@@ -35,12 +37,19 @@ struct CalEntry {
     bool skip;
 };
 
-// one entry
-__device__ __forceinline__ CalEntry cal_entry(const RowModel& M, int64_t row, int64_t mrow, int n, int nq, const double* zt,
-                                              const double* lt, int max_count) {
+// one entry under the moments of `src` (row_walk.h); a checked source whose m or s2 is not finite: skipped, before anything
+// is computed from them
+template <class Src>
+__device__ __forceinline__ CalEntry cal_entry(const Src& src, const RowModel& M, int64_t row, int64_t mrow, int n, int nq,
+                                              const double* zt, const double* lt, int max_count) {
     CalEntry e = {0.0, 0.0, 0.0, false};
-    const EntryMoments em = entry_moments(M, row, mrow, n);
+    const EntryMoments em = src.moments(M, row, mrow, n);
     const double m = em.m, s2 = em.s2, yv = em.y;
+    if (Src::checked && !moments_finite(em)) {
+        e.lo = e.hi = NAN;
+        e.skip = true;
+        return e;
+    }
     if (M.gauss[n]) {
         const double nz = M.noise[n] + s2, d = yv - m;
         e.lo = e.hi = 0.5 * erfc(-d / sqrt(2.0 * nz));
@@ -54,7 +63,7 @@ __device__ __forceinline__ CalEntry cal_entry(const RowModel& M, int64_t row, in
         return e;
     }
     const int k = min((int)yv, max_count);
-    const double lam = exp(clamp10(row_quad(M, mrow, n, m)));
+    const double lam = exp(clamp10(src.rate_arg(M, mrow, n, em)));
     const double llam = log(lam);
     double lo = 0.0, pk = 0.0;
 #pragma unroll 1
@@ -97,35 +106,63 @@ __device__ __forceinline__ double cal_column(const CalEntry& e, int c, const Cal
     return c == 0 ? e.pearson : c == 1 ? 1.0 : 0.0;
 }
 
+struct CalLds { NodeTables t; double lev[4]; };
+
+// the columns of a group are computed from lo, hi as the group is emitted (of a lane that is not live: from zeros)
+template <class Src, class Emit>
+__device__ __forceinline__ void cal_scorer_entry(const Src& src, const RowModel& M, const Nodes& q, const CalCols& k, int groups,
+                                                 double* cdf, const CalLds& l, int64_t row, int64_t mrow, int n, bool live,
+                                                 int64_t at, Emit emit) {
+    CalEntry e = {0.0, 0.0, 0.0, false};
+    if (live) {
+        e = cal_entry(src, M, row, mrow, n, q.n, l.t.z, l.t.lwa, k.max_count);
+        if (cdf) {
+            cdf[2 * at] = e.lo;
+            cdf[2 * at + 1] = e.hi;
+        }
+    }
+    for (int g = 0; g < groups; ++g) {
+        double s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = cal_column(e, 4 * g + j, k, l.lev);
+        emit(s);
+    }
+}
+
 struct CalScorer {
     Nodes q;
     CalCols k;
     int groups;    // G = ceil((J + C + 3) / 4)
     double* cdf;   // plain (rows, N, 2), group replicas (rows, n_pairs, 2), masked (rows, N, 2) filled with NaN beforehand:
                    // lo | hi; or null
-    struct Lds { NodeTables t; double lev[4]; };
+    typedef CalLds Lds;
     __device__ void stage(Lds& l) const {
         nodes_stage(q, l.t);
         if ((int)threadIdx.x < k.n_levels) l.lev[threadIdx.x] = k.levels[threadIdx.x];
     }
-    // the columns of a group are computed from lo, hi as the group is emitted (of a lane that is not live: from zeros)
     template <class Emit>
     __device__ __forceinline__ void entry(const RowModel& M, const Lds& l, int64_t row, int64_t mrow, int n, bool live,
                                           int64_t at, Emit emit) const {
-        CalEntry e = {0.0, 0.0, 0.0, false};
-        if (live) {
-            e = cal_entry(M, row, mrow, n, q.n, l.t.z, l.t.lwa, k.max_count);
-            if (cdf) {
-                cdf[2 * at] = e.lo;
-                cdf[2 * at + 1] = e.hi;
-            }
-        }
-        for (int g = 0; g < groups; ++g) {
-            double s[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[j] = cal_column(e, 4 * g + j, k, l.lev);
-            emit(s);
-        }
+        cal_scorer_entry(SetMoments{}, M, q, k, groups, cdf, l, row, mrow, n, live, at, emit);
+    }
+};
+
+// vlgp_calibration_cov: the same entry under the caller's mu, cov
+struct CalCovScorer {
+    Nodes q;
+    CalCols k;
+    int groups;
+    double* cdf;
+    CovMoments src;
+    typedef CalLds Lds;
+    __device__ void stage(Lds& l) const {
+        nodes_stage(q, l.t);
+        if ((int)threadIdx.x < k.n_levels) l.lev[threadIdx.x] = k.levels[threadIdx.x];
+    }
+    template <class Emit>
+    __device__ __forceinline__ void entry(const RowModel& M, const Lds& l, int64_t row, int64_t mrow, int n, bool live,
+                                          int64_t at, Emit emit) const {
+        cal_scorer_entry(src, M, q, k, groups, cdf, l, row, mrow, n, live, at, emit);
     }
 };
 
@@ -136,4 +173,12 @@ int launch_calibration(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const do
     const CalCols K = {n_bins, n_levels, max_count, d_levels};
     const CalScorer S = {{n_nodes, d_nodes}, K, (n_bins + n_levels + 3 + 3) / 4, d_cdf};
     return launch_row_scores(ctx, "vlgp_calibration", us, vb, S, d_part, d_sums);
+}
+
+int launch_calibration_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double* d_nodes, const double* d_mu,
+                           const double* d_cov, int n_bins, int n_levels, const double* d_levels, int max_count,
+                           double* d_cdf, double* d_part, double* d_sums) {
+    const CalCols K = {n_bins, n_levels, max_count, d_levels};
+    const CalCovScorer S = {{n_nodes, d_nodes}, K, (n_bins + n_levels + 3 + 3) / 4, d_cdf, {d_mu, d_cov}};
+    return launch_row_scores(ctx, "vlgp_calibration_cov", us, 1, S, d_part, d_sums);
 }

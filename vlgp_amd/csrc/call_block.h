@@ -14,7 +14,7 @@ struct BlockLayout {
     int64_t need() const { return at; }
 };
 
-// ---- the blocks of the seven calls: integers in, named offsets and `need` out; the regions in the order of the block -------
+// ---- the blocks of the calls: integers in, named offsets and `need` out; the regions in the order of the block -------
 // (a braced list is evaluated left to right: the initialisers below ARE the order of the regions)
 // rate (n_rate, when wanted) | sums (slots, 4); the partials live in vlgp_ctx::d_work
 struct LoglikLayout { int64_t rate, sums, need; };
@@ -40,6 +40,15 @@ inline CalibrationLayout calibration_layout(int64_t slots, int64_t n_rate, int64
     const int64_t G = (n_bins + n_levels + 3 + 3) / 4;
     return {b.doubles(128), b.doubles(4), b.doubles(want_cdf ? 2 * n_rate : 0), b.doubles(4 * G * slots),
             b.doubles(slots * G * n_blk * 4), G, b.need()};
+}
+
+// The siblings that score under a supplied posterior (vlgp_predictive_cov, vlgp_calibration_cov): the sibling's block, then
+// mu (post_rows, L) | cov (post_rows, L (L + 1) / 2) over the rows of the posterior's set
+struct MomentsLayout { int64_t mu, cov, need; };
+inline MomentsLayout moments_layout(int64_t sibling_need, int64_t post_rows, int64_t L) {
+    BlockLayout b;
+    b.at = sibling_need;
+    return {b.doubles(post_rows * L), b.doubles(post_rows * (L * (L + 1) / 2)), b.need()};
 }
 
 // partials (N, n_blk, 4) | sums (N, 4) | terms (tasks, 4) | row_ell (rows, when wanted) | flags (tasks)
@@ -80,6 +89,13 @@ struct JointLayout { int64_t work, stats, v; SampleLayout s; int64_t need; };
 inline JointLayout joint_layout(int64_t work, int64_t rows, int64_t L, int64_t R, int64_t M, int64_t n_tiles, int64_t K) {
     BlockLayout b;
     return {b.doubles(work), b.doubles(8 * M), b.doubles(rows * L), sample_layout(b, M, L, R, n_tiles, K > 0), b.need()};
+}
+
+// vlgp_joint_posterior: the Newton workspace | stats (M, 8) | cov (rows, L (L + 1) / 2); mu lives in the workspace
+struct JointPosteriorLayout { int64_t work, stats, cov, need; };
+inline JointPosteriorLayout joint_posterior_layout(int64_t work, int64_t rows, int64_t L, int64_t M) {
+    BlockLayout b;
+    return {b.doubles(work), b.doubles(8 * M), b.doubles(rows * (L * (L + 1) / 2)), b.need()};
 }
 
 #ifdef __HIPCC__

@@ -348,7 +348,8 @@ struct Admission { const char* what; unsigned kinds; const char* refusal; };
 int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a);  // (a null: admit() is the caller's)
 int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a);
 extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_calibration, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
-    admit_vlgp_joint_laplace;  // the scoring entry points' rows of the table (eval_api.hip)
+    admit_vlgp_joint_laplace, admit_vlgp_joint_posterior, admit_vlgp_predictive_cov,
+    admit_vlgp_calibration_cov;  // the scoring entry points' rows of the table (eval_api.hip)
 
 // profiling brackets (HIP events on ctx->stream)
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st = nullptr);
@@ -415,6 +416,14 @@ int launch_predictive(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const dou
 // null; d_part: (slots, G, ceil(source rows / 256), 4) doubles of the caller's workspace; d_sums (slots, 4 G)
 int launch_calibration(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const double* d_nodes, int n_bins, int n_levels,
                        const double* d_levels, int max_count, double* d_cdf, double* d_part, double* d_sums);
+// the two above under a supplied posterior of the linear predictor (vlgp_predictive_cov, vlgp_calibration_cov): d_mu
+// (rows of the set, L) and d_cov (rows of the set, L (L + 1) / 2), pair (l, l'), l' <= l, at l (l + 1) / 2 + l', take
+// the place of the set's mu, v with vb = 1
+int launch_predictive_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double* d_nodes, const double* d_mu,
+                          const double* d_cov, double* d_rate, double* d_lpd, double* d_part, double* d_sums);
+int launch_calibration_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double* d_nodes, const double* d_mu,
+                           const double* d_cov, int n_bins, int n_levels, const double* d_levels, int max_count,
+                           double* d_cdf, double* d_part, double* d_sums);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace
@@ -438,12 +447,14 @@ int launch_marginal(vlgp_ctx* ctx, UnitSet& us, int rp, int kc, const double* d_
 int launch_marginal_rows(vlgp_ctx* ctx, UnitSet& us, const char* who, int kc, const double* d_beta, const double* d_c,
                          double* d_part, int tile_rows, const int64_t* d_tile_off, int64_t n_tiles, double* d_logw,
                          double* d_parts);  // its row kernel and finish alone: beta_k and c come from the caller
-// joint Laplace posterior of a plain set (joint.hip).  JointWork: the call's device block cut into its pieces by
+// joint Laplace posterior of a plain set, or of a masked set of one replica (joint.hip).  JointWork: the call's device block cut into its pieces by
 // joint_work_doubles (which returns the doubles needed; W may be null to ask), Dmax the largest stacked dimension of the set.
 // launch_joint_init: the mean-field start; launch_joint_round: one row pass, the step decision and, where the step was
 // accepted, H, its factor and the next direction, W.n_done counting the finished units; launch_joint_finish: stats (M, 8)
-// and mu, v (rows, L) or null; launch_joint_draw: kc <= 64 draws into d_beta (M, L, R, 64), their c into d_c (M, L, 64)
+// and mu (rows, L) with v (rows, L) or cov (rows, L (L + 1) / 2), or null; who: the entry point, for the messages;
+// launch_joint_draw: kc <= 64 draws into d_beta (M, L, R, 64), their c into d_c (M, L, 64)
 struct JointWork {
+    const char* who = "vlgp_joint_laplace";
     double* base = nullptr;
     int Dmax = 0;
     size_t state_bytes = 0;
@@ -454,5 +465,6 @@ struct JointWork {
 int64_t joint_work_doubles(const vlgp_ctx* ctx, const UnitSet& us, int Dmax, JointWork* W);
 int launch_joint_init(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W);
 int launch_joint_round(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_iter, double tol);
-int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, double* d_stats, double* d_mu, double* d_v);
+int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, double* d_stats, double* d_mu, double* d_v,
+                        double* d_cov);
 int launch_joint_draw(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int kc, const double* d_eps, double* d_beta, double* d_c);

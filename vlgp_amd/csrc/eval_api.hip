@@ -1,5 +1,5 @@
-// The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_calibration, vlgp_elbo,
-// vlgp_forecast, vlgp_marginal, vlgp_joint_laplace.  Every one is put together the same way: open the set,
+// The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_calibration and their _cov
+// siblings, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior.  Every one is put together the same way: open the set,
 // check the arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
 #include <algorithm>
 
@@ -42,39 +42,72 @@ extern "C" int vlgp_loglik(vlgp_ctx* ctx, int set, int vb, double* rate, double*
     return cp.finish("vlgp_loglik", "copy-out");
 }
 
+// The _cov siblings of vlgp_predictive and vlgp_calibration: the caller's mu (rows, L) and cov (rows, L (L + 1) / 2) over
+// the rows of the posterior's set go in behind the sibling's block (moments_layout).  given: the call is such a sibling.
+struct Moments { bool given; const double* mu; const double* cov; };
+static int need_moments(vlgp_ctx* ctx, const char* who, const Moments& m) {
+    if (m.given && !m.mu) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs mu", who);
+    if (m.given && !m.cov) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs cov", who);
+    return VLGP_OK;
+}
+static void copy_moments_in(Copies& cp, const CallBlock& blk, const MomentsLayout& o, const Moments& m, int64_t post_rows,
+                            int64_t L) {
+    cp.in(blk.at(o.mu), m.mu, sizeof(double) * (size_t)(post_rows * L));
+    cp.in(blk.at(o.cov), m.cov, sizeof(double) * (size_t)(post_rows * (L * (L + 1) / 2)));
+}
+
 // vlgp_loglik's shapes with a second per-entry output; the waits of a read-only call (no epoch bump): the partials are in
 // the call's own block
-extern "C" int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa,
-                               double* rate, double* lpd, double* sums) {
+static int predictive_call(vlgp_ctx* ctx, const char* who, const Admission& a, int set, int vb, int n_nodes, const double* z,
+                           const double* lwa, const Moments& m, double* rate, double* lpd, double* sums) {
     UnitSet* us = nullptr;
     CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
     if (n_nodes < 1 || n_nodes > 64)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: n_nodes = %d, need 1 <= n_nodes <= 64", n_nodes);
-    if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive needs z, lwa and sums");
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_nodes = %d, need 1 <= n_nodes <= 64", who, n_nodes);
+    if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs z, lwa and sums", who);
+    CHK(need_moments(ctx, who, m));
     RowScore r;
-    CHK(open_row_score(ctx, set, us, admit_vlgp_predictive, rate || lpd, "rate or lpd", &r));
-    if (r.S.slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_predictive: too many (replica, channel) slots");
+    CHK(open_row_score(ctx, set, us, a, rate || lpd, "rate or lpd", &r));
+    if (r.S.slots > 0x7fffffffLL / 4) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (replica, channel) slots", who);
     const PredictiveLayout o = predictive_layout(r.S.slots, r.S.n_rate, r.n_blk, rate != nullptr, lpd != nullptr);
+    const MomentsLayout om = moments_layout(o.need, m.given ? us->rows : 0, ctx->L);
     CallBlock blk(ctx);
-    HIPCHK(ctx, blk.alloc(o.need));
+    HIPCHK(ctx, blk.alloc(om.need));
     Copies cp(ctx);
     cp.in(blk.at(o.nodes), z, sizeof(double) * (size_t)n_nodes);
     cp.in(blk.at(o.nodes) + n_nodes, lwa, sizeof(double) * (size_t)n_nodes);
+    if (m.given) copy_moments_in(cp, blk, om, m, us->rows, ctx->L);
     if (r.by_row) cp.nan_fill(blk.at(o.rate), o.sums - o.rate);  // (rate and lpd lie side by side)
-    CHK(cp.status("vlgp_predictive", "copy-in"));
-    CHK(launch_predictive(ctx, *us, vb, n_nodes, blk.at(o.nodes), blk.opt(rate, o.rate), blk.opt(lpd, o.lpd), blk.at(o.part),
-                          blk.at(o.sums)));
+    CHK(cp.status(who, "copy-in"));
+    if (m.given)
+        CHK(launch_predictive_cov(ctx, *us, n_nodes, blk.at(o.nodes), blk.at(om.mu), blk.at(om.cov), blk.opt(rate, o.rate),
+                                  blk.opt(lpd, o.lpd), blk.at(o.part), blk.at(o.sums)));
+    else
+        CHK(launch_predictive(ctx, *us, vb, n_nodes, blk.at(o.nodes), blk.opt(rate, o.rate), blk.opt(lpd, o.lpd), blk.at(o.part),
+                              blk.at(o.sums)));
     cp.out(sums, blk.at(o.sums), sizeof(double) * 4 * (size_t)r.S.slots);
     cp.out(rate, blk.at(o.rate), sizeof(double) * (size_t)r.S.n_rate);
     cp.out(lpd, blk.at(o.lpd), sizeof(double) * (size_t)r.S.n_rate);
-    return cp.finish("vlgp_predictive", "copy-out");
+    return cp.finish(who, "copy-out");
+}
+
+extern "C" int vlgp_predictive(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa,
+                               double* rate, double* lpd, double* sums) {
+    return predictive_call(ctx, "vlgp_predictive", admit_vlgp_predictive, set, vb, n_nodes, z, lwa, {false, nullptr, nullptr},
+                           rate, lpd, sums);
+}
+
+extern "C" int vlgp_predictive_cov(vlgp_ctx* ctx, int set, int n_nodes, const double* z, const double* lwa, const double* mu,
+                                   const double* cov, double* rate, double* lpd, double* sums) {
+    return predictive_call(ctx, "vlgp_predictive_cov", admit_vlgp_predictive_cov, set, 1, n_nodes, z, lwa, {true, mu, cov},
+                           rate, lpd, sums);
 }
 
 // vlgp_predictive's frame with W columns per slot: the device sums are (slots, 4 G) for the G groups of four that
 // launch_sums_finish adds, and the first W of every row go out
-extern "C" int vlgp_calibration(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, int n_bins,
-                                int n_levels, const double* levels, int max_count, double* cdf, double* sums) {
-    static const char* who = "vlgp_calibration";
+static int calibration_call(vlgp_ctx* ctx, const char* who, const Admission& a, int set, int vb, int n_nodes, const double* z,
+                            const double* lwa, const Moments& m, int n_bins, int n_levels, const double* levels, int max_count,
+                            double* cdf, double* sums) {
     UnitSet* us = nullptr;
     CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
     if (n_nodes < 1 || n_nodes > 64) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_nodes = %d, need 1 <= n_nodes <= 64", who, n_nodes);
@@ -84,27 +117,47 @@ extern "C" int vlgp_calibration(vlgp_ctx* ctx, int set, int vb, int n_nodes, con
         return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: max_count = %d, need 1 <= max_count <= 65536", who, max_count);
     if (!z || !lwa || !sums) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs z, lwa and sums", who);
     if (n_levels > 0 && !levels) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: n_levels = %d needs levels", who, n_levels);
+    CHK(need_moments(ctx, who, m));
     for (int c = 0; c < n_levels; ++c)
         if (!(levels[c] > 0.0 && levels[c] < 1.0))
             return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: levels[%d] = %g, need 0 < level < 1", who, c, levels[c]);
     RowScore r;
-    CHK(open_row_score(ctx, set, us, admit_vlgp_calibration, cdf != nullptr, "cdf", &r));
+    CHK(open_row_score(ctx, set, us, a, cdf != nullptr, "cdf", &r));
     const int W = n_bins + n_levels + 3;
     const CalibrationLayout o = calibration_layout(r.S.slots, r.S.n_rate, r.n_blk, n_bins, n_levels, cdf != nullptr);
     if (r.S.slots > 0x7fffffffLL / (4 * o.groups)) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (replica, channel) slots", who);
+    const MomentsLayout om = moments_layout(o.need, m.given ? us->rows : 0, ctx->L);
     CallBlock blk(ctx);
-    HIPCHK(ctx, blk.alloc(o.need));
+    HIPCHK(ctx, blk.alloc(om.need));
     Copies cp(ctx);
     cp.in(blk.at(o.nodes), z, sizeof(double) * (size_t)n_nodes);
     cp.in(blk.at(o.nodes) + n_nodes, lwa, sizeof(double) * (size_t)n_nodes);
     if (n_levels) cp.in(blk.at(o.levels), levels, sizeof(double) * (size_t)n_levels);
+    if (m.given) copy_moments_in(cp, blk, om, m, us->rows, ctx->L);
     if (r.by_row) cp.nan_fill(blk.at(o.cdf), o.sums - o.cdf);
     CHK(cp.status(who, "copy-in"));
-    CHK(launch_calibration(ctx, *us, vb, n_nodes, blk.at(o.nodes), n_bins, n_levels, blk.at(o.levels), max_count,
-                           blk.opt(cdf, o.cdf), blk.at(o.part), blk.at(o.sums)));
+    if (m.given)
+        CHK(launch_calibration_cov(ctx, *us, n_nodes, blk.at(o.nodes), blk.at(om.mu), blk.at(om.cov), n_bins, n_levels,
+                                   blk.at(o.levels), max_count, blk.opt(cdf, o.cdf), blk.at(o.part), blk.at(o.sums)));
+    else
+        CHK(launch_calibration(ctx, *us, vb, n_nodes, blk.at(o.nodes), n_bins, n_levels, blk.at(o.levels), max_count,
+                               blk.opt(cdf, o.cdf), blk.at(o.part), blk.at(o.sums)));
     cp.out2d(sums, (size_t)W, blk.at(o.sums), (size_t)(4 * o.groups), (size_t)W, (size_t)r.S.slots);
     cp.out(cdf, blk.at(o.cdf), sizeof(double) * 2 * (size_t)r.S.n_rate);
     return cp.finish(who, "copy-out");
+}
+
+extern "C" int vlgp_calibration(vlgp_ctx* ctx, int set, int vb, int n_nodes, const double* z, const double* lwa, int n_bins,
+                                int n_levels, const double* levels, int max_count, double* cdf, double* sums) {
+    return calibration_call(ctx, "vlgp_calibration", admit_vlgp_calibration, set, vb, n_nodes, z, lwa, {false, nullptr, nullptr},
+                            n_bins, n_levels, levels, max_count, cdf, sums);
+}
+
+extern "C" int vlgp_calibration_cov(vlgp_ctx* ctx, int set, int n_nodes, const double* z, const double* lwa, const double* mu,
+                                    const double* cov, int n_bins, int n_levels, const double* levels, int max_count,
+                                    double* cdf, double* sums) {
+    return calibration_call(ctx, "vlgp_calibration_cov", admit_vlgp_calibration_cov, set, 1, n_nodes, z, lwa, {true, mu, cov},
+                            n_bins, n_levels, levels, max_count, cdf, sums);
 }
 
 // ---- the scores of a posterior (elbo, forecast, marginal, joint Laplace) --------------------------------------------------
@@ -116,7 +169,8 @@ struct Posterior { UnitSet* us = nullptr; int64_t tasks = 0; int rp = 1; };
 static int open_posterior(vlgp_ctx* ctx, int set, const Admission& a, int* n_failed, Posterior* p) {
     CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &p->us, &a));
     const UnitSet& us = *p->us;
-    if (!us.x_ones) CHK(vlgp_refresh_xb(ctx, *p->us));
+    UnitSet& rows_of = vlgp_rows_owner(ctx, *p->us);  // (the set itself, or the source of a masked set of one replica)
+    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
     CHK(vlgp_bind_priors(ctx, *p->us));
     p->tasks = (int64_t)us.M * ctx->L;
     if (p->tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (unit, latent) pairs", a.what);
@@ -264,14 +318,55 @@ extern "C" int vlgp_marginal(vlgp_ctx* ctx, int set, int vb, int n_samples, cons
     return count_flags(cp, who, blk.ints(o.flag), p.tasks, n_failed);
 }
 
+// ---- what vlgp_joint_laplace and vlgp_joint_posterior share ----------------------------------------------------------------
+// the arguments of the Newton iteration
+static int joint_args(vlgp_ctx* ctx, const char* who, int max_iter, double tol) {
+    if (max_iter < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: max_iter = %d, need >= 1", who, max_iter);
+    if (!(tol > 0.0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: tol = %g, need > 0", who, tol);
+    return VLGP_OK;
+}
+
+// *Dmax: the largest D = sum_l r_l among the units
+static int joint_dmax(vlgp_ctx* ctx, const char* who, const UnitSet& us, int* Dmax) {
+    *Dmax = 1;
+    for (int m = 0; m < us.M; ++m) {  // D = sum_l r_l of the unit's length
+        const Prior& pr = ctx->priors.find((int)(us.off[m + 1] - us.off[m]))->second;  // (vlgp_bind_priors found every length)
+        int D = 0;
+        for (int l = 0; l < ctx->L; ++l) D += pr.rl[l];
+        if (D > 512)
+            return vlgp_fail(ctx, VLGP_ERR_STATE, "%s: unit %d has D = %d weights, at most 512 are supported", who, m, D);
+        *Dmax = std::max(*Dmax, D);
+    }
+    return VLGP_OK;
+}
+
+// the start and the Newton rounds
+static int joint_newton(vlgp_ctx* ctx, Copies& cp, const Posterior& p, const JointWork& W, int max_iter, double tol) {
+    CHK(launch_joint_init(ctx, *p.us, p.rp, W));
+    // every round finishes a unit, factors it (at most max_iter times) or halves its step (at most 30 times per factor)
+    for (int64_t round = 0, done = 0; done < p.us->M && round <= 32 * ((int64_t)max_iter + 1); ++round) {
+        CHK(launch_joint_round(ctx, *p.us, W, max_iter, tol));
+        int nd = 0;
+        cp.out(&nd, W.n_done, sizeof(int));
+        CHK(cp.finish(W.who, "a Newton round"));
+        done = nd;
+    }
+    return VLGP_OK;
+}
+
+// (NaN laplace: the unit failed)
+static void count_failed_units(const double* stats, int M, int* n_failed) {
+    if (n_failed)
+        for (int m = 0; m < M; ++m) *n_failed += stats[8 * (size_t)m] != stats[8 * (size_t)m] ? 1 : 0;
+}
+
 extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_samples, const double* eps,
                                   double* beta, double* stats, double* mu, double* v, double* log_w, double* parts,
                                   int* n_failed) {
     static const char* who = "vlgp_joint_laplace";
     Posterior p;
     CHK(open_posterior(ctx, set, admit_vlgp_joint_laplace, n_failed, &p));
-    if (max_iter < 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: max_iter = %d, need >= 1", max_iter);
-    if (!(tol > 0.0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: tol = %g, need > 0", tol);
+    CHK(joint_args(ctx, who, max_iter, tol));
     if (n_samples < 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples = %d, need >= 0", n_samples);
     if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace needs stats");
     if (n_samples > 0 && (!eps || !log_w)) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: n_samples > 0 needs eps and log_w");
@@ -279,14 +374,7 @@ extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double t
     const int L = ctx->L, R = ctx->R, M = us->M, tile_rows = marginal_tile_rows(L);
     const int64_t K = n_samples, rows = us->rows;
     int Dmax = 1;
-    for (int m = 0; m < M; ++m) {  // D = sum_l r_l of the unit's length
-        const Prior& pr = ctx->priors.find((int)(us->off[m + 1] - us->off[m]))->second;  // (vlgp_bind_priors found every length)
-        int D = 0;
-        for (int l = 0; l < L; ++l) D += pr.rl[l];
-        if (D > 512)
-            return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_joint_laplace: unit %d has D = %d weights, at most 512 are supported", m, D);
-        Dmax = std::max(Dmax, D);
-    }
+    CHK(joint_dmax(ctx, who, *us, &Dmax));
     const std::vector<int64_t> tile_off = tile_table(*us, tile_rows);
     const int64_t n_tiles = tile_off[(size_t)M];
     const JointLayout o = joint_layout(joint_work_doubles(ctx, *us, Dmax, nullptr), rows, L, R, M, n_tiles, K);
@@ -297,28 +385,52 @@ extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double t
     (void)joint_work_doubles(ctx, *us, Dmax, &W);
     int64_t* d_tab = blk.i64(o.s.tab);
     Copies cp(ctx);
-    CHK(launch_joint_init(ctx, *us, p.rp, W));
-    // every round finishes a unit, factors it (at most max_iter times) or halves its step (at most 30 times per factor)
-    for (int64_t round = 0, done = 0; done < M && round <= 32 * ((int64_t)max_iter + 1); ++round) {
-        CHK(launch_joint_round(ctx, *us, W, max_iter, tol));
-        int nd = 0;
-        cp.out(&nd, W.n_done, sizeof(int));
-        CHK(cp.finish("vlgp_joint_laplace:", "a Newton round"));
-        done = nd;
-    }
+    CHK(joint_newton(ctx, cp, p, W, max_iter, tol));
     const bool path = mu || v;
-    CHK(launch_joint_finish(ctx, *us, p.rp, W, blk.at(o.stats), path ? W.g : nullptr, blk.opt(path, o.v)));
+    CHK(launch_joint_finish(ctx, *us, p.rp, W, blk.at(o.stats), path ? W.g : nullptr, blk.opt(path, o.v), nullptr));
     cp.out(stats, blk.at(o.stats), sizeof(double) * 8 * (size_t)M);
     cp.out(beta, W.beta, sizeof(double) * (size_t)(p.tasks * R));
     cp.out(mu, W.g, sizeof(double) * (size_t)(rows * L));
     cp.out(v, blk.at(o.v), sizeof(double) * (size_t)(rows * L));
     if (K) cp.in(d_tab, tile_off.data(), sizeof(int64_t) * tile_off.size());
     CHK(cp.finish(who, "copy-out"));
-    if (n_failed)
-        for (int m = 0; m < M; ++m) *n_failed += stats[8 * (size_t)m] != stats[8 * (size_t)m] ? 1 : 0;  // (NaN: the unit failed)
+    count_failed_units(stats, M, n_failed);
     return sample_stage(cp, who, blk, o.s, p.tasks * R, M, K, eps, log_w, parts, [&](int kc) {
         CHK(launch_joint_draw(ctx, *us, W, kc, blk.at(o.s.eps), blk.at(o.s.beta), blk.at(o.s.c)));
         return launch_marginal_rows(ctx, *us, who, kc, blk.at(o.s.beta), blk.at(o.s.c), blk.at(o.s.part), tile_rows, d_tab,
                                     n_tiles, blk.at(o.s.lw), blk.at(o.s.parts));
     });
+}
+
+// vlgp_joint_laplace's mode without draws, on a plain set or a masked set of one replica, with the covariance of every row
+extern "C" int vlgp_joint_posterior(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats, double* mu,
+                                    double* cov, int* n_failed) {
+    static const char* who = "vlgp_joint_posterior";
+    Posterior p;
+    CHK(open_posterior(ctx, set, admit_vlgp_joint_posterior, n_failed, &p));
+    UnitSet* us = p.us;
+    int Dmax = 1;
+    CHK(joint_args(ctx, who, max_iter, tol));
+    if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_posterior needs stats");
+    CHK(joint_dmax(ctx, who, *us, &Dmax));
+    const int L = ctx->L, M = us->M;
+    const int64_t rows = us->rows, npair = (int64_t)L * (L + 1) / 2;
+    const JointPosteriorLayout o = joint_posterior_layout(joint_work_doubles(ctx, *us, Dmax, nullptr), rows, L, M);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    JointWork W;
+    W.who = who;
+    W.base = blk.at(o.work);
+    (void)joint_work_doubles(ctx, *us, Dmax, &W);
+    Copies cp(ctx);
+    CHK(joint_newton(ctx, cp, p, W, max_iter, tol));
+    const bool path = mu || cov;
+    CHK(launch_joint_finish(ctx, *us, p.rp, W, blk.at(o.stats), path ? W.g : nullptr, nullptr, blk.opt(path, o.cov)));
+    cp.out(stats, blk.at(o.stats), sizeof(double) * 8 * (size_t)M);
+    cp.out(beta, W.beta, sizeof(double) * (size_t)(p.tasks * ctx->R));
+    cp.out(mu, W.g, sizeof(double) * (size_t)(rows * L));
+    cp.out(cov, blk.at(o.cov), sizeof(double) * (size_t)(rows * npair));
+    CHK(cp.finish(who, "copy-out"));
+    count_failed_units(stats, M, n_failed);
+    return VLGP_OK;
 }

@@ -1,6 +1,8 @@
 // Joint Laplace posterior of a unit set (vlgp_joint_laplace): the mode of the posterior over ALL prior weights of a unit,
 // found by a damped Newton iteration on the device, the Laplace evidence, latent variances that include the coupling
-// between latents, and joint Gaussian draws for the importance weights of marginal.hip.
+// between latents, and joint Gaussian draws for the importance weights of marginal.hip.  vlgp_joint_posterior is the same
+// iteration without draws, also on a masked set of one replica, with the L x L covariance of the latents of every row,
+// cov[t; l, l'] = G_l[t, :] (H^-1)_ll' G_l'[t, :]', in place of v.
 //
 // For one unit of T rows, G_l (T x r_l) the compact prior factor of latent l as task_view hands it out, the stacked index
 // I = (l, i) latent-major, D = sum_l r_l <= 512 (vlgp_joint_laplace refuses more: the factor's panel must fit LDS):
@@ -11,7 +13,9 @@
 //   grad_l f = beta_l - G_l' g[:, l],                    g[t, l] = sum_n a[l, n] res[t, n]
 //   H[(l, i), (l', j)] = delta + sum_t G_l[t, i] c[t, l, l'] G_l'[t, j],   c[t, l, l'] = sum_n a[l, n] a[l', n] cur[t, n]
 //   H = Lc Lc'
-// Start: the mean-field centres m_l = H_l^-1 G_l'(g + w o mu)_l of task_weight_posterior (the caller's z, vb = 0).
+// Start: the mean-field centres m_l = H_l^-1 G_l'(g + w o mu)_l of task_weight_posterior (the caller's z, vb = 0); a
+// masked set (vlgp_joint_posterior) starts at beta = 0: forecast_rows' z reads every y, and the mode does not depend on
+// the start.
 // Iteration, per unit: y = Lc^-1 grad f, decrement = |y|^2; stop (converged) when decrement <= tol, stop (not converged)
 // after max_iter factorisations; else d = Lc^-T y and the trial point beta - s d, s = 1.  The trial is accepted when
 //   f(beta - s d) <= f(beta) - JT_ARMIJO s decrement + JT_SLACK (1/2 |beta - s d|^2 + sum |ll terms of the rows|),
@@ -24,7 +28,9 @@
 // Kernels (DESIGN 4.11 has the reasons):
 //   joint_init     one wave per (unit, latent): m_l into beta (marginal_task's first half).
 //   joint_rows     one lane per row: x, the row's ll and sum |terms|, res and cur channel-major into a workspace, then g
-//                  and the packed c from that workspace.  Rows of finished units are skipped.
+//                  and the packed c from that workspace.  Rows of finished units are skipped.  joint_rows_masked is the
+//                  same body (joint_row<MASKED>) with the mask words of the row, one replica, so the mask row is the
+//                  row: a held-out entry adds nothing to ll and sum |terms|, its res = cur = 0, and y is not read there.
 //   joint_decide   one workgroup per unit: f of the trial point, accept or halve.
 //   joint_assemble one workgroup of 256 per (unit, pair of latents l' <= l): the r_l x r_l' block of H, rows of G_l o c and
 //                  G_l' staged 32 at a time in LDS, a 4 x 4 register tile per thread.  H is a (D + 1) x (D + 1) row-major
@@ -37,6 +43,12 @@
 //                  the decision above and, by one wave, the back substitution for d.
 //   joint_var      one wave per (unit, latent): lane j the column (l, j) of H^-1 by two substitutions in a per-lane global
 //                  vector, the r x r block (H^-1)_ll into LDS, then lane = row: v and mu.
+//   joint_cov      vlgp_joint_posterior's joint_var, one wave per (unit, latent l): lane j the WHOLE column (l, j) of
+//                  H^-1 -- the forward substitution still starts at the latent's first index, the back substitution runs
+//                  down to index 0 -- in the same per-lane global vector; then for every l' <= l the r_l' x r_l block
+//                  (H^-1)_l'l into LDS, and lane = row: cov[t; l, l'] = G_l'[t, :] (H^-1)_l'l G_l[t, :]' at pair
+//                  l (l + 1) / 2 + l', summed as joint_var sums v (over i of G_l' in order, each term a chain over j), so
+//                  the pair (l, l) is joint_var's v bit for bit; mu as there.
 //   joint_stats    one workgroup per unit: the sums of the final row pass into stats.
 //   joint_draw     one wave per unit, lane k one sample: the back substitution against Lc' in a per-lane global vector.
 // A pivot that is not positive and finite marks the unit failed: its stats[0 .. 4], mu, v and c are NaN.  Every sum has a
@@ -150,10 +162,12 @@ __global__ void __launch_bounds__(64) joint_init(JointInitArgs A) {
 }
 
 // ---- the row pass ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) joint_rows(JointArgs A) {
+template <bool MASKED>
+__device__ __forceinline__ void joint_row(const JointArgs& A, const unsigned long long* mask, int nw) {
     const RowModel& M = A.m;
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= M.rows) return;
+    const unsigned long long* mk = MASKED ? mask + row * nw : nullptr;  // (one replica: the row of the mask is the row)
     const int L = M.L, N = M.N;
     int u = 0;
     for (int hi = A.P.M; hi - u > 1;) {  // off[u] <= row < off[u + 1]
@@ -179,6 +193,11 @@ __global__ void __launch_bounds__(256) joint_rows(JointArgs A) {
     for (int n = 0; n < N; ++n) {
         double eta = M.xb ? M.xb[row * N + n] : M.b[n];
         for (int l = 0; l < L; ++l) eta = fma(A.x[row * L + l], M.a[l * N + n], eta);
+        if (MASKED && ((mk[n >> 6] >> (n & 63)) & 1ull)) {  // held out: no term, and y is not read
+            A.res[(int64_t)n * M.rows + row] = 0.0;
+            A.cur[(int64_t)n * M.rows + row] = 0.0;
+            continue;
+        }
         const double yv = M.y[row * N + n];
         double rs, cu;
         if (M.gauss[n]) {
@@ -211,6 +230,11 @@ __global__ void __launch_bounds__(256) joint_rows(JointArgs A) {
             A.c[row * A.npair + l * (l + 1) / 2 + l2] = c;
         }
     }
+}
+
+__global__ void __launch_bounds__(256) joint_rows(JointArgs A) { joint_row<false>(A, nullptr, 0); }
+__global__ void __launch_bounds__(256) joint_rows_masked(JointArgs A, const unsigned long long* mask, int nw) {
+    joint_row<true>(A, mask, nw);
 }
 
 // ---- accept or halve ------------------------------------------------------------------------------------------------
@@ -511,6 +535,80 @@ __global__ void __launch_bounds__(64) joint_var(JointOutArgs O) {
     }
 }
 
+// joint_var with the cross blocks: cov (rows, npair), pair (l, l') at l (l + 1) / 2 + l'
+__global__ void __launch_bounds__(64) joint_cov(JointOutArgs O, double* cov) {
+    extern __shared__ double lds[];  // S (rp x rs) | tile of G_l (64 x rs) | tile of G_l' (64 x rs)
+    const JointArgs& A = O.J;
+    const int lane = threadIdx.x, task = blockIdx.x, L = A.P.L;
+    if (task >= A.P.M * L) return;
+    const TaskView t = task_view(A.P, task);
+    const int r = unit_rank(A.P, t.p, t.l, A.R);
+    const int* si = A.si + (int64_t)t.u * JT_ST;
+    int D = 0, d0 = 0, rmax = 0;
+    for (int l = 0; l < L; ++l) {
+        if (l == t.l) d0 = D;
+        const int rl = unit_rank(A.P, t.p, l, A.R);
+        rmax = max(rmax, rl);
+        D += rl;
+    }
+    const double nan = __builtin_nan("");
+    const int pair0 = t.l * (t.l + 1) / 2;
+    if (si[JI_FAILED] || r < 1 || rmax > O.rp || D > A.Dmax) {
+        for (int tt = lane; tt < t.T; tt += 64) {
+            O.mu[(t.r0 + tt) * L + t.l] = nan;
+            for (int l2 = 0; l2 <= t.l; ++l2) cov[(t.r0 + tt) * A.npair + pair0 + l2] = nan;
+        }
+        return;
+    }
+    const int ld = D + 1, rs = O.rs;
+    const double* __restrict__ buf = A.H + (int64_t)t.u * (A.Dmax + 1) * (A.Dmax + 1);
+    double* z = A.zw + (int64_t)task * A.Dmax * 64 + lane;  // entry I at z[I * 64]
+    const int j = lane < r ? lane : 0;
+    // y = Lc^-1 e_(d0 + j): zero above d0
+    for (int I = d0; I < D; ++I) {
+        double s = I == d0 + j ? 1.0 : 0.0;
+        for (int Q = d0; Q < I; ++Q) s = fma(-buf[(int64_t)Q * ld + I], z[(int64_t)Q * 64], s);
+        z[(int64_t)I * 64] = s / buf[(int64_t)I * ld + I];
+    }
+    // Lc^-T y, down to 0: the whole column (the entries at and behind d0 are joint_var's)
+    for (int I = D - 1; I >= 0; --I) {
+        const double* __restrict__ row = buf + (int64_t)I * ld;
+        double s = I >= d0 ? z[(int64_t)I * 64] : 0.0;  // (y is zero above d0 and was not stored there)
+        for (int Q = I + 1; Q < D; ++Q) s = fma(-row[Q], z[(int64_t)Q * 64], s);
+        z[(int64_t)I * 64] = s / row[I];
+    }
+    double* S = lds;
+    double* tile = S + O.rp * rs;
+    double* tile2 = tile + EW_TILE * rs;
+    int d2 = 0;
+    for (int l2 = 0; l2 <= t.l; ++l2) {
+        const int r2 = unit_rank(A.P, t.p, l2, A.R);
+        const double* __restrict__ G2 = A.P.prior_base[t.p] + A.P.prior_goff[t.p * L + l2];
+        if (lane < r)
+            for (int i = 0; i < r2; ++i) S[i * rs + lane] = z[(int64_t)(d2 + i) * 64];  // (H^-1)[(l2, i), (l, lane)]
+        wave_sync();
+        for (int t0 = 0; t0 < t.T; t0 += EW_TILE) {
+            const int nt = min(EW_TILE, t.T - t0);
+            stage_rows(t.G, r, r, rs, t0, nt, tile, lane);
+            stage_rows(G2, r2, r2, rs, t0, nt, tile2, lane);
+            wave_sync();
+            if (lane < nt) {
+                const double* xr = tile + lane * rs;
+                const double* x2 = tile2 + lane * rs;
+                double cv = 0.0;
+                for (int i = 0; i < r2; ++i) cv = fma(x2[i], tile_row_dot(S + i * rs, xr, r), cv);
+                cov[(t.r0 + t0 + lane) * A.npair + pair0 + l2] = cv;
+                if (l2 == t.l) {
+                    const int64_t at = (t.r0 + t0 + lane) * L + t.l;
+                    O.mu[at] = A.x[at];
+                }
+            }
+            wave_sync();  // (the tiles and S are overwritten next)
+        }
+        d2 += r2;
+    }
+}
+
 __global__ void __launch_bounds__(256) joint_stats(JointOutArgs O) {
     __shared__ double red[4][3];
     const JointArgs& A = O.J;
@@ -589,7 +687,7 @@ __global__ void __launch_bounds__(64) joint_draw(JointOutArgs O) {
 
 JointArgs fill_joint(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_iter, double tol, int final) {
     JointArgs A;
-    A.m = fill_row_model(ctx, us, us, 0);
+    A.m = fill_row_model(ctx, vlgp_rows_owner(ctx, us), us, 0);  // (a masked set of one replica: the source's y, xb)
     A.P = fill_task_prior(ctx, us);
     A.R = ctx->R; A.Dmax = W.Dmax; A.npair = ctx->L * (ctx->L + 1) / 2; A.max_iter = max_iter; A.final = final;
     A.tol = tol;
@@ -621,20 +719,34 @@ int64_t joint_work_doubles(const vlgp_ctx* ctx, const UnitSet& us, int Dmax, Joi
     return o;
 }
 
-// the start: z = g + w o mu (vb = 0) into W.g, the mean-field centres into W.beta, the per-unit state zeroed
+// the start: z = g + w o mu (vb = 0) into W.g, the mean-field centres into W.beta, the per-unit state zeroed; a masked
+// set starts at beta = 0
 int launch_joint_init(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W) {
     if (rp < 1 || rp > VLGP_WAVE || rp > ctx->R)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: effective rank %d outside [1, %d]", rp, std::min(VLGP_WAVE, ctx->R));
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: effective rank %d outside [1, %d]", W.who, rp, std::min(VLGP_WAVE, ctx->R));
     HIPCHK(ctx, hipMemsetAsync(W.sd, 0, W.state_bytes, ctx->stream));  // sd | si | n_done
+    if (us.is(SET_BY_ROW)) {
+        HIPCHK(ctx, hipMemsetAsync(W.beta, 0, sizeof(double) * (size_t)(W.sd - W.beta), ctx->stream));  // beta | dvec
+        return VLGP_OK;
+    }
     CHK(launch_forecast_z(ctx, us, 0, W.g));
     JointInitArgs K;
     K.P = fill_task_prior(ctx, us);
     K.R = ctx->R; K.rp = rp; K.rs = rp | 1;
     K.w = us.w; K.z = W.g; K.beta = W.beta; K.dvec = W.dvec;
     const size_t lds = sizeof(double) * (size_t)joint_wave_lds_doubles(K.rp, K.rs);
-    if ((int64_t)lds > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: rank %d needs %zu bytes of LDS", rp, lds);
+    if ((int64_t)lds > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: rank %d needs %zu bytes of LDS", W.who, rp, lds);
     if (lds > 64 * 1024) CHK(vlgp_raise_lds(ctx, (const void*)joint_init, ctx->lds_max));
     hipLaunchKernelGGL(joint_init, dim3((unsigned)(us.M * ctx->L)), dim3(64), lds, ctx->stream, K);
+    HIPCHK(ctx, hipGetLastError());
+    return VLGP_OK;
+}
+
+// the row pass of a plain set or of a masked set of one replica
+static int launch_joint_rows(vlgp_ctx* ctx, UnitSet& us, const JointArgs& A) {
+    const dim3 grid((unsigned)((us.rows + 255) / 256));
+    if (us.is(SET_BY_ROW)) hipLaunchKernelGGL(joint_rows_masked, grid, dim3(256), 0, ctx->stream, A, us.rep.d_mask, us.rep.nw);
+    else hipLaunchKernelGGL(joint_rows, grid, dim3(256), 0, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
 }
@@ -645,10 +757,9 @@ int launch_joint_round(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_i
     const JointArgs A = fill_joint(ctx, us, W, max_iter, tol, 0);
     const size_t lds = sizeof(double) * (size_t)joint_factor_lds_doubles(W.Dmax);
     const int ceiling = ctx->lds_max - JT_STATIC_LDS;  // (the kernel's own __shared__ variables count against the same limit)
-    if ((int64_t)lds > ceiling) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: D = %d needs %zu bytes of LDS", W.Dmax, lds);
+    if ((int64_t)lds > ceiling) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: D = %d needs %zu bytes of LDS", W.who, W.Dmax, lds);
     if (lds > 64 * 1024) CHK(vlgp_raise_lds(ctx, (const void*)joint_factor, ceiling));
-    hipLaunchKernelGGL(joint_rows, dim3((unsigned)((us.rows + 255) / 256)), dim3(256), 0, ctx->stream, A);
-    HIPCHK(ctx, hipGetLastError());
+    CHK(launch_joint_rows(ctx, us, A));
     hipLaunchKernelGGL(joint_decide, dim3((unsigned)us.M), dim3(256), 0, ctx->stream, A);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(joint_assemble, dim3((unsigned)A.npair, (unsigned)us.M), dim3(256), 0, ctx->stream, A);
@@ -658,21 +769,25 @@ int launch_joint_round(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_i
     return VLGP_OK;
 }
 
-// after the last round: the row pass at beta itself, then stats (M, 8) and, where asked for, mu and v (rows, L)
-int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, double* d_stats, double* d_mu, double* d_v) {
+// after the last round: the row pass at beta itself, then stats (M, 8) and, where asked for, mu (rows, L) with either v
+// (rows, L: joint_var) or cov (rows, L (L + 1) / 2: joint_cov)
+int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, double* d_stats, double* d_mu, double* d_v,
+                        double* d_cov) {
     JointOutArgs O = {};
     O.J = fill_joint(ctx, us, W, 1, 0.0, 1);
     O.rp = rp; O.rs = rp | 1;
     O.stats = d_stats; O.mu = d_mu; O.v = d_v;
-    hipLaunchKernelGGL(joint_rows, dim3((unsigned)((us.rows + 255) / 256)), dim3(256), 0, ctx->stream, O.J);
-    HIPCHK(ctx, hipGetLastError());
+    CHK(launch_joint_rows(ctx, us, O.J));
     hipLaunchKernelGGL(joint_stats, dim3((unsigned)us.M), dim3(256), 0, ctx->stream, O);
     HIPCHK(ctx, hipGetLastError());
-    if (d_mu && d_v) {
-        const size_t lds = sizeof(double) * (size_t)(O.rp * O.rs + EW_TILE * O.rs);
-        if ((int64_t)lds > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_laplace: rank %d needs %zu bytes of LDS", rp, lds);
-        if (lds > 64 * 1024) CHK(vlgp_raise_lds(ctx, (const void*)joint_var, ctx->lds_max));
-        hipLaunchKernelGGL(joint_var, dim3((unsigned)(us.M * ctx->L)), dim3(64), lds, ctx->stream, O);
+    if (d_mu && (d_v || d_cov)) {
+        const size_t lds = sizeof(double) * (size_t)(O.rp * O.rs + (d_cov ? 2 : 1) * EW_TILE * O.rs);
+        const void* fn = d_cov ? (const void*)joint_cov : (const void*)joint_var;
+        if ((int64_t)lds > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: rank %d needs %zu bytes of LDS", W.who, rp, lds);
+        if (lds > 64 * 1024) CHK(vlgp_raise_lds(ctx, fn, ctx->lds_max));
+        const dim3 grid((unsigned)(us.M * ctx->L));
+        if (d_cov) hipLaunchKernelGGL(joint_cov, grid, dim3(64), lds, ctx->stream, O, d_cov);
+        else hipLaunchKernelGGL(joint_var, grid, dim3(64), lds, ctx->stream, O);
         HIPCHK(ctx, hipGetLastError());
     }
     return VLGP_OK;

@@ -18,10 +18,32 @@
 // sit in LDS and every lane walks them in order (wave-uniform addresses: broadcast reads).  The log-sum-exp is online -- a
 // running maximum, the sum rescaled when the maximum moves -- so a term costs two exponentials and nothing is indexed
 // dynamically in registers.  The entries of the three forms of set are walked by row_scores (row_walk.h); block_sums4 and
-// launch_sums_finish add in a fixed order: no atomics, the same bits on every run.
+// launch_sums_finish add in a fixed order: no atomics, the same bits on every run.  vlgp_predictive_cov is the same entry
+// with m and s2 from a supplied mean and covariance of the latents (CovMoments, row_walk.h) and vb = 1.
 #include "pred_entry.h"  // the node tables in LDS and poisson_lognormal, shared with calibrate.hip
 
 namespace {
+
+// one entry under the moments of `src` (row_walk.h).  A checked source whose m or s2 is not finite: lpd and rate are NaN,
+// in the entry's outputs and in its sums; y and lgamma(y + 1) or y^2 stay.
+template <class Src, class Emit>
+__device__ __forceinline__ void pred_entry(const Src& src, const RowModel& M, const Nodes& q, const NodeTables& t, double* rate,
+                                           double* lpd, int64_t row, int64_t mrow, int n, bool live, int64_t at, Emit emit) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (live) {
+        const EntryMoments e = src.moments(M, row, mrow, n);
+        if (M.gauss[n]) {
+            gauss_sums(e.y, e.m, M.noise[n] + e.s2, s);
+        } else {
+            poisson_sums_at(e.y, src.rate_arg(M, mrow, n, e), s);
+            s[0] = e.s2 < 1e-30 ? poisson_ll(s) : poisson_lognormal(e.y, e.m, e.s2, q.n, t.z, t.lwa) - s[3];
+        }
+        if (Src::checked && !moments_finite(e)) s[0] = s[2] = NAN;
+        if (rate) rate[at] = s[2];
+        if (lpd) lpd[at] = s[0];
+    }
+    emit(s);
+}
 
 struct PredScorer {
     Nodes q;
@@ -33,19 +55,23 @@ struct PredScorer {
     template <class Emit>
     __device__ __forceinline__ void entry(const RowModel& M, const Lds& t, int64_t row, int64_t mrow, int n, bool live,
                                           int64_t at, Emit emit) const {
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            const EntryMoments e = entry_moments(M, row, mrow, n);
-            if (M.gauss[n]) {
-                gauss_sums(e.y, e.m, M.noise[n] + e.s2, s);
-            } else {
-                poisson_sums(M, mrow, n, e.y, e.m, s);
-                s[0] = e.s2 < 1e-30 ? poisson_ll(s) : poisson_lognormal(e.y, e.m, e.s2, q.n, t.z, t.lwa) - s[3];
-            }
-            if (rate) rate[at] = s[2];
-            if (lpd) lpd[at] = s[0];
-        }
-        emit(s);
+        pred_entry(SetMoments{}, M, q, t, rate, lpd, row, mrow, n, live, at, emit);
+    }
+};
+
+// vlgp_predictive_cov: the same entry under the caller's mu, cov
+struct PredCovScorer {
+    Nodes q;
+    CovMoments src;
+    double* rate;
+    double* lpd;
+    static constexpr int groups = 1;
+    typedef NodeTables Lds;
+    __device__ void stage(Lds& t) const { nodes_stage(q, t); }
+    template <class Emit>
+    __device__ __forceinline__ void entry(const RowModel& M, const Lds& t, int64_t row, int64_t mrow, int n, bool live,
+                                          int64_t at, Emit emit) const {
+        pred_entry(src, M, q, t, rate, lpd, row, mrow, n, live, at, emit);
     }
 };
 
@@ -54,4 +80,10 @@ struct PredScorer {
 int launch_predictive(vlgp_ctx* ctx, UnitSet& us, int vb, int n_nodes, const double* d_nodes, double* d_rate, double* d_lpd,
                       double* d_part, double* d_sums) {
     return launch_row_scores(ctx, "vlgp_predictive", us, vb, PredScorer{{n_nodes, d_nodes}, d_rate, d_lpd}, d_part, d_sums);
+}
+
+int launch_predictive_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double* d_nodes, const double* d_mu,
+                          const double* d_cov, double* d_rate, double* d_lpd, double* d_part, double* d_sums) {
+    return launch_row_scores(ctx, "vlgp_predictive_cov", us, 1, PredCovScorer{{n_nodes, d_nodes}, {d_mu, d_cov}, d_rate, d_lpd},
+                             d_part, d_sums);
 }

@@ -109,11 +109,59 @@ __device__ __forceinline__ void gauss_sums(double yv, double m, double nz, doubl
     s[3] = yv * yv;
 }
 
-// Poisson at the rate trunc_exp(m + 1/2 (a_n^2) . v), the variance term continuing the chain of m: . | y | rate |
-// lgamma(y + 1); s[0] is the scorer's, poisson_ll(s) the plug-in one
-__device__ __forceinline__ void poisson_sums(const RowModel& M, int64_t mrow, int n, double yv, double m, double (&s)[4]) {
+// Poisson at the rate trunc_exp(arg): . | y | rate | lgamma(y + 1); s[0] is the scorer's, poisson_ll(s) the plug-in one
+__device__ __forceinline__ void poisson_sums_at(double yv, double arg, double (&s)[4]) {
     s[1] = yv;
-    s[2] = exp(clamp10(row_quad(M, mrow, n, m)));
+    s[2] = exp(clamp10(arg));
     s[3] = lgamma(yv + 1.0);
 }
+// ... with arg = m + 1/2 (a_n^2) . v, the variance term continuing the chain of m
+__device__ __forceinline__ void poisson_sums(const RowModel& M, int64_t mrow, int n, double yv, double m, double (&s)[4]) {
+    poisson_sums_at(yv, row_quad(M, mrow, n, m), s);
+}
 __device__ __forceinline__ double poisson_ll(const double (&s)[4]) { return s[1] * log(s[2]) - s[2] - s[3]; }
+
+// ---- where the moments of an entry come from (predictive.hip, calibrate.hip) -------------------------------------------
+// moments(): m, s2, y of an entry; rate_arg(): the argument of the Poisson rate trunc_exp(m + s2 / 2); checked: whether m
+// and s2 may be non-finite and the scorer must look (the set's own mu, v are the E-step's and are not looked at).
+// SetMoments: the set's mu, v -- entry_moments and the chain of row_quad.
+struct SetMoments {
+    static constexpr bool checked = false;
+    __device__ __forceinline__ EntryMoments moments(const RowModel& M, int64_t row, int64_t mrow, int n) const {
+        return entry_moments(M, row, mrow, n);
+    }
+    __device__ __forceinline__ double rate_arg(const RowModel& M, int64_t mrow, int n, const EntryMoments& e) const {
+        return row_quad(M, mrow, n, e.m);
+    }
+};
+// CovMoments: a supplied Gaussian posterior of the latents of every row, mu (rows of the posterior's set, L) and cov
+// (the same rows, L (L + 1) / 2), the pair (l, l'), l' <= l, at l (l + 1) / 2 + l'.  m is row_eta's chain with this mu;
+//   t_l = sum_l' C[l, l'] a_l'n   a chain of fma from 0 over l' = 0 ... L - 1 (C[l, l'] read at the pair (max, min)),
+//   q = sum_l a_ln t_l            a chain of fma from 0 over l = 0 ... L - 1,
+// s2 = max(0, q) when q is finite and NaN otherwise; rate_arg = fma(1/2, s2, m).
+struct CovMoments {
+    const double* mu;
+    const double* cov;
+    static constexpr bool checked = true;
+    __device__ __forceinline__ EntryMoments moments(const RowModel& M, int64_t row, int64_t mrow, int n) const {
+        const int L = M.L;
+        EntryMoments e = {M.xb ? M.xb[row * M.N + n] : M.b[n], 0.0, M.y[row * M.N + n]};
+        for (int l = 0; l < L; ++l) e.m = fma(mu[mrow * L + l], M.a[l * M.N + n], e.m);
+        const double* __restrict__ C = cov + mrow * (L * (L + 1) / 2);
+        double q = 0.0;
+        for (int l = 0; l < L; ++l) {
+            double t = 0.0;
+            for (int l2 = 0; l2 < L; ++l2) {
+                const int hi = max(l, l2), lo = min(l, l2);
+                t = fma(C[hi * (hi + 1) / 2 + lo], M.a[l2 * M.N + n], t);
+            }
+            q = fma(M.a[l * M.N + n], t, q);
+        }
+        e.s2 = isfinite(q) ? fmax(q, 0.0) : NAN;
+        return e;
+    }
+    __device__ __forceinline__ double rate_arg(const RowModel&, int64_t, int, const EntryMoments& e) const {
+        return fma(0.5, e.s2, e.m);
+    }
+};
+__device__ __forceinline__ bool moments_finite(const EntryMoments& e) { return isfinite(e.m) && isfinite(e.s2); }

@@ -68,6 +68,30 @@ def unpack_mask(words, n_channels):
     return bits[..., :int(n_channels)].astype(bool)
 
 
+def pack_cov(cov, rows, n_latents):
+    """Per-row covariances as vlgp_predictive_cov takes them: float64 (rows, L (L + 1) / 2), the pair ``(l, l')``,
+    ``l' <= l``, at ``l (l + 1) / 2 + l'``.  ``cov``: that packed form, or (rows, L, L), of which the lower triangle is
+    read."""
+    L = int(n_latents)
+    cov = np.asarray(cov, dtype=float)
+    il, jl = np.tril_indices(L)  # (row-major over the lower triangle: exactly the packed order)
+    if cov.shape == (rows, L, L):
+        cov = cov[:, il, jl]
+    if cov.shape != (rows, len(il)):
+        raise ValueError("cov must be (%d, %d, %d) or packed (%d, %d), got %r" % (rows, L, L, rows, len(il), cov.shape))
+    return _f64(cov)
+
+
+def unpack_cov(packed, n_latents):
+    """The inverse of ``pack_cov``: (rows, L (L + 1) / 2) -> symmetric (rows, L, L)."""
+    L = int(n_latents)
+    il, jl = np.tril_indices(L)
+    out = np.empty((packed.shape[0], L, L))
+    out[:, il, jl] = packed
+    out[:, jl, il] = packed
+    return out
+
+
 MAX_NODES = 64  # the largest quadrature rule vlgp_predictive takes
 
 
@@ -313,30 +337,58 @@ class Engine:
         self._ck(self.lib.vlgp_loglik(self.h, int(set_id), int(bool(vb)), dptr(rate), dptr(sums)))
         return sums, rate
 
-    def predictive(self, set_id, n_nodes=12, vb=True, want_rate=False, want_lpd=False):
+    def _moments(self, set_id, mu, cov):
+        """The ``mu, cov`` of ``predictive`` and ``calibration`` as the ``_cov`` entry points take them: None, None, or
+        float64 ``mu`` (rows of the set, L) and ``cov`` packed (rows, L (L + 1) / 2) from either form (``pack_cov``)."""
+        if mu is None and cov is None:
+            return None, None
+        if mu is None or cov is None:
+            raise ValueError("mu and cov go together: a posterior mean and covariance per row of the set")
+        rows = self.sets[set_id][1]
+        mu = _f64(mu)
+        if mu.shape != (rows, self.L):
+            raise ValueError("mu must be (%d, %d), got %r" % (rows, self.L, mu.shape))
+        return mu, pack_cov(cov, rows, self.L)
+
+    def predictive(self, set_id, n_nodes=12, vb=True, want_rate=False, want_lpd=False, mu=None, cov=None):
         """Posterior-predictive log density of a set's entries (vlgp_predictive): ``(sums, rate, lpd)``.  ``sums`` has
         the shape and slots of ``loglik``'s with ``sum lpd`` in column 0; ``rate`` (``loglik``'s plug-in rate) and
         ``lpd`` have the shape of ``loglik``'s rate, or are None.  ``n_nodes``: points of the mode-centred Gauss-Hermite
-        rule of the Poisson channels (``hermite_nodes``).  Changes no state."""
+        rule of the Poisson channels (``hermite_nodes``).  ``mu`` (rows of the set, L) and ``cov`` (those rows, L, L), or
+        packed as ``joint_posterior`` unpacks it: score under this posterior of the latents instead of the set's own
+        ``mu, v`` (vlgp_predictive_cov; ``vb`` is then not read).  Changes no state."""
         z, lwa = hermite_nodes(n_nodes)
+        mu, cov = self._moments(set_id, mu, cov)
         sums, entry = self._score_shapes(set_id)
         sums, rate, lpd = np.empty(sums), np.empty(entry) if want_rate else None, np.empty(entry) if want_lpd else None
+        if mu is not None:
+            self._ck(self.lib.vlgp_predictive_cov(self.h, int(set_id), len(z), dptr(z), dptr(lwa), dptr(mu), dptr(cov),
+                                                  dptr(rate), dptr(lpd), dptr(sums)))
+            return sums, rate, lpd
         self._ck(self.lib.vlgp_predictive(self.h, int(set_id), int(bool(vb)), len(z), dptr(z), dptr(lwa), dptr(rate),
                                           dptr(lpd), dptr(sums)))
         return sums, rate, lpd
 
-    def calibration(self, set_id, n_bins=10, levels=(0.5, 0.9), n_nodes=12, vb=True, max_count=4096, want_cdf=False):
+    def calibration(self, set_id, n_bins=10, levels=(0.5, 0.9), n_nodes=12, vb=True, max_count=4096, want_cdf=False,
+                    mu=None, cov=None):
         """Calibration sums of a set's predictive distribution (vlgp_calibration): ``(sums, cdf)``.  ``sums`` has the
         leading shape of ``predictive``'s sums and ``W = n_bins + len(levels) + 3`` columns per slot,
         ``pit_0 ... | covered_0 ... | pearson | entries | skipped`` (``evaluation.calibration_from_sums`` reads them);
         ``cdf``, with ``want_cdf``, has the per-entry shape of ``predictive``'s ``lpd`` plus ``(2,)``: ``F(y - 1), F(y)``,
         NaN for a skipped entry (a Poisson count that is negative, no integer, not finite or above ``max_count``), else
-        None.  The arguments are checked before any device call.  Changes no state."""
+        None.  ``mu``, ``cov``: as ``predictive`` takes them (vlgp_calibration_cov); an entry whose moments are not finite
+        is skipped.  The arguments are checked before any device call.  Changes no state."""
         n_bins, levels, max_count = check_calibration_args(n_bins, levels, max_count)
         z, lwa = hermite_nodes(n_nodes)
+        mu, cov = self._moments(set_id, mu, cov)
         sums, entry = self._score_shapes(set_id)
         sums = np.empty(sums[:-1] + (n_bins + len(levels) + 3,))
         cdf = np.empty(entry + (2,)) if want_cdf else None
+        if mu is not None:
+            self._ck(self.lib.vlgp_calibration_cov(self.h, int(set_id), len(z), dptr(z), dptr(lwa), dptr(mu), dptr(cov),
+                                                   n_bins, len(levels), dptr(levels) if len(levels) else None, max_count,
+                                                   dptr(cdf), dptr(sums)))
+            return sums, cdf
         self._ck(self.lib.vlgp_calibration(self.h, int(set_id), int(bool(vb)), len(z), dptr(z), dptr(lwa), n_bins,
                                            len(levels), dptr(levels) if len(levels) else None, max_count, dptr(cdf),
                                            dptr(sums)))
@@ -423,6 +475,24 @@ class Engine:
         if eps is not None:
             out.update(log_w=log_w, parts=parts)
         return out
+
+    def joint_posterior(self, set_id, max_iter=50, tol=1e-10):
+        """``joint_laplace`` without draws and with the covariance of every row, on a plain set or on a set replicated
+        with ``held_out`` of one replica, whose held-out entries the posterior does not see (vlgp_joint_posterior).
+        Returns ``joint_laplace``'s dict without ``v``, ``log_w`` and ``parts``, plus ``cov`` (rows, L, L), symmetric:
+        ``cov[t, l, l'] = G_l[t] (H^-1)_{l l'} G_l'[t]'``, whose diagonal is ``joint_laplace``'s ``v``.  A failed unit's
+        rows of ``mu`` and ``cov`` are NaN.  Changes no state."""
+        units, rows, _ = self.sets[set_id]
+        beta = np.empty((units, self.L, self.R))
+        stats = np.empty((units, 8))
+        mu, packed = np.empty((rows, self.L)), np.empty((rows, self.L * (self.L + 1) // 2))
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_joint_posterior(self.h, int(set_id), int(max_iter), float(tol), dptr(beta), dptr(stats),
+                                               dptr(mu), dptr(packed), C.byref(n)))
+        return {"beta": beta, "stats": stats, "mu": mu, "cov": unpack_cov(packed, self.L), "n_failed": n.value,
+                "laplace": stats[:, 0].copy(), "ll": stats[:, 1].copy(), "beta_sq": stats[:, 2].copy(),
+                "logdet": stats[:, 3].copy(), "decrement": stats[:, 4].copy(), "n_newton": stats[:, 5].astype(np.int64),
+                "converged": stats[:, 6] > 0, "D": stats[:, 7].astype(np.int64)}
 
     def unit_ranks(self, set_id):
         """(units, L) effective rank of the prior factor each (unit, latent) of the set is bound to."""

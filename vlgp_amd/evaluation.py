@@ -176,8 +176,19 @@ Per scored entry, with ``m``, ``s2`` and ``rate`` as above:
 - per slot the device sums ``W = n_bins + n_levels + 3`` columns, ``pit_0 ... | covered_0 ... | pearson | entries |
   skipped``; ``calibration_from_sums`` turns them into frequencies.
 
+Held-out scores under the joint posterior (``posterior="joint"`` in ``leave_entries_out``, ``leave_group_out`` and
+``calibration``; ``joint_posterior(held_out=, cov=)``; ``vlgp_joint_posterior``, ``vlgp_predictive_cov``,
+``vlgp_calibration_cov``).  The joint Laplace posterior above, computed with the fold's entries held out -- a held-out
+entry ``(t, n)`` has no term in ``ll``, ``res = cur = 0``, and what ``y`` holds there is never read -- and reported with
+the covariance of the latents of every bin, ``cov[t, l, l'] = G_l[t, :] (H^-1)_{l l'} G_l'[t, :]'``, whose diagonal is
+``v``.  A held-out entry is then scored with the predictive density and distribution function above at
+``m = a_n . mu_t + (b x)_tn`` and ``s2 = max(0, a_n' cov[t] a_n)``: the coupling between latents counts, where the
+mean-field ``s2 = (a_n^2) . v_t`` drops it.  One fold at a time: a masked replica of the test set, the E-step, the Newton
+iteration (from ``beta = 0``: the mode does not depend on the start), the score, free.
+
 Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``, ``vlgp_marginal``,
-``vlgp_predictive``, ``vlgp_calibration``, ``vlgp_joint_laplace``): the results are the same bits on every run.
+``vlgp_predictive``, ``vlgp_calibration``, ``vlgp_joint_laplace``, ``vlgp_joint_posterior`` and the ``_cov`` scores): the
+results are the same bits on every run.
 """
 import contextlib
 import math
@@ -258,12 +269,13 @@ def _zero_start(trials, L):
             for tr in trials]
 
 
-def _score(eng, set_id, vb, density, want_rate=True):
+def _score(eng, set_id, vb, density, want_rate=True, mu=None, cov=None):
     """``(sums, rate)`` of a resident set under ``density``: None for the plug-in density (``vlgp_loglik``), else the
-    number of quadrature nodes of the posterior-predictive density (``vlgp_predictive``)."""
+    number of quadrature nodes of the posterior-predictive density (``vlgp_predictive``; with ``mu, cov`` under that
+    posterior of the latents, ``vlgp_predictive_cov``)."""
     if density is None:
         return eng.loglik(set_id, vb=vb, want_rate=want_rate)
-    return eng.predictive(set_id, n_nodes=density, vb=vb, want_rate=want_rate)[:2]
+    return eng.predictive(set_id, n_nodes=density, vb=vb, want_rate=want_rate, mu=mu, cov=cov)[:2]
 
 
 def _density(predictive, n_nodes):
@@ -277,9 +289,10 @@ def _density(predictive, n_nodes):
 
 def _log_scorer(density=None):
     """The scorer of the log scores, as the chunk loops take it: ``scorer(eng, set_id, vb) -> (sums, rate)`` by ``_score``
-    under ``density``; ``width`` columns of sums per slot; ``predictive``: which ``_PREDICTIVE_KEY`` its results carry."""
-    def scorer(eng, set_id, vb):
-        return _score(eng, set_id, vb, density)
+    under ``density`` (``mu=, cov=``: under that posterior, ``_joint_fold``); ``width`` columns of sums per slot;
+    ``predictive``: which ``_PREDICTIVE_KEY`` its results carry."""
+    def scorer(eng, set_id, vb, mu=None, cov=None):
+        return _score(eng, set_id, vb, density, mu=mu, cov=cov)
     scorer.width, scorer.predictive = 4, density is not None
     return scorer
 
@@ -290,8 +303,9 @@ def _calibration_scorer(n_bins, levels, n_nodes, max_count):
     n_bins, levels, max_count = E.check_calibration_args(n_bins, levels, max_count)
     E.hermite_nodes(n_nodes)
 
-    def scorer(eng, set_id, vb):
-        sums, _ = eng.calibration(set_id, n_bins=n_bins, levels=levels, n_nodes=int(n_nodes), vb=vb, max_count=max_count)
+    def scorer(eng, set_id, vb, mu=None, cov=None):
+        sums, _ = eng.calibration(set_id, n_bins=n_bins, levels=levels, n_nodes=int(n_nodes), vb=vb, max_count=max_count,
+                                  mu=mu, cov=cov)
         return sums, None
     scorer.width, scorer.predictive = n_bins + len(levels) + 3, True
     return scorer
@@ -307,6 +321,65 @@ def _replica_chunk(eng, n_iter, dmu_bound, vb, posterior=False, scorer=None, **w
     post = eng.download(SET_REPLICAS, ("mu", "v", "w")) if posterior else None
     eng.free_units(SET_REPLICAS)
     return sums, rate, n_failed, post
+
+
+POSTERIORS = ("mean_field", "joint")
+
+
+def _check_posterior(posterior, predictive=True):
+    """``posterior`` of the held-out scores: ``"mean_field"``, the E-step's ``mu, v``, or ``"joint"``, the joint Laplace
+    posterior with its covariance, which only a predictive density can use."""
+    if posterior not in POSTERIORS:
+        raise ValueError("posterior must be 'mean_field' or 'joint', got %r" % (posterior,))
+    if posterior == "joint" and not predictive:
+        raise ValueError("posterior='joint' needs predictive=True: the plug-in density has no use for a covariance")
+    return posterior == "joint"
+
+
+def _joint_fold(eng, held, n_iter, dmu_bound, vb, scorer, max_iter=50, tol=1e-10):
+    """One fold under the joint posterior: ``SET_TEST`` replicated once with the entries ``held`` (bool (rows, N)) held
+    out, the E-step as ``_replica_chunk`` runs it, the joint Laplace posterior of the replica from there
+    (``Engine.joint_posterior``: the held-out entries reach neither), the fold scored under its ``mu, cov``, the replica
+    freed.  Returns ``(sums (N, scorer.width), rate (rows, N) or None, n_failed, converged, n_newton)``, the last two per
+    trial; ``n_failed`` counts failed E-step updates and failed trials."""
+    eng.replicate(SET_TEST, SET_REPLICAS, held_out=held[None])
+    n_failed = eng.estep(SET_REPLICAS, n_iter, dmu_bound, vb)
+    joint = eng.joint_posterior(SET_REPLICAS, max_iter=max_iter, tol=tol)
+    sums, rate = scorer(eng, SET_REPLICAS, vb, mu=joint["mu"], cov=joint["cov"])
+    eng.free_units(SET_REPLICAS)
+    return sums[0], rate, int(n_failed) + int(joint["n_failed"]), joint["converged"], joint["n_newton"]
+
+
+def _joint_folds(trials, params, config, masks, n_iter, device, scorer):
+    """``_joint_fold`` for every mask of ``masks`` (bool (rows, N) each, pairwise disjoint) in order, from a zero start:
+    ``(sums (n_folds, N, scorer.width), rate (rows, N), n_failed, extra, gauss)`` -- ``rate`` holds every entry's rate
+    from the fold that holds it out, NaN elsewhere; ``extra`` is ``converged`` and ``n_newton``, (n_folds, trials)."""
+    L, N = int(params["zdim"]), int(params["ydim"])
+    n_iter = int(config["max_iter"] if n_iter is None else n_iter)
+    vb = config["method"] == "VB"
+    rows = int(sum(int(tr["y"].shape[0]) for tr in trials))
+    sums, conv, newton = [], [], []
+    rate = np.full((rows, N), np.nan)
+    n_failed = 0
+    with _resident(trials, params, _zero_start(trials, L), device) as eng:
+        for held in masks:
+            s, r, bad, c, n = _joint_fold(eng, held, n_iter, config["dmu_bound"], vb, scorer)
+            sums.append(s)
+            conv.append(c)
+            newton.append(n)
+            n_failed += bad
+            if r is not None:
+                rate[held] = r[held]
+        gauss = eng.gauss.copy()
+    return np.stack(sums), rate, int(n_failed), {"converged": np.stack(conv), "n_newton": np.stack(newton)}, gauss
+
+
+def _group_masks(groups, rows, N):
+    """A channel fold as a mask of entries: constant along the rows."""
+    for g in groups:
+        held = np.zeros((rows, N), dtype=bool)
+        held[:, g] = True
+        yield held
 
 
 def _per_trial(arr, lengths):
@@ -478,19 +551,34 @@ def _leave_out_sums(trials, params, config, groups, n_iter, path, max_replicas, 
     return sums, rate, int(n_failed), used, eng.gauss[channels]
 
 
-def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device, scorer):
+def _leave_out_sums_joint(trials, params, config, groups, n_iter, device, scorer):
+    """``_leave_out_sums`` under the joint posterior, one group at a time (``_joint_folds``): its first three values, the
+    path ``"joint"``, ``gauss`` of the channels, and ``converged``, ``n_newton`` per (group, trial)."""
+    channels = [c for g in groups for c in g]
+    rows, N = int(sum(int(tr["y"].shape[0]) for tr in trials)), int(params["ydim"])
+    got, rate, n_failed, extra, gauss = _joint_folds(trials, params, config, _group_masks(groups, rows, N), n_iter, device,
+                                                     scorer)
+    sums = np.concatenate([got[k][g] for k, g in enumerate(groups)], axis=0)
+    return sums, rate[:, channels], n_failed, "joint", gauss[channels], extra
+
+
+def _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device, scorer, joint=False):
     """What ``leave_one_out`` and ``leave_group_out`` share, for validated ``groups`` and a log scorer
-    (``_leave_out_sums``).  Returns ``channels`` (the groups concatenated), ``rate`` per trial, ``ll``, ``ll_null``,
-    ``n_spikes``, ``bits_per_spike``, ``n_failed``, ``path``."""
-    sums, rate, n_failed, used, gauss = _leave_out_sums(trials, params, config, groups, n_iter, path, max_replicas, device,
-                                                        scorer)
+    (``_leave_out_sums``; ``joint``: ``_leave_out_sums_joint``).  Returns ``channels`` (the groups concatenated), ``rate``
+    per trial, ``ll``, ``ll_null``, ``n_spikes``, ``bits_per_spike``, ``n_failed``, ``path``."""
+    extra = {}
+    if joint:
+        sums, rate, n_failed, used, gauss, extra = _leave_out_sums_joint(trials, params, config, groups, n_iter, device, scorer)
+    else:
+        sums, rate, n_failed, used, gauss = _leave_out_sums(trials, params, config, groups, n_iter, path, max_replicas,
+                                                            device, scorer)
     lengths = [int(tr["y"].shape[0]) for tr in trials]
     ll, ll_null, ny, bps = bits_per_spike(sums, int(sum(lengths)), gauss)
     return {
         "channels": [c for g in groups for c in g],
         "rate": _per_trial(rate, lengths),
         "ll": ll, "ll_null": ll_null, "n_spikes": ny, "bits_per_spike": bps,
-        "n_failed": n_failed, "path": used, **_PREDICTIVE_KEY[scorer.predictive],
+        "n_failed": n_failed, "path": used, **_PREDICTIVE_KEY[scorer.predictive], **extra,
     }
 
 
@@ -557,7 +645,7 @@ def _check_groups(groups, N):
 
 
 def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_iter=None, path="auto",
-                    max_replicas=None, device=0, predictive=False, n_nodes=12):
+                    max_replicas=None, device=0, predictive=False, n_nodes=12, posterior="mean_field"):
     """Leave-group-out (co-smoothing) prediction of held-out trials (module docstring for the definitions).
 
     As ``leave_one_out``, with a set of channels where it has one.  ``groups``: a list of channel lists, non-empty,
@@ -569,13 +657,20 @@ def leave_group_out(trials, params, config, groups=None, n_folds=5, seed=0, n_it
 
     Returns a dict: ``groups``; ``channels``, the groups concatenated in order; ``group_of``, the group index of each of
     those channels; ``rate``, a list per trial of (T, len(channels)); per channel ``ll``, ``ll_null``, ``n_spikes``,
-    ``bits_per_spike``; ``co_bps``; ``n_failed``; ``path``.  ``predictive``, ``n_nodes``: as ``leave_one_out``."""
+    ``bits_per_spike``; ``co_bps``; ``n_failed``; ``path``.  ``predictive``, ``n_nodes``: as ``leave_one_out``.
+
+    ``posterior="joint"`` (needs ``predictive=True``, else ``ValueError``) scores every group under the joint Laplace
+    posterior of the trials inferred without it -- mean and full covariance of the latents per bin (module docstring) --
+    one group at a time in order, the group held out as a mask of entries that is constant along the rows (``path`` and
+    ``max_replicas`` are then not read; ``path`` is reported as ``"joint"``).  The dict gains ``converged`` and
+    ``n_newton``, (groups, trials), and ``n_failed`` also counts trials whose ``H`` could not be factored."""
     if path not in ("auto", "batched", "sequential"):
         raise ValueError("path must be 'auto', 'batched' or 'sequential'")
+    joint = _check_posterior(posterior, predictive)
     N = int(params["ydim"])
     groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
     out = _leave_out(trials, params, config, groups, n_iter, path, max_replicas, device,
-                     _log_scorer(_density(predictive, n_nodes)))
+                     _log_scorer(_density(predictive, n_nodes)), joint=joint)
     out.update(groups=groups, group_of=[k for k, g in enumerate(groups) for _ in g],
                co_bps=co_bits_per_spike(out["ll"], out["ll_null"], out["n_spikes"]))
     return out
@@ -678,7 +773,7 @@ def _entry_masks(trials, params, folds, n_folds, seed):
 
 
 def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_iter=None, max_replicas=None, device=0,
-                      predictive=False, n_nodes=12):
+                      predictive=False, n_nodes=12, posterior="mean_field"):
     """Speckled hold-out on held-out trials: single (row, channel) entries left out of the inference and predicted
     (module docstring for the definitions).
 
@@ -692,15 +787,24 @@ def leave_entries_out(trials, params, config, folds=None, n_folds=5, seed=0, n_i
 
     Returns a dict: ``folds``; ``rate``, per trial (T, N), NaN where never held out (Gaussian: means); per channel
     ``ll``, ``ll_null``, ``n_spikes``, ``n_entries``, ``bits_per_spike``; ``ll_per_fold`` (n_folds, N);
-    ``speckled_bps``; ``n_failed``.  ``predictive``, ``n_nodes``: as ``leave_one_out``."""
+    ``speckled_bps``; ``n_failed``.  ``predictive``, ``n_nodes``: as ``leave_one_out``.
+
+    ``posterior="joint"`` (needs ``predictive=True``, else ``ValueError``) scores every fold under the joint Laplace
+    posterior of the trials inferred without it, as ``leave_group_out`` does: one fold at a time in fold order
+    (``max_replicas`` is then not read), the dict gaining ``converged`` and ``n_newton``, (n_folds, trials)."""
     density = _density(predictive, n_nodes)
+    joint = _check_posterior(posterior, predictive)
     lengths = [int(tr["y"].shape[0]) for tr in trials]
     F, held = _entry_masks(trials, params, folds, n_folds, seed)
-    sums, rate, n_failed, _, gauss = _entries_out(trials, params, config, held, n_iter, max_replicas, device,
-                                                  scorer=_log_scorer(density))
+    extra = {}
+    if joint:
+        sums, rate, n_failed, extra, gauss = _joint_folds(trials, params, config, held, n_iter, device, _log_scorer(density))
+    else:
+        sums, rate, n_failed, _, gauss = _entries_out(trials, params, config, held, n_iter, max_replicas, device,
+                                                      scorer=_log_scorer(density))
     out = entry_scores(sums, (F >= 0).sum(axis=0), gauss)
     out.update(folds=_per_trial(F, lengths), rate=_per_trial(rate, lengths), n_failed=n_failed,
-               **_PREDICTIVE_KEY[density is not None])
+               **_PREDICTIVE_KEY[density is not None], **extra)
     return out
 
 
@@ -750,7 +854,8 @@ def calibration_from_sums(sums, n_bins, levels):
 
 
 def calibration(trials, params, config, how="in_sample", groups=None, folds=None, n_folds=5, seed=0, n_bins=10,
-                levels=(0.5, 0.9), n_nodes=12, max_count=4096, n_iter=None, max_replicas=None, device=0):
+                levels=(0.5, 0.9), n_nodes=12, max_count=4096, n_iter=None, max_replicas=None, device=0,
+                posterior="mean_field"):
     """Calibration of the predictive distribution, per channel (module docstring for the definitions): PIT histogram,
     coverage of the central intervals ``levels`` and Pearson dispersion.
 
@@ -763,14 +868,42 @@ def calibration(trials, params, config, how="in_sample", groups=None, folds=None
     scored.  Trials that carry ``missing`` raise ``ValueError``.
 
     Returns ``calibration_from_sums``' dict with one slot per channel, the replicas or folds added in order, plus
-    ``n_failed`` (failed E-step updates; 0 in sample).  A channel no group holds has no entry: NaN."""
+    ``n_failed`` (failed E-step updates; 0 in sample).  A channel no group holds has no entry: NaN.
+
+    ``posterior="joint"``: the same three questions asked of the joint Laplace posterior, mean and full covariance of the
+    latents per bin.  In sample it is the posterior of the trials' own data, the Newton iteration started from their stored
+    ``mu, w``; for ``"channels"`` and ``"entries"`` the one of ``leave_group_out`` and ``leave_entries_out`` with
+    ``posterior="joint"``, one fold at a time.  An entry of a trial whose ``H`` could not be factored is skipped and
+    counted in ``skipped``.  The dict gains ``converged`` and ``n_newton``, per (fold, trial) or, in sample, per trial, and
+    ``n_failed`` also counts the failed trials."""
     if how not in ("in_sample", "channels", "entries"):
         raise ValueError("how must be 'in_sample', 'channels' or 'entries', got %r" % (how,))
+    joint = _check_posterior(posterior)
     _no_missing(trials, "calibration")
     scorer = _calibration_scorer(n_bins, levels, n_nodes, max_count)
     N, L = int(params["ydim"]), int(params["zdim"])
-    n_failed = 0
-    if how == "in_sample":
+    n_failed, extra = 0, {}
+    if joint:
+        rows = int(sum(int(tr["y"].shape[0]) for tr in trials))
+        if how == "in_sample":
+            with _posterior(trials, params, config, False, n_iter, device) as (eng, _):
+                post = eng.joint_posterior(SET_TEST)
+                sums, _ = scorer(eng, SET_TEST, True, mu=post["mu"], cov=post["cov"])
+            n_failed, extra = post["n_failed"], {"converged": post["converged"], "n_newton": post["n_newton"]}
+        elif how == "channels":
+            groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
+            got, _, n_failed, extra, _ = _joint_folds(trials, params, config, _group_masks(groups, rows, N), n_iter, device,
+                                                      scorer)
+            sums = np.zeros((N, scorer.width))
+            for k, g in enumerate(groups):
+                sums[g] = got[k][g]
+        else:
+            _, held = _entry_masks(trials, params, folds, n_folds, seed)
+            got, _, n_failed, extra, _ = _joint_folds(trials, params, config, held, n_iter, device, scorer)
+            sums = np.zeros((N, scorer.width))
+            for k in range(got.shape[0]):
+                sums += got[k]
+    elif how == "in_sample":
         units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "v": tr.get("v", np.zeros((tr["y"].shape[0], L))),
                   "w": None} for tr in trials]
         with _resident(trials, params, units, device, priors=False) as eng:
@@ -789,6 +922,7 @@ def calibration(trials, params, config, how="in_sample", groups=None, folds=None
             sums += got[k]
     out = calibration_from_sums(sums, n_bins, levels)
     out["n_failed"] = int(n_failed)
+    out.update(extra)
     return out
 
 
@@ -869,10 +1003,11 @@ def weights_summary(log_w):
 
 
 @contextlib.contextmanager
-def _posterior(trials, params, config, infer, n_iter, device):
+def _posterior(trials, params, config, infer, n_iter, device, estep=True):
     """``(eng, n_failed)``: a ``_resident`` engine whose ``SET_TEST`` holds the trials' posterior -- with ``infer`` from a
     zero start and ``n_iter`` E-step iterations (default ``config["max_iter"]``; ``n_failed`` its failed updates), else the
-    trials' stored ``mu, v, w`` (``n_failed = 0``)."""
+    trials' stored ``mu, v, w`` (``n_failed = 0``).  ``estep=False`` leaves the zero start as it is: the caller's E-step
+    runs on a replica of the set."""
     L = int(params["zdim"])
     if infer:
         units = _zero_start(trials, L)
@@ -882,7 +1017,7 @@ def _posterior(trials, params, config, infer, n_iter, device):
                  for tr in trials]
     n_iter = int(config["max_iter"] if n_iter is None else n_iter)
     with _resident(trials, params, units, device) as eng:
-        yield eng, eng.estep(SET_TEST, n_iter, config["dmu_bound"], config["method"] == "VB") if infer else 0
+        yield eng, eng.estep(SET_TEST, n_iter, config["dmu_bound"], config["method"] == "VB") if infer and estep else 0
 
 
 def _evidence_bps(total, sums, rows, gauss):
@@ -954,7 +1089,8 @@ def marginal_loglik(trials, params, config, n_samples=64, seed=0, rng=None, infe
     return out
 
 
-def joint_posterior(trials, params, config, infer=True, n_iter=None, max_iter=50, tol=1e-10, device=0):
+def joint_posterior(trials, params, config, infer=True, n_iter=None, max_iter=50, tol=1e-10, device=0, held_out=None,
+                    cov=None):
     """The joint Laplace posterior of every trial: the mode of the posterior over all prior weights of the trial, found by
     a damped Newton iteration on the device (module docstring for the definitions).
 
@@ -968,16 +1104,40 @@ def joint_posterior(trials, params, config, infer=True, n_iter=None, max_iter=50
     ``config["method"]`` is --, ``laplace`` (the Laplace evidence ``log p(y_trial)``), ``converged``, ``n_newton``; and
     over all trials ``total``, the sum of ``laplace``; ``laplace_bps = (total - LL_null) / (n_spikes ln 2)`` by
     ``marginal_loglik``'s null model, NaN unless every channel is Poisson; ``n_failed`` (failed E-step updates plus trials
-    whose ``H`` could not be factored: their numbers are NaN, and so is ``total``)."""
+    whose ``H`` could not be factored: their numbers are NaN, and so is ``total``).
+
+    ``cov=True`` adds per trial ``cov`` (T, L, L), the covariance of the latents of every bin, whose diagonal is ``v``
+    (``vlgp_joint_posterior``).  ``held_out``: per trial a (T, N) bool, True where an entry is held out -- neither the
+    E-step nor the Newton iteration sees those entries, whatever ``y`` holds there, and ``laplace`` is the evidence of the
+    others; ``cov`` then defaults to True, the E-step runs on a masked replica of the trials (``infer=False`` starts it
+    from the stored posterior), and ``laplace_bps`` is NaN: its null model counts every entry."""
     _no_missing(trials, "joint_posterior")
     vb = config["method"] == "VB"
     lengths = [int(tr["y"].shape[0]) for tr in trials]
-    with _posterior(trials, params, config, infer, n_iter, device) as (eng, n_failed):
-        joint = eng.joint_laplace(SET_TEST, max_iter=max_iter, tol=tol)
-        sums, _ = eng.loglik(SET_TEST, vb=vb)
+    want_cov = held_out is not None if cov is None else bool(cov)
+    if held_out is not None:
+        held = np.concatenate(_per_trial_entries(held_out, trials, "held_out", bool), axis=0)
+    with _posterior(trials, params, config, infer, n_iter, device, estep=held_out is None) as (eng, n_failed):
+        sid = SET_TEST
+        if held_out is not None:
+            sid = SET_REPLICAS
+            eng.replicate(SET_TEST, sid, held_out=held[None])
+            n_iter = int(config["max_iter"] if n_iter is None else n_iter)
+            n_failed = eng.estep(sid, n_iter, config["dmu_bound"], vb) if infer else 0
+        if want_cov or held_out is not None:
+            joint = eng.joint_posterior(sid, max_iter=max_iter, tol=tol)
+            joint["v"] = np.ascontiguousarray(np.diagonal(joint["cov"], axis1=1, axis2=2))
+        else:
+            joint = eng.joint_laplace(sid, max_iter=max_iter, tol=tol)
+        if held_out is not None:
+            eng.free_units(sid)
+        sums = None if held_out is not None else eng.loglik(SET_TEST, vb=vb)[0]
         gauss = eng.gauss.copy()
     total = float(np.sum(joint["laplace"]))
-    return {"mu": _per_trial(joint["mu"], lengths), "v": _per_trial(joint["v"], lengths), "laplace": joint["laplace"],
-            "converged": joint["converged"], "n_newton": joint["n_newton"], "total": total,
-            "laplace_bps": _evidence_bps(total, sums, sum(lengths), gauss),
-            "n_failed": int(n_failed) + int(joint["n_failed"])}
+    out = {"mu": _per_trial(joint["mu"], lengths), "v": _per_trial(joint["v"], lengths), "laplace": joint["laplace"],
+           "converged": joint["converged"], "n_newton": joint["n_newton"], "total": total,
+           "laplace_bps": float("nan") if held_out is not None else _evidence_bps(total, sums, sum(lengths), gauss),
+           "n_failed": int(n_failed) + int(joint["n_failed"])}
+    if want_cov:
+        out["cov"] = _per_trial(joint["cov"], lengths)
+    return out
