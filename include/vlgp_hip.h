@@ -559,6 +559,10 @@ int vlgp_debug_reload_switches(vlgp_ctx* ctx);
 /* The value the handle currently holds for the switch `name` ("VLGP_..."): a flag 0 / 1, a tri-state -1 (unset) / 0 / 1,
  * an integer or a real.  VLGP_ERR_ARG for a name the table does not hold. */
 int vlgp_debug_switch(vlgp_ctx* ctx, const char* name, double* value);
+/* What the library holds at this moment, over every handle of the process: out[0] device blocks, out[1] their bytes,
+ * out[2] pinned / mapped host blocks, out[3] their bytes.  Every allocation of the library is counted (csrc/dev_mem.h),
+ * so a test of lifetimes asserts equalities instead of watching the free memory of a shared card.  No handle needed. */
+int vlgp_debug_live_memory(int64_t out[4]);
 /* Counters of the H-step objective calls since the handle was created: out[0] evaluations that took the low-rank round,
  * out[1] the sum of their predicted ranks (even + odd block), out[2] evaluations that took the dense round,
  * out[3] low-rank rounds re-run densely because a rank exceeded the prediction. */

@@ -116,6 +116,7 @@ _SIGNATURES = {
     "vlgp_debug_last_hstep_path": (C.c_int, [_h, _ip]),
     "vlgp_debug_reload_switches": (C.c_int, [_h]),
     "vlgp_debug_switch": (C.c_int, [_h, C.c_char_p, C.POINTER(C.c_double)]),
+    "vlgp_debug_live_memory": (C.c_int, [_i64p]),
     "vlgp_debug_hstep_stats": (C.c_int, [_h, _dp]),
     "vlgp_debug_hstep_plan": (C.c_int, [_h, _ip]),
     "vlgp_debug_mstep_plan": (C.c_int, [_h, C.c_int64, _ip]),
@@ -194,3 +195,10 @@ def device_count():
     n = C.c_int(0)
     rc = load().vlgp_device_count(C.byref(n))
     return n.value if rc == 0 else 0
+
+
+def live_memory():
+    """(device blocks, device bytes, host blocks, host bytes) the library holds right now (vlgp_debug_live_memory)."""
+    out = (C.c_int64 * 4)()
+    check(load().vlgp_debug_live_memory(out))
+    return tuple(int(v) for v in out)

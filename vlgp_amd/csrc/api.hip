@@ -26,28 +26,22 @@ int vlgp_fail(vlgp_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-static int dev_alloc(vlgp_ctx* ctx, double** p, int64_t n, bool zero) {
-    *p = nullptr;
+static int dev_alloc(vlgp_ctx* ctx, DevPtr<double>& p, int64_t n, bool zero) {
     if (n <= 0) n = 1;
-    HIPCHK(ctx, hipMalloc(p, (size_t)n * sizeof(double)));
-    if (zero) HIPCHK(ctx, hipMemsetAsync(*p, 0, (size_t)n * sizeof(double), ctx->stream));
+    HIPCHK(ctx, p.alloc((size_t)n));
+    if (zero) HIPCHK(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), ctx->stream));
     return VLGP_OK;
 }
 
 // a workspace of at least n doubles, grown with headroom once the stream that uses it has drained
-static int ensure_work(vlgp_ctx* ctx, hipStream_t st, double** buf, int64_t* len, int64_t n) {
-    if (n <= *len) return VLGP_OK;
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (*buf) HIPCHK(ctx, hipFree(*buf));
-    *buf = nullptr;
-    *len = 0;
-    const int64_t cap = n + n / 4 + 1024;
-    HIPCHK(ctx, hipMalloc(buf, (size_t)cap * sizeof(double)));
-    *len = cap;
+int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n) {
+    HIPCHK(ctx, ctx->d_work.ensure(n, n + n / 4 + 1024, ctx->stream));
     return VLGP_OK;
 }
-int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n) { return ensure_work(ctx, ctx->stream, &ctx->d_work, &ctx->work_len, n); }
-int vlgp_ensure_work_m(vlgp_ctx* ctx, int64_t n) { return ensure_work(ctx, ctx->mstream, &ctx->d_work_m, &ctx->work_m_len, n); }
+int vlgp_ensure_work_m(vlgp_ctx* ctx, int64_t n) {
+    HIPCHK(ctx, ctx->d_work_m.ensure(n, n + n / 4 + 1024, ctx->mstream));
+    return VLGP_OK;
+}
 
 // wait for a queued norms pass (vlgp_norms_begin): its sequence word in mapped host memory
 static int wait_norms(vlgp_ctx* ctx) {
@@ -79,14 +73,7 @@ int vlgp_join_m(vlgp_ctx* ctx) {
 }
 
 int vlgp_ensure_pinned(vlgp_ctx* ctx, int64_t n) {
-    if (n <= ctx->pinned_len) return VLGP_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_pinned) HIPCHK(ctx, hipHostFree(ctx->h_pinned));
-    ctx->h_pinned = nullptr;
-    ctx->pinned_len = 0;
-    const int64_t cap = n + 1024;
-    HIPCHK(ctx, hipHostMalloc(&ctx->h_pinned, (size_t)cap * sizeof(double), hipHostMallocDefault));
-    ctx->pinned_len = cap;
+    HIPCHK(ctx, ctx->h_pinned.ensure(n, n + 1024, ctx->stream, hipHostMallocDefault));
     return VLGP_OK;
 }
 
@@ -199,10 +186,10 @@ static int open_pair(vlgp_ctx* ctx, int src, int dst, bool bad_args, const char*
 // ---- profiling -----------------------------------------------------------
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st) {
     if (!ctx->prof_on) return;
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    (void)hipEventRecord(a, st ? st : ctx->stream);
-    ctx->pending.push_back({kind, a, b, 0.0, false});
+    DevEvent a, b;
+    if (hipEventCreate(a.put()) != hipSuccess || hipEventCreate(b.put()) != hipSuccess) return;
+    (void)hipEventRecord(a, st ? st : ctx->stream.get());
+    ctx->pending.push_back({kind, std::move(a), std::move(b), 0.0, false});
 }
 void vlgp_prof_end(vlgp_ctx* ctx, int kind, double units, hipStream_t st) {
     if (!ctx->prof_on) return;
@@ -211,7 +198,7 @@ void vlgp_prof_end(vlgp_ctx* ctx, int kind, double units, hipStream_t st) {
         if (it->kind != kind || it->done) continue;
         it->units = units;
         it->done = true;
-        (void)hipEventRecord(it->b, st ? st : ctx->stream);
+        (void)hipEventRecord(it->b, st ? st : ctx->stream.get());
         return;
     }
 }
@@ -226,14 +213,18 @@ static void prof_drain(vlgp_ctx* ctx) {
             ctx->prof[p.kind].ms += ms;
             ctx->prof[p.kind].units += p.units;
         }
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
     }
     ctx->pending.clear();
 }
 
 // ---- lifetime --------------------------------------------------------------
 extern "C" int vlgp_abi_version(void) { return VLGP_ABI_VERSION; }
+
+extern "C" int vlgp_debug_live_memory(int64_t out[4]) {
+    if (!out) return vlgp_fail(nullptr, VLGP_ERR_ARG, "null output");
+    for (int i = 0; i < 4; ++i) out[i] = g_live_memory[i].load();
+    return VLGP_OK;
+}
 
 extern "C" int vlgp_device_count(int* count) {
     int n = 0;
@@ -248,21 +239,21 @@ extern "C" int vlgp_device_count(int* count) {
 
 extern "C" const char* vlgp_last_error(vlgp_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
+// wait for the stream, give the source its user count back, release what the set owns (what it borrows stays: dev_mem.h)
 static void free_set(vlgp_ctx* ctx, UnitSet& us) {
     if (!us.valid) return;
     (void)hipStreamSynchronize(ctx->stream);
-    auto fr = [](void* p) { if (p) (void)hipFree(p); };
-    if (us.is(SET_REPLICATED)) {  // replicas: y, x, xb are the source's
-        Replicas& r = us.rep;
-        fr(us.mu); fr(us.v); fr(us.w); fr(r.d_ch); fr(r.d_pair); fr(r.d_mask); fr(r.d_wconst); fr(r.d_nobs); fr(r.d_xa);
-        ctx->sets[r.src].rep_users--;
-        us.d_xb = nullptr;
-    } else if (!us.alias) {
-        fr(us.y); fr(us.x); fr(us.mu); fr(us.v); fr(us.w);
-    }
-    fr(us.dmu); fr(us.d_off); fr(us.d_src_start); fr(us.d_unit_prior); fr(us.d_xb); fr(us.d_scratch); fr(us.d_mu_stash);
-    fr(us.d_links);
+    if (us.rep.src >= 0) ctx->sets[us.rep.src].rep_users--;
     us = UnitSet();
+}
+
+// A set is built in a local UnitSet and moved into its slot when every step has succeeded; a source counts its user then.
+// A step that fails leaves the slot empty (its old contents went first) and the local releases what it had allocated.
+static int commit_set(UnitSet& slot, UnitSet& built, UnitSet* source) {
+    built.valid = true;
+    slot = std::move(built);
+    if (source) source->rep_users++;
+    return VLGP_OK;
 }
 
 // ... and, first, the tiling cuts that share its rows
@@ -306,15 +297,15 @@ extern "C" int vlgp_create(int device, int N, int L, int P, int R, const uint8_t
         // priority, the M-step lane the lowest, so that M kernels only fill what H leaves idle
         int prio_lo = 0, prio_hi = 0;
         CREATE_CHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        CREATE_CHK(hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio_hi));
-        CREATE_CHK(hipStreamCreateWithPriority(&ctx->mstream, hipStreamNonBlocking, prio_lo));
+        CREATE_CHK(hipStreamCreateWithPriority(ctx->stream.put(), hipStreamNonBlocking, prio_hi));
+        CREATE_CHK(hipStreamCreateWithPriority(ctx->mstream.put(), hipStreamNonBlocking, prio_lo));
         ctx->lanes[LANE_MAIN].stream = ctx->stream;
         ctx->lanes[LANE_M].stream = ctx->mstream;
     }
-    CREATE_CHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    CREATE_CHK(hipEventCreate(&ctx->ev_m_start));
-    CREATE_CHK(hipEventCreate(&ctx->ev_m_done));
-    CREATE_CHK(hipMalloc(&ctx->d_fail_m, sizeof(int)));
+    CREATE_CHK(hipEventCreateWithFlags(ctx->ev_fork.put(), hipEventDisableTiming));
+    CREATE_CHK(hipEventCreate(ctx->ev_m_start.put()));
+    CREATE_CHK(hipEventCreate(ctx->ev_m_done.put()));
+    CREATE_CHK(ctx->d_fail_m.alloc(1));
     CREATE_CHK(hipMemset(ctx->d_fail_m, 0, sizeof(int)));
     ctx->gauss.assign(N, 0);
     std::vector<int> gi(N, 0);
@@ -324,16 +315,16 @@ extern "C" int vlgp_create(int device, int N, int L, int P, int R, const uint8_t
         gi[n] = g ? 1 : 0;
         ctx->n_gauss += g ? 1 : 0;
     }
-    CREATE_CHK(hipMalloc(&ctx->d_gauss, sizeof(int) * N));
+    CREATE_CHK(ctx->d_gauss.alloc(N));
     CREATE_CHK(hipMemcpy(ctx->d_gauss, gi.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-    CREATE_CHK(hipMalloc(&ctx->d_a, sizeof(double) * L * N));
-    CREATE_CHK(hipMalloc(&ctx->d_da, sizeof(double) * L * N));
-    CREATE_CHK(hipMalloc(&ctx->d_b, sizeof(double) * P * N));
-    CREATE_CHK(hipMalloc(&ctx->d_db, sizeof(double) * P * N));
-    CREATE_CHK(hipMalloc(&ctx->d_noise, sizeof(double) * N));
+    CREATE_CHK(ctx->d_a.alloc((size_t)L * N));
+    CREATE_CHK(ctx->d_da.alloc((size_t)L * N));
+    CREATE_CHK(ctx->d_b.alloc((size_t)P * N));
+    CREATE_CHK(ctx->d_db.alloc((size_t)P * N));
+    CREATE_CHK(ctx->d_noise.alloc(N));
     CREATE_CHK(hipMemset(ctx->d_da, 0, sizeof(double) * L * N));
     CREATE_CHK(hipMemset(ctx->d_db, 0, sizeof(double) * P * N));
-    CREATE_CHK(hipMalloc(&ctx->d_fail, sizeof(int)));
+    CREATE_CHK(ctx->d_fail.alloc(1));
     CREATE_CHK(hipMemset(ctx->d_fail, 0, sizeof(int)));
 #undef CREATE_CHK
     *out = ctx;
@@ -342,10 +333,6 @@ extern "C" int vlgp_create(int device, int N, int L, int P, int R, const uint8_t
 
 static void free_priors(vlgp_ctx* ctx) {
     ctx->prior_pending.clear();  // (every caller has synchronised the stream; the ranks go with the priors)
-    for (auto& kv : ctx->priors) {
-        if (kv.second.d_full) (void)hipFree(kv.second.d_full);
-        if (kv.second.d_compact) (void)hipFree(kv.second.d_compact);
-    }
     ctx->priors.clear();
 }
 
@@ -363,34 +350,7 @@ extern "C" int vlgp_destroy(vlgp_ctx* ctx) {
     for (int pass = 0; pass < 2; ++pass)
         for (auto& us : ctx->sets)
             if (us.valid && (pass == 1 || us.is(SET_TILING))) free_set(ctx, us);
-    free_priors(ctx);
-    auto fr = [](void* p) { if (p) (void)hipFree(p); };
-    fr(ctx->d_gauss); fr(ctx->d_a); fr(ctx->d_b); fr(ctx->d_noise); fr(ctx->d_da); fr(ctx->d_db);
-    fr(ctx->d_hwlm); fr(ctx->d_ecols); fr(ctx->d_fail); fr(ctx->d_fail_m); fr(ctx->d_work_m); fr(ctx->d_clk); fr(ctx->d_work); fr(ctx->d_elbo);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_m_start) (void)hipEventDestroy(ctx->ev_m_start);
-    if (ctx->ev_m_done) (void)hipEventDestroy(ctx->ev_m_done);
-    if (ctx->ev_e_fork) (void)hipEventDestroy(ctx->ev_e_fork);
-    for (int i = 0; i < VLGP_E_LANES - 1; ++i) {
-        if (ctx->ev_e_join[i]) (void)hipEventDestroy(ctx->ev_e_join[i]);
-        if (ctx->elane[i]) (void)hipStreamDestroy(ctx->elane[i]);
-    }
-    if (ctx->mstream) (void)hipStreamDestroy(ctx->mstream); fr((void*)ctx->d_prior_base); fr(ctx->d_prior_rl); fr(ctx->d_prior_goff);
-    if (ctx->ev_e_done) (void)hipEventDestroy(ctx->ev_e_done);
-    if (ctx->ev_stage_par) (void)hipEventDestroy(ctx->ev_stage_par);
-    if (ctx->ev_stage_map) (void)hipEventDestroy(ctx->ev_stage_map);
-    fr(ctx->d_xwork); fr(ctx->d_stage_map);
-    if (ctx->h_xres) (void)hipHostFree(ctx->h_xres);
-    if (ctx->h_msnap) (void)hipHostFree(ctx->h_msnap);
-    if (ctx->h_stage_par) (void)hipHostFree(ctx->h_stage_par);
-    if (ctx->h_stage_map) (void)hipHostFree(ctx->h_stage_map);
-    if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    if (ctx->h_hres) (void)hipHostFree(ctx->h_hres);
-    if (ctx->h_prior_mb) (void)hipHostFree(ctx->h_prior_mb);
-    fr(ctx->d_prior_mb);
-    fr(ctx->d_hsync); fr(ctx->d_hmom); fr(ctx->d_hmpart);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // every buffer, event and stream is a member that releases itself (dev_mem.h)
     return VLGP_OK;
 }
 
@@ -427,16 +387,16 @@ static int set_offsets(vlgp_ctx* ctx, UnitSet& us, int M, const int64_t* off) {
         us.Tmax = std::max<int>(us.Tmax, (int)T);
         us.Tmin = std::min<int>(us.Tmin, (int)T);
     }
-    HIPCHK(ctx, hipMalloc(&us.d_off, sizeof(int64_t) * (M + 1)));
+    HIPCHK(ctx, us.d_off.alloc((size_t)M + 1));
     HIPCHK(ctx, hipMemcpyAsync(us.d_off, us.off.data(), sizeof(int64_t) * (M + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMalloc(&us.d_unit_prior, sizeof(int) * M));
+    HIPCHK(ctx, us.d_unit_prior.alloc(M));
     us.prior_epoch = 0;
     return VLGP_OK;
 }
 
-static int up(vlgp_ctx* ctx, double** dst, const double* src, int64_t n) {
+static int up(vlgp_ctx* ctx, DevPtr<double>& dst, const double* src, int64_t n) {
     CHK(dev_alloc(ctx, dst, n, src == nullptr));
-    if (src) HIPCHK(ctx, hipMemcpyAsync(*dst, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (src) HIPCHK(ctx, hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     return VLGP_OK;
 }
 
@@ -448,18 +408,18 @@ extern "C" int vlgp_upload_units(vlgp_ctx* ctx, int set, int M, const int64_t* o
     if (offsets[0] != 0) return vlgp_fail(ctx, VLGP_ERR_ARG, "offsets[0] must be 0");
     if (!x && ctx->P != 1) return vlgp_fail(ctx, VLGP_ERR_ARG, "x == NULL (all ones) requires xdim == 1");
     free_with_tiling_cuts(ctx, set);
-    CHK(set_offsets(ctx, *us, M, offsets));
-    const int64_t rows = us->rows;
-    CHK(up(ctx, &us->y, y, rows * ctx->N));
-    us->x_ones = (x == nullptr);
-    if (x) CHK(up(ctx, &us->x, x, rows * ctx->P * ctx->N));
-    CHK(up(ctx, &us->mu, mu, rows * ctx->L));
-    CHK(up(ctx, &us->v, v, rows * ctx->L));
-    CHK(up(ctx, &us->w, w, rows * ctx->L));
-    CHK(dev_alloc(ctx, &us->dmu, rows * ctx->L, true));
+    UnitSet made;
+    CHK(set_offsets(ctx, made, M, offsets));
+    const int64_t rows = made.rows;
+    CHK(up(ctx, made.y, y, rows * ctx->N));
+    made.x_ones = (x == nullptr);
+    if (x) CHK(up(ctx, made.x, x, rows * ctx->P * ctx->N));
+    CHK(up(ctx, made.mu, mu, rows * ctx->L));
+    CHK(up(ctx, made.v, v, rows * ctx->L));
+    CHK(up(ctx, made.w, w, rows * ctx->L));
+    CHK(dev_alloc(ctx, made.dmu, rows * ctx->L, true));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // host buffers are the caller's again
-    us->valid = true;
-    return VLGP_OK;
+    return commit_set(*us, made, nullptr);
 }
 
 extern "C" int vlgp_cut_units(vlgp_ctx* ctx, int src, int dst, int M_dst, const int64_t* start, int window) {
@@ -474,31 +434,30 @@ extern "C" int vlgp_cut_units(vlgp_ctx* ctx, int src, int dst, int M_dst, const 
         if (start[k] != (int64_t)k * window) exact = false;
     }
     free_set(ctx, *d);
+    UnitSet made;
     std::vector<int64_t> off(M_dst + 1);
     for (int k = 0; k <= M_dst; ++k) off[k] = (int64_t)k * window;
-    CHK(set_offsets(ctx, *d, M_dst, off.data()));
-    d->parent = src;
-    d->x_ones = s->x_ones;
-    d->src_start.assign(start, start + M_dst);
-    HIPCHK(ctx, hipMalloc(&d->d_src_start, sizeof(int64_t) * M_dst));
-    HIPCHK(ctx, hipMemcpyAsync(d->d_src_start, start, sizeof(int64_t) * M_dst, hipMemcpyHostToDevice, ctx->stream));
-    const int64_t rows = d->rows;
-    CHK(dev_alloc(ctx, &d->dmu, rows * ctx->L, true));
-    if (exact) {
-        d->alias = true;
-        d->y = s->y; d->x = s->x; d->mu = s->mu; d->v = s->v; d->w = s->w;
+    CHK(set_offsets(ctx, made, M_dst, off.data()));
+    made.parent = src;
+    made.x_ones = s->x_ones;
+    made.src_start.assign(start, start + M_dst);
+    HIPCHK(ctx, made.d_src_start.alloc(M_dst));
+    HIPCHK(ctx, hipMemcpyAsync(made.d_src_start, start, sizeof(int64_t) * M_dst, hipMemcpyHostToDevice, ctx->stream));
+    const int64_t rows = made.rows;
+    CHK(dev_alloc(ctx, made.dmu, rows * ctx->L, true));
+    made.alias = exact;
+    if (exact) {  // a tiling cut: the parent's rows
+        made.y.borrow(s->y); made.x.borrow(s->x); made.mu.borrow(s->mu); made.v.borrow(s->v); made.w.borrow(s->w);
     } else {
-        d->alias = false;
-        CHK(dev_alloc(ctx, &d->y, rows * ctx->N, false));
-        if (!s->x_ones) CHK(dev_alloc(ctx, &d->x, rows * ctx->P * ctx->N, false));
-        CHK(dev_alloc(ctx, &d->mu, rows * ctx->L, false));
-        CHK(dev_alloc(ctx, &d->v, rows * ctx->L, false));
-        CHK(dev_alloc(ctx, &d->w, rows * ctx->L, false));
-        CHK(launch_gather(ctx, *s, *d, window));
+        CHK(dev_alloc(ctx, made.y, rows * ctx->N, false));
+        if (!s->x_ones) CHK(dev_alloc(ctx, made.x, rows * ctx->P * ctx->N, false));
+        CHK(dev_alloc(ctx, made.mu, rows * ctx->L, false));
+        CHK(dev_alloc(ctx, made.v, rows * ctx->L, false));
+        CHK(dev_alloc(ctx, made.w, rows * ctx->L, false));
+        CHK(launch_gather(ctx, *s, made, window));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    d->valid = true;
-    return VLGP_OK;
+    return commit_set(*d, made, nullptr);
 }
 
 extern "C" int vlgp_merge_units(vlgp_ctx* ctx, int cut_set) {
@@ -515,7 +474,7 @@ extern "C" int vlgp_stash_mu(vlgp_ctx* ctx, int set, int restore) {
     CHK(open_set(ctx, set, OPEN_JOIN, &us, &admit_vlgp_stash_mu));
     const size_t nb = (size_t)us->rows * ctx->L * sizeof(double);
     if (!restore) {
-        if (!us->d_mu_stash) HIPCHK(ctx, hipMalloc(&us->d_mu_stash, nb));
+        if (!us->d_mu_stash) HIPCHK(ctx, us->d_mu_stash.alloc((size_t)us->rows * ctx->L));
         HIPCHK(ctx, hipMemcpyAsync(us->d_mu_stash, us->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
         return VLGP_OK;
     }
@@ -554,9 +513,8 @@ static int replicas_check(vlgp_ctx* ctx, int src, int dst, int n_rep, const Unit
     return VLGP_OK;
 }
 
-// dst := n_rep replicas of src, replica-major: offsets, y and x aliased, mu, v, w, dmu its own, copies of the source's
-// (enqueued; the caller adds its tables and synchronises).  From `valid` on free_set releases whatever was allocated,
-// should a later step fail.
+// d := n_rep replicas of src, replica-major: offsets, y and x borrowed, mu, v, w, dmu its own, copies of the source's
+// (enqueued; the caller adds its tables, synchronises and commits d to slot dst, whose old contents go here).
 static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s, UnitSet* d) {
     free_with_tiling_cuts(ctx, dst);
     const int Ms = s->M, L = ctx->L;
@@ -571,16 +529,14 @@ static int replicas_make(vlgp_ctx* ctx, int src, int dst, int n_rep, UnitSet* s,
     d->rep.rows_src = rs;
     d->rep.nw = (ctx->N + 63) / 64;
     d->x_ones = s->x_ones;
-    d->y = s->y;  // aliased: a copy per replica would be rows x N doubles each
-    d->x = s->x;
-    s->rep_users++;
-    d->valid = true;
+    d->y.borrow(s->y);  // a copy per replica would be rows x N doubles each
+    d->x.borrow(s->x);
     const size_t nb = (size_t)rs * L * sizeof(double);
-    CHK(dev_alloc(ctx, &d->mu, n_rep * rs * L, false));
-    CHK(dev_alloc(ctx, &d->v, n_rep * rs * L, false));
-    CHK(dev_alloc(ctx, &d->w, n_rep * rs * L, false));
-    CHK(dev_alloc(ctx, &d->dmu, n_rep * rs * L, false));
-    HIPCHK(ctx, hipMalloc(&d->rep.d_xa, sizeof(d->rep.xh)));
+    CHK(dev_alloc(ctx, d->mu, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, d->v, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, d->w, n_rep * rs * L, false));
+    CHK(dev_alloc(ctx, d->dmu, n_rep * rs * L, false));
+    HIPCHK(ctx, d->rep.d_xa.alloc(sizeof(d->rep.xh) / sizeof(double)));
     for (int k = 0; k < n_rep; ++k) {
         const int64_t o = k * rs * L;
         HIPCHK(ctx, hipMemcpyAsync(d->mu + o, s->mu, nb, hipMemcpyDeviceToDevice, ctx->stream));
@@ -616,19 +572,20 @@ extern "C" int vlgp_replicate_groups(vlgp_ctx* ctx, int src, int dst, int n_rep,
     }
     const int n_pairs = group_start[n_rep];
     CHK(replicas_check(ctx, src, dst, n_rep, s, d));
-    CHK(replicas_make(ctx, src, dst, n_rep, s, d));
-    Replicas& r = d->rep;
+    UnitSet made;
+    CHK(replicas_make(ctx, src, dst, n_rep, s, &made));
+    Replicas& r = made.rep;
     r.n_pairs = n_pairs;
-    HIPCHK(ctx, hipMalloc(&r.d_ch, sizeof(int) * n_pairs));
-    HIPCHK(ctx, hipMalloc(&r.d_pair, sizeof(int) * n_pairs));
-    HIPCHK(ctx, hipMalloc(&r.d_mask, sizeof(unsigned long long) * mask.size()));
-    HIPCHK(ctx, hipMalloc(&r.d_wconst, sizeof(double) * 16 * n_rep));
+    HIPCHK(ctx, r.d_ch.alloc(n_pairs));
+    HIPCHK(ctx, r.d_pair.alloc(n_pairs));
+    HIPCHK(ctx, r.d_mask.alloc(mask.size()));
+    HIPCHK(ctx, r.d_wconst.alloc((size_t)16 * n_rep));
     HIPCHK(ctx, hipMemcpyAsync(r.d_ch, channel, sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(r.d_pair, pair_rep.data(), sizeof(int) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(r.d_mask, mask.data(), sizeof(unsigned long long) * mask.size(), hipMemcpyHostToDevice,
                                ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the channel list is the caller's again, the host tables may go)
-    return VLGP_OK;
+    return commit_set(*d, made, s);
 }
 
 // Speckled hold-out: replica k leaves out the entries (row, n) whose bit is set in held_out[(k rows_src + row) nw + (n >> 6)].
@@ -655,14 +612,15 @@ extern "C" int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep,
                 sw |= mk[q];
             }
         }
-    CHK(replicas_make(ctx, src, dst, n_rep, s, d));
-    Replicas& rp = d->rep;
+    UnitSet made;
+    CHK(replicas_make(ctx, src, dst, n_rep, s, &made));
+    Replicas& rp = made.rep;
     rp.by_row = true;
     rp.overlap = overlap;
     const size_t words = (size_t)n_rep * rs * nw;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "mask words are 64 bits");
-    HIPCHK(ctx, hipMalloc(&rp.d_mask, sizeof(uint64_t) * words));
-    if (ctx->n_gauss > 0) HIPCHK(ctx, hipMalloc(&rp.d_wconst, sizeof(double) * (size_t)n_rep * rs * ctx->L));
+    HIPCHK(ctx, rp.d_mask.alloc(words));
+    if (ctx->n_gauss > 0) HIPCHK(ctx, rp.d_wconst.alloc((size_t)n_rep * rs * ctx->L));
     HIPCHK(ctx, hipMemcpyAsync(rp.d_mask, held_out, sizeof(uint64_t) * words, hipMemcpyHostToDevice, ctx->stream));
     std::vector<double> nobs;  // one replica: a masked fit set, whose M-step divides by the observed rows of each channel
     if (n_rep == 1) {
@@ -670,11 +628,11 @@ extern "C" int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep,
         for (int64_t r = 0; r < rs; ++r)
             for (int n = 0; n < N; ++n)
                 if ((held_out[(size_t)r * nw + (n >> 6)] >> (n & 63)) & 1ull) nobs[n] -= 1.0;
-        HIPCHK(ctx, hipMalloc(&rp.d_nobs, sizeof(double) * (size_t)N));
+        HIPCHK(ctx, rp.d_nobs.alloc((size_t)N));
         HIPCHK(ctx, hipMemcpyAsync(rp.d_nobs, nobs.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the mask is the caller's again)
-    return VLGP_OK;
+    return commit_set(*d, made, s);
 }
 
 // leave-one-out replicas: singleton groups
@@ -693,8 +651,8 @@ extern "C" int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, 
     // through a pinned buffer of its own: the copies are truly asynchronous and nothing waits for them here (the E-step's
     // launches follow on the same stream); the buffer is reused only after the event behind the last copy has fired
     if (!ctx->h_stage_par) {
-        HIPCHK(ctx, hipHostMalloc(&ctx->h_stage_par, sizeof(double) * ((size_t)(L + P) * N + N), hipHostMallocDefault));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_stage_par, hipEventDisableTiming));
+        HIPCHK(ctx, ctx->h_stage_par.alloc((size_t)(L + P) * N + N, hipHostMallocDefault));
+        HIPCHK(ctx, hipEventCreateWithFlags(ctx->ev_stage_par.put(), hipEventDisableTiming));
     }
     if (ctx->stage_par_busy) HIPCHK(ctx, hipEventSynchronize(ctx->ev_stage_par));
     double* ha = ctx->h_stage_par;
@@ -763,10 +721,7 @@ static int rebuild_prior_table(vlgp_ctx* ctx) {
     const int L = ctx->L;
     const int rows = (int)ctx->priors.size();
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_prior_base) (void)hipFree((void*)ctx->d_prior_base);
-    if (ctx->d_prior_rl) (void)hipFree(ctx->d_prior_rl);
-    if (ctx->d_prior_goff) (void)hipFree(ctx->d_prior_goff);
-    ctx->d_prior_base = nullptr; ctx->d_prior_rl = nullptr; ctx->d_prior_goff = nullptr;
+    ctx->d_prior_base.reset(); ctx->d_prior_rl.reset(); ctx->d_prior_goff.reset();
     ctx->prior_rows = rows;
     ctx->prior_epoch++;
     if (rows == 0) return VLGP_OK;
@@ -784,10 +739,10 @@ static int rebuild_prior_table(vlgp_ctx* ctx) {
         }
         ++i;
     }
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_prior_base, sizeof(double*) * rows));
-    HIPCHK(ctx, hipMalloc(&ctx->d_prior_rl, sizeof(int) * rows * L));
-    HIPCHK(ctx, hipMalloc(&ctx->d_prior_goff, sizeof(int64_t) * rows * L));
-    HIPCHK(ctx, hipMemcpy((void*)ctx->d_prior_base, base.data(), sizeof(double*) * rows, hipMemcpyHostToDevice));
+    HIPCHK(ctx, ctx->d_prior_base.alloc(rows));
+    HIPCHK(ctx, ctx->d_prior_rl.alloc((size_t)rows * L));
+    HIPCHK(ctx, ctx->d_prior_goff.alloc((size_t)rows * L));
+    HIPCHK(ctx, hipMemcpy(ctx->d_prior_base.get(), base.data(), sizeof(double*) * rows, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->d_prior_rl, rl.data(), sizeof(int) * rows * L, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->d_prior_goff, goff.data(), sizeof(int64_t) * rows * L, hipMemcpyHostToDevice));
     return VLGP_OK;
@@ -803,15 +758,15 @@ static int new_prior(vlgp_ctx* ctx, int T, Prior** out) {
     Prior pr;
     pr.T = T;
     const int64_t n = (int64_t)ctx->L * T * ctx->R;
-    HIPCHK(ctx, hipMalloc(&pr.d_full, (size_t)n * sizeof(double)));
-    HIPCHK(ctx, hipMalloc(&pr.d_compact, (size_t)n * sizeof(double)));
+    HIPCHK(ctx, pr.d_full.alloc((size_t)n));
+    HIPCHK(ctx, pr.d_compact.alloc((size_t)n));
     // capacity layout of the compact copy: latent l at l*T*R whatever the ranks turn out to be, so that the
     // factorisation kernel can write it (and the table never needs the ranks of the other latents)
     pr.goff.resize(ctx->L);
     for (int l = 0; l < ctx->L; ++l) pr.goff[l] = (int64_t)l * T * ctx->R;
     pr.compact_len = n;
     pr.rl.assign(ctx->L, 1);
-    auto res = ctx->priors.emplace(T, pr);
+    auto res = ctx->priors.emplace(T, std::move(pr));
     *out = &res.first->second;
     return VLGP_OK;
 }
@@ -840,8 +795,6 @@ extern "C" int vlgp_build_prior(vlgp_ctx* ctx, int n_lengths, const int* lengths
         for (auto it = ctx->priors.begin(); it != ctx->priors.end();) {
             if (std::find(lengths, lengths + n_lengths, it->first) == lengths + n_lengths) {
                 HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                if (it->second.d_full) (void)hipFree(it->second.d_full);
-                if (it->second.d_compact) (void)hipFree(it->second.d_compact);
                 it = ctx->priors.erase(it);
             } else {
                 ++it;
@@ -906,7 +859,7 @@ int vlgp_bind_priors(vlgp_ctx* ctx, UnitSet& us) {
 
 int vlgp_refresh_xb(vlgp_ctx* ctx, UnitSet& us) {
     if (us.x_ones) return VLGP_OK;
-    if (!us.d_xb) HIPCHK(ctx, hipMalloc(&us.d_xb, (size_t)us.rows * ctx->N * sizeof(double)));
+    if (!us.d_xb) HIPCHK(ctx, us.d_xb.alloc((size_t)us.rows * ctx->N));
     return launch_xb(ctx, us);
 }
 
@@ -954,19 +907,19 @@ static int estep_staged(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double
         v.valid = true; v.M = cnt; v.rows = (int64_t)cnt * W; v.Tmax = v.Tmin = W;
         v.off.resize(cnt + 1);
         for (int m = 0; m <= cnt; ++m) v.off[m] = (int64_t)m * W;
-        v.d_off = us.d_off;  // 0, W, 2 W, ...: the first cnt + 1 entries serve any range of equal-length units
+        v.d_off.borrow(us.d_off);  // 0, W, 2 W, ...: the first cnt + 1 entries serve any range of equal-length units
         const int64_t r0 = (int64_t)u0 * W;
-        v.y = us.y + r0 * N; v.x = us.x ? us.x + r0 * P * N : nullptr;
-        v.mu = us.mu + r0 * L; v.v = us.v + r0 * L; v.w = us.w + r0 * L; v.dmu = us.dmu + r0 * L;
-        v.x_ones = us.x_ones; v.alias = true;  // (owns nothing)
-        v.d_unit_prior = us.d_unit_prior + u0; v.prior_epoch = us.prior_epoch;
+        v.y.borrow(us.y + r0 * N); v.x.borrow(us.x ? us.x + r0 * P * N : nullptr);
+        v.mu.borrow(us.mu + r0 * L); v.v.borrow(us.v + r0 * L); v.w.borrow(us.w + r0 * L); v.dmu.borrow(us.dmu + r0 * L);
+        v.x_ones = us.x_ones; v.alias = true;  // (borrows everything)
+        v.d_unit_prior.borrow(us.d_unit_prior + u0); v.prior_epoch = us.prior_epoch;
         if (!us.x_ones) {
-            if (!us.d_xb) HIPCHK(ctx, hipMalloc(&us.d_xb, (size_t)us.rows * N * sizeof(double)));
-            v.d_xb = us.d_xb + r0 * N;
+            if (!us.d_xb) HIPCHK(ctx, us.d_xb.alloc((size_t)us.rows * N));
+            v.d_xb.borrow(us.d_xb + r0 * N);
         }
-        v.d_scratch = us.d_scratch; v.scratch_len = us.scratch_len;  // the stages run one after the other
+        v.d_scratch = std::move(us.d_scratch);  // the stages run one after the other
         const int rc = launch_estep(ctx, v, mode, n_iter, dmu_bound, vb);
-        us.d_scratch = v.d_scratch; us.scratch_len = v.scratch_len;  // (re)allocated inside: stays with the set
+        us.d_scratch = std::move(v.d_scratch);  // (re)allocated inside: stays with the set
         if (rc != VLGP_OK) return rc;
         CHK(launch_links_copy(ctx, us, us.link_start[s], us.link_start[s + 1], 1));
     }
@@ -983,7 +936,7 @@ extern "C" int vlgp_estep(vlgp_ctx* ctx, int set, int n_iter, double dmu_bound, 
     const int mode = EM_FACTOR0 | EM_MEAN | EM_W | (vb ? EM_V : 0);
     if (us->stage_start.size() > 2) CHK(estep_staged(ctx, *us, mode, n_iter, dmu_bound, vb ? 1 : 0));
     else CHK(launch_estep(ctx, *us, mode, n_iter, dmu_bound, vb ? 1 : 0));
-    if (!ctx->ev_e_done) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_e_done, hipEventDisableTiming));
+    if (!ctx->ev_e_done) HIPCHK(ctx, hipEventCreateWithFlags(ctx->ev_e_done.put(), hipEventDisableTiming));
     HIPCHK(ctx, hipEventRecord(ctx->ev_e_done, ctx->stream));  // (vlgp_estep_wait: this call's launches, not what is queued behind)
     ctx->e_done_valid = true;
     return end_count(ctx, n_failed);
@@ -1021,12 +974,11 @@ extern "C" int vlgp_set_overlaps(vlgp_ctx* ctx, int set, int n_stages, const int
     us->stage_start.assign(stage_start, stage_start + n_stages + 1);
     us->link_start.assign(n_links > 0 ? link_start : stage_start, (n_links > 0 ? link_start : stage_start) + n_stages + 1);
     if (n_links == 0) us->link_start.assign(n_stages + 1, 0);
-    if (us->d_links) HIPCHK(ctx, hipFree(us->d_links));
-    us->d_links = nullptr;
+    us->d_links.reset();
     us->n_links = n_links;
     us->share_mu = true;
     if (n_links > 0) {
-        HIPCHK(ctx, hipMalloc(&us->d_links, sizeof(int) * 3 * n_links));
+        HIPCHK(ctx, us->d_links.alloc((size_t)3 * n_links));
         HIPCHK(ctx, hipMemcpy(us->d_links, links, sizeof(int) * 3 * n_links, hipMemcpyHostToDevice));
     }
     return VLGP_OK;
@@ -1057,8 +1009,8 @@ extern "C" int vlgp_mstep_begin(vlgp_ctx* ctx, int set, int n_iter, int use_hess
     {   // what the caller pulls afterwards (vlgp_get_params, the failure count), written out by the lane itself
         const int N = ctx->N, L = ctx->L, P = ctx->P;
         if (!ctx->h_msnap) {
-            HIPCHK(ctx, hipHostMalloc(&ctx->h_msnap, sizeof(double) * (2 * (size_t)(L + P) * N + N + 8), hipHostMallocMapped));
-            HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_msnap), ctx->h_msnap, 0));
+            HIPCHK(ctx, ctx->h_msnap.alloc(2 * (size_t)(L + P) * N + N + 8, hipHostMallocMapped));
+            CHK(device_view(ctx, ctx->d_msnap, ctx->h_msnap));
         }
         CHK(launch_snapshot_params(ctx, ctx->mstream, ctx->d_msnap));
         ctx->msnap_valid = true;  // (read only after vlgp_join_m; any vlgp_set_params in between clears it)
@@ -1165,9 +1117,9 @@ extern "C" int vlgp_apply_latent_map(vlgp_ctx* ctx, int set, const double* map, 
     // staged through a pinned and a device buffer of its own, reused after the event behind the last kernel that read
     // them: nothing waits here (this is the first call of every EM iteration, constrain_loading)
     if (!ctx->h_stage_map) {
-        HIPCHK(ctx, hipHostMalloc(&ctx->h_stage_map, sizeof(double) * (L * L + L + 8), hipHostMallocDefault));
-        HIPCHK(ctx, hipMalloc(&ctx->d_stage_map, sizeof(double) * (L * L + L + 8)));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_stage_map, hipEventDisableTiming));
+        HIPCHK(ctx, ctx->h_stage_map.alloc((size_t)L * L + L + 8, hipHostMallocDefault));
+        HIPCHK(ctx, ctx->d_stage_map.alloc((size_t)L * L + L + 8));
+        HIPCHK(ctx, hipEventCreateWithFlags(ctx->ev_stage_map.put(), hipEventDisableTiming));
     }
     if (ctx->stage_map_busy) HIPCHK(ctx, hipEventSynchronize(ctx->ev_stage_map));
     memcpy(ctx->h_stage_map, map, sizeof(double) * L * L);
@@ -1191,7 +1143,7 @@ static int moments_host(vlgp_ctx* ctx, UnitSet& us, std::vector<double>& out) {
     CHK(launch_moments(ctx, us));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_work, sizeof(double) * K, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    out.assign(ctx->h_pinned, ctx->h_pinned + K);
+    out.assign(ctx->h_pinned.get(), ctx->h_pinned + K);
     return VLGP_OK;
 }
 
@@ -1225,11 +1177,11 @@ extern "C" int vlgp_norms_begin(vlgp_ctx* ctx, int set) {
         return VLGP_OK;
     }
     if (!ctx->h_xres) {
-        HIPCHK(ctx, hipMalloc(&ctx->d_xwork, sizeof(double) * (2 * 1024 + 8)));
+        HIPCHK(ctx, ctx->d_xwork.alloc(2 * 1024 + 8));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_xwork, 0, sizeof(double) * (2 * 1024 + 8), ctx->stream));
-        HIPCHK(ctx, hipHostMalloc(&ctx->h_xres, sizeof(double) * 8, hipHostMallocMapped));
+        HIPCHK(ctx, ctx->h_xres.alloc(8, hipHostMallocMapped));
         memset(ctx->h_xres, 0, sizeof(double) * 8);
-        HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_xres), ctx->h_xres, 0));
+        CHK(device_view(ctx, ctx->d_xres, ctx->h_xres));
     }
     ++ctx->x_seq;
     CHK(launch_norms(ctx, *us, ctx->d_xwork, reinterpret_cast<unsigned*>(ctx->d_xwork + 2 * 1024), ctx->d_xres, ctx->x_seq));
@@ -1439,11 +1391,10 @@ extern "C" int vlgp_debug_phase_clock(vlgp_ctx* ctx, int on, uint64_t out[8]) {
         if (ctx->d_clk) HIPCHK(ctx, hipMemcpy(out, ctx->d_clk, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     if (on) {
-        if (!ctx->d_clk) HIPCHK(ctx, hipMalloc(&ctx->d_clk, 8 * sizeof(uint64_t)));
+        if (!ctx->d_clk) HIPCHK(ctx, ctx->d_clk.alloc(8));
         HIPCHK(ctx, hipMemset(ctx->d_clk, 0, 8 * sizeof(uint64_t)));
-    } else if (ctx->d_clk) {
-        (void)hipFree(ctx->d_clk);
-        ctx->d_clk = nullptr;
+    } else {
+        ctx->d_clk.reset();
     }
     return VLGP_OK;
 }

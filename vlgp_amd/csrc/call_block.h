@@ -105,16 +105,12 @@ inline JointPosteriorLayout joint_posterior_layout(int64_t work, int64_t rows, i
 // frees the block: early CHK / HIPCHK returns are safe.
 struct CallBlock {
     vlgp_ctx* ctx;
-    double* d = nullptr;
+    DevPtr<double> d;
     explicit CallBlock(vlgp_ctx* c) : ctx(c) {}
-    CallBlock(const CallBlock&) = delete;
-    CallBlock& operator=(const CallBlock&) = delete;
     ~CallBlock() {
-        if (!d) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d);
+        if (d) (void)hipStreamSynchronize(ctx->stream);
     }
-    hipError_t alloc(int64_t need) { return hipMalloc(&d, sizeof(double) * (size_t)need); }
+    hipError_t alloc(int64_t need) { return d.alloc((size_t)need); }
     double* at(int64_t o) const { return d + o; }
     double* opt(bool want, int64_t o) const { return want ? d + o : nullptr; }
     int* ints(int64_t o) const { return reinterpret_cast<int*>(d + o); }

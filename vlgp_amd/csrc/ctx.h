@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/vlgp_hip.h"
+#include "dev_mem.h"
 
 #define VLGP_WAVE 64
 #define VLGP_E_LANES 4          // split E-step: the unit set runs as up to this many independent lanes (streams)
@@ -16,8 +17,8 @@
 // One low-rank prior factor per distinct unit length (gp.make_cholesky).
 struct Prior {
     int T = 0;
-    double* d_full = nullptr;     // (L, T, R) as the reference lays it out
-    double* d_compact = nullptr;  // per latent: (T, rl) row-major, zero columns dropped
+    DevPtr<double> d_full;        // (L, T, R) as the reference lays it out
+    DevPtr<double> d_compact;     // per latent: (T, rl) row-major, zero columns dropped
     std::vector<int> rl;          // effective rank per latent
     std::vector<int64_t> goff;    // offset of latent l inside d_compact (doubles)
     int64_t compact_len = 0;
@@ -55,34 +56,36 @@ struct Replicas {
     bool by_row = false, overlap = false;
     int n = 0, n_pairs = 0, nw = 0;
     int64_t rows_src = 0;
-    int* d_ch = nullptr;          // groups: (n_pairs) left-out channel of each pair
-    int* d_pair = nullptr;        // groups: (n_pairs) replica of each pair
-    unsigned long long* d_mask = nullptr;  // groups (n, nw), by_row (n rows_src, nw): membership masks
-    double* d_wconst = nullptr;   // Gaussian constant of w (estep_split.hip): groups (n, 16) per replica, by_row per row
-    double* d_nobs = nullptr;     // by_row with n == 1 only: (N) observed rows per channel (M-step noise)
-    void* d_xa = nullptr;         // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
+    DevPtr<int> d_ch;             // groups: (n_pairs) left-out channel of each pair
+    DevPtr<int> d_pair;           // groups: (n_pairs) replica of each pair
+    DevPtr<unsigned long long> d_mask;  // groups (n, nw), by_row (n rows_src, nw): membership masks
+    DevPtr<double> d_wconst;      // Gaussian constant of w (estep_split.hip): groups (n, 16) per replica, by_row per row
+    DevPtr<double> d_nobs;        // by_row with n == 1 only: (N) observed rows per channel (M-step noise)
+    DevPtr<double> d_xa;          // the replica table of the row passes (estep_split.hip, ExclArgs), and its host copy
     double xh[8] = {};
 };
 
+// Move-only: every device pointer is an owner (dev_mem.h).  What a set borrows instead of owning, by kind:
+// a tiling cut y, x, mu, v, w of its parent; a replicated set y, x and (launch_estep) d_xb of its source; the view of
+// one stage that estep_staged builds everything.
 struct UnitSet {
     bool valid = false;
     int M = 0;
     int64_t rows = 0;
     int Tmax = 0, Tmin = 0;
     std::vector<int64_t> off;     // host copy of offsets (M+1)
-    int64_t* d_off = nullptr;
-    double *y = nullptr, *x = nullptr, *mu = nullptr, *v = nullptr, *w = nullptr, *dmu = nullptr;
+    DevPtr<int64_t> d_off;
+    DevPtr<double> y, x, mu, v, w, dmu;
     bool x_ones = true;
     bool alias = false;           // shares y/x/mu/v/w with `parent` (exact tiling cut)
     int parent = -1;
     std::vector<int64_t> src_start;  // for non-aliased cuts: source row of each unit
-    int64_t* d_src_start = nullptr;
-    int* d_unit_prior = nullptr;  // prior-table row per unit
+    DevPtr<int64_t> d_src_start;
+    DevPtr<int> d_unit_prior;     // prior-table row per unit
     uint64_t prior_epoch = 0;     // epoch of the table d_unit_prior was built against
-    double* d_xb = nullptr;       // (rows, N) x.b, only when !x_ones
-    double* d_mu_stash = nullptr; // copy of mu taken by vlgp_stash_mu (rows x L)
-    double* d_scratch = nullptr;  // long-unit E-step scratch
-    int64_t scratch_len = 0;
+    DevPtr<double> d_xb;          // (rows, N) x.b, only when !x_ones
+    DevPtr<double> d_mu_stash;    // copy of mu taken by vlgp_stash_mu (rows x L)
+    GrowBuf<double> d_scratch;    // E-step scratch (generic, long-unit and split families)
     double rows_all_ranks = 0.0;  // sum of `rows` over the ranks (M-step noise), exchanged on first use; 0 = unknown
     // Overlapping segments of a non-aliased cut (trial lengths that are not multiples of the window, vlgp/util.py:482-496).
     // In the reference they are VIEWS of the same trial rows: segment k + 1 starts its E-step from the mu, v that segment k
@@ -91,7 +94,7 @@ struct UnitSet {
     // runs stage by stage and the shared rows are copied forward before and back after each stage (vlgp_set_overlaps).
     std::vector<int> stage_start;   // unit index of the first unit of each stage, + M at the end; empty: no overlaps
     std::vector<int> link_start;    // per stage s: links [link_start[s], link_start[s + 1]) have their second unit in s
-    int* d_links = nullptr;         // (n_links, 3): first unit, second unit, shared rows
+    DevPtr<int> d_links;            // (n_links, 3): first unit, second unit, shared rows
     int n_links = 0;
     bool share_mu = true;           // false once the segments' mu was rebound (constrain_loading "svd")
     Replicas rep;                   // what a replicated set holds beside its own mu, v, w, dmu (default: not replicated)
@@ -168,25 +171,25 @@ struct ProfSlot {
 
 struct vlgp_ctx {
     int dev = 0;
-    hipStream_t stream = nullptr;
+    DevStream stream;
     int N = 0, L = 0, P = 0, R = 0;
     int n_cu = 256;
     std::vector<uint8_t> gauss;   // host copy
     int n_gauss = 0;
-    int* d_gauss = nullptr;       // (N) int flags
-    double *d_a = nullptr, *d_b = nullptr, *d_noise = nullptr, *d_da = nullptr, *d_db = nullptr;
+    DevPtr<int> d_gauss;          // (N) int flags
+    DevPtr<double> d_a, d_b, d_noise, d_da, d_db;
     bool have_params = false;
 
     std::map<int, Prior> priors;
     uint64_t prior_epoch = 1;
-    const double** d_prior_base = nullptr;  // table row -> compact base pointer
-    int* d_prior_rl = nullptr;              // (rows, L)
-    int64_t* d_prior_goff = nullptr;        // (rows, L)
+    DevPtr<const double*> d_prior_base;     // table row -> compact base pointer
+    DevPtr<int> d_prior_rl;                 // (rows, L)
+    DevPtr<int64_t> d_prior_goff;           // (rows, L)
     int prior_rows = 0;
     // mailbox of the prior kernel: per launch slot the L ranks, then a sequence word (mapped host memory)
-    int* h_prior_mb = nullptr;
-    int* d_prior_mb_host = nullptr;         // device view of h_prior_mb
-    int* d_prior_mb = nullptr;              // device slots + arrival counter
+    HostPtr<int> h_prior_mb;
+    DevPtr<int> d_prior_mb_host;            // device view of h_prior_mb (borrowed)
+    DevPtr<int> d_prior_mb;                 // device slots + arrival counter
     unsigned long long prior_seq = 0;
     std::vector<struct Prior*> prior_pending;   // launched, host-side ranks not taken yet (vlgp_prior_collect)
     unsigned long long prior_pending_seq = 0;
@@ -195,11 +198,10 @@ struct vlgp_ctx {
 
     // second execution lane: the M-step runs here, concurrently with the H-step
     // rounds on the main stream (they touch disjoint data: a, b vs omega)
-    hipStream_t mstream = nullptr;
-    double* d_work_m = nullptr;
-    int64_t work_m_len = 0;
-    int* d_fail_m = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_m_start = nullptr, ev_m_done = nullptr;
+    DevStream mstream;
+    GrowBuf<double> d_work_m;
+    DevPtr<int> d_fail_m;
+    DevEvent ev_fork, ev_m_start, ev_m_done;
     bool m_pending = false;
     // single rank: the M-step's launch sequence (52 launches at Mniter = 25) as an instantiated hipGraph, replayed while
     // its key (buffers, sizes, options) is unchanged: one enqueue instead of ~0.25 ms of host launch calls in front of
@@ -207,30 +209,26 @@ struct vlgp_ctx {
     void* m_graph_exec = nullptr;
     std::vector<double> m_graph_key;
 
-    double* d_ecols = nullptr;    // E-step per-channel records + wconst (fast kernel), rebuilt per launch
-    int* d_fail = nullptr;        // device failure counter
-    unsigned long long* d_clk = nullptr;  // E-step per-phase cycle counters (debug), 8 slots
-    double* d_work = nullptr;     // general workspace (M-step partials, H-step, reductions)
-    int64_t work_len = 0;
-    double* h_pinned = nullptr;   // small pinned staging buffer
-    int64_t pinned_len = 0;
+    DevPtr<double> d_ecols;       // E-step per-channel records + wconst (fast kernel), rebuilt per launch
+    DevPtr<int> d_fail;           // device failure counter
+    DevPtr<unsigned long long> d_clk;     // E-step per-phase cycle counters (debug), 8 slots
+    GrowBuf<double> d_work;       // general workspace (M-step partials, H-step, reductions)
+    HostGrowBuf<double> h_pinned; // small pinned staging buffer
     // H-step round kernel: device flags/counter and the mapped host mailbox it publishes to
-    unsigned* d_hsync = nullptr;
-    double* h_hres = nullptr;     // 48 results + sequence word
-    double* d_hres = nullptr;     // device view of h_hres
+    DevPtr<unsigned> d_hsync;
+    HostPtr<double> h_hres;       // 48 results + sequence word
+    DevPtr<double> d_hres;        // device view of h_hres (borrowed)
     unsigned h_seq = 0;
-    double* d_hmpart = nullptr;   // their partial sums by chunks of segments
+    GrowBuf<double> d_hmpart;     // their partial sums by chunks of segments
     bool hprep = false;           // vlgp_hstep_prepare built moments and the w copy for write_epoch hprep_epoch
-    hipEvent_t ev_e_done = nullptr;  // behind the last launch of the most recent vlgp_estep call (vlgp_estep_wait)
+    DevEvent ev_e_done;           // behind the last launch of the most recent vlgp_estep call (vlgp_estep_wait)
     bool e_done_valid = false;
     uint64_t hprep_epoch = 0, write_epoch = 0;  // write_epoch: bumped by every entry point that may change unit state
-    double* d_hmom = nullptr;     // (L, T, T) second moments of mu for the quadratic terms
-    int64_t hmom_len = 0;
+    GrowBuf<double> d_hmom;       // (L, T, T) second moments of mu for the quadratic terms
     const UnitSet* hmom_us = nullptr;
     int hmom_T = 0;
     bool hmom_bracket = false;    // inside vlgp_hstep_begin/end: d_hmom stays valid across objective calls
-    double* d_hwlm = nullptr;     // inside the bracket: w of the set latent-major, (L, rows), for the round kernels
-    int64_t hwlm_len = 0;
+    GrowBuf<double> d_hwlm;       // inside the bracket: w of the set latent-major, (L, rows), for the round kernels
     bool hwlm_valid = false;
     // low-rank H-step round (hstep_lr.h): per (window, dt, tol) the largest omega whose folded kernel blocks have rank <= r
     struct LrThr { int T; double dt, tol; std::vector<double> om; };
@@ -249,8 +247,7 @@ struct vlgp_ctx {
     // profiling
     bool prof_on = false;
     ProfSlot prof[VLGP_PROF_KINDS];
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct PendingProf { int kind; hipEvent_t a, b; double units; bool done; };
+    struct PendingProf { int kind; DevEvent a, b; double units; bool done; };
     std::vector<PendingProf> pending;
 
     // communication (comm.hip): the main lane and the M-step lane's own (collectives of one communicator must not interleave)
@@ -259,34 +256,33 @@ struct vlgp_ctx {
     int rank = 0, world = 1;
 
     // second lane of the split E-step (estep_split.hip): half of the unit set runs its sweeps here
-    hipStream_t elane[VLGP_E_LANES - 1] = {};
-    hipEvent_t ev_e_fork = nullptr, ev_e_join[VLGP_E_LANES - 1] = {};
+    DevStream elane[VLGP_E_LANES - 1];
+    DevEvent ev_e_fork, ev_e_join[VLGP_E_LANES - 1];
     int last_estep_path = 0;      // VLGP_PATH_ESTEP_* of the most recent E-step / update_w / update_v launch
     int lds_max = 64 * 1024;      // hipDeviceAttributeMaxSharedMemoryPerBlock (gfx950: 160 KB)
 
     // Pieces of an EM iteration's tail taken off its critical path (api.hip):
     // (1) the norms of mu, dmu for the stopping rule: one kernel queued behind the E-step, results in mapped host memory
-    double* d_xwork = nullptr;    // 1024 x 2 partial sums | ticket
-    double* h_xres = nullptr;     // mapped: |mu|^2, |dmu|^2, sequence word
-    double* d_xres = nullptr;     // its device view
+    DevPtr<double> d_xwork;       // 1024 x 2 partial sums | ticket
+    HostPtr<double> h_xres;       // mapped: |mu|^2, |dmu|^2, sequence word
+    DevPtr<double> d_xres;        // its device view (borrowed)
     unsigned long long x_seq = 0;
     int x_pending = 0;            // 1: queued (sequence x_seq), 2: deferred to vlgp_norms_end (several ranks)
     int x_set = -1;
     // (2) the M-step lane leaves a, b, noise, da, db and its failure count in pinned memory behind its last kernel
-    double* h_msnap = nullptr;    // mapped host memory
-    double* d_msnap = nullptr;    // its device view
+    HostPtr<double> h_msnap;      // mapped host memory
+    DevPtr<double> d_msnap;       // its device view (borrowed)
     bool msnap_valid = false;
     // (3) vlgp_set_params / vlgp_apply_latent_map stage through their own pinned (and device) buffers, reuse guarded by
     // an event: no stream synchronisation in front of the E-step's first launch
-    double* h_stage_par = nullptr;
-    double* h_stage_map = nullptr;
-    double* d_stage_map = nullptr;
-    hipEvent_t ev_stage_par = nullptr, ev_stage_map = nullptr;
+    HostPtr<double> h_stage_par;
+    HostPtr<double> h_stage_map;
+    DevPtr<double> d_stage_map;
+    DevEvent ev_stage_par, ev_stage_map;
     bool stage_par_busy = false, stage_map_busy = false;
 
     // vlgp_elbo's own device buffer (partials, sums, terms, flags): it never borrows d_work, which a prepared H-step owns
-    double* d_elbo = nullptr;
-    int64_t elbo_len = 0;
+    GrowBuf<double> d_elbo;
 
     std::string err;
 };
@@ -319,6 +315,15 @@ int vlgp_fail(vlgp_ctx* ctx, int code, const char* fmt, ...);
         int rc__ = (expr);        \
         if (rc__ != VLGP_OK) return rc__; \
     } while (0)
+
+// the device view of a mapped host block: borrowed, it goes with the block
+template <class T>
+inline int device_view(vlgp_ctx* ctx, DevPtr<T>& d, const HostPtr<T>& h) {
+    void* p = nullptr;
+    HIPCHK(ctx, hipHostGetDevicePointer(&p, h.get(), 0));
+    d.borrow(static_cast<T*>(p));
+    return VLGP_OK;
+}
 
 int vlgp_ensure_work(vlgp_ctx* ctx, int64_t n_doubles);
 int vlgp_ensure_pinned(vlgp_ctx* ctx, int64_t n_doubles);

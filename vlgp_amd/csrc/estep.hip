@@ -446,7 +446,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
     } else {  // (a replicated set: x.b of the source rows; it takes the split E-step or an error, never another family)
         UnitSet& src = vlgp_rows_owner(ctx, us);
         if (!src.x_ones) CHK(vlgp_refresh_xb(ctx, src));
-        us.d_xb = src.d_xb;
+        if (&src != &us) us.d_xb.borrow(src.d_xb);
     }
 
     // ranks and LDS demands over the priors this set uses
@@ -537,12 +537,7 @@ int launch_estep(vlgp_ctx* ctx, UnitSet& us, int mode, int n_iter, double dmu_bo
         lc_total = lcsz * us.M;
         A.lc_stride = lcsz;
     }
-    if (us.scratch_len < need + lc_total) {
-        if (us.d_scratch) HIPCHK(ctx, hipFree(us.d_scratch));
-        us.d_scratch = nullptr;
-        HIPCHK(ctx, hipMalloc(&us.d_scratch, (size_t)(need + lc_total) * 8));
-        us.scratch_len = need + lc_total;
-    }
+    HIPCHK(ctx, us.d_scratch.ensure(need + lc_total, need + lc_total));
     A.scratch = us.d_scratch;
     if (lc_total) A.lc_global = us.d_scratch + need;
     A.rg = 64;

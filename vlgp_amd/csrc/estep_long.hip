@@ -560,12 +560,7 @@ int launch_estep_long(vlgp_ctx* ctx, UnitSet& us, EstepArgs A, int* handled, int
     }
     const int64_t need = 3 * us.rows * L;
     const int64_t part = (int64_t)NWL * L * 64;
-    if (us.scratch_len < need + part * us.M) {
-        if (us.d_scratch) HIPCHK(ctx, hipFree(us.d_scratch));
-        us.d_scratch = nullptr;
-        HIPCHK(ctx, hipMalloc(&us.d_scratch, (size_t)(need + part * us.M) * 8));
-        us.scratch_len = need + part * us.M;
-    }
+    HIPCHK(ctx, us.d_scratch.ensure(need + part * us.M, need + part * us.M));
     A.scratch = us.d_scratch;
     A.lc_global = us.d_scratch + need;  // here: per-unit partial-sum area
     A.lc_stride = part;

@@ -2120,15 +2120,9 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     const bool lng = P.lng;
     const LatentClasses& C = P.C;
     const int64_t nRL = P.nRL;
-    if (us.scratch_len < P.scratch_len) {
-        if (us.d_scratch) HIPCHK(ctx, hipFree(us.d_scratch));
-        us.d_scratch = nullptr;
-        us.scratch_len = 0;
-        HIPCHK(ctx, hipMalloc(&us.d_scratch, (size_t)P.scratch_len * 8));
-        us.scratch_len = P.scratch_len;
-    }
+    HIPCHK(ctx, us.d_scratch.ensure(P.scratch_len, P.scratch_len));
     // records + wconst in ctx->d_ecols
-    if (!ctx->d_ecols) HIPCHK(ctx, hipMalloc(&ctx->d_ecols, sizeof(double) * ((size_t)N * 50 + 32)));
+    if (!ctx->d_ecols) HIPCHK(ctx, ctx->d_ecols.alloc((size_t)N * 50 + 32));
     double* cols = ctx->d_ecols;
     double* wconst = ctx->d_ecols + (int64_t)N * 34;
     double* ycoef = wconst + 32;  // (N, LT), LT <= 10
@@ -2192,16 +2186,16 @@ int launch_estep_split(vlgp_ctx* ctx, UnitSet& us, EstepArgs E, const RankSummar
     const int kind = lng ? VLGP_PROF_ESTEP_LONG
                          : (P.maxra <= 16 ? VLGP_PROF_ESTEP_RA16 : (P.maxra <= 24 ? VLGP_PROF_ESTEP_RA24 : VLGP_PROF_ESTEP_RA32));
     vlgp_prof_begin(ctx, kind);
-    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.rep.d_xa) : nullptr, by_row};
+    Lane main_lane{ctx->stream, rep ? &XA : nullptr, rep ? reinterpret_cast<const ExclArgs*>(us.rep.d_xa.get()) : nullptr, by_row};
     int rc = VLGP_OK;
     if (with_mean) rc = run_ya(ctx, main_lane, A, LT, cols, ycoef);
 
     for (int h = 1; h < n_lanes; ++h) {
         if (ctx->elane[h - 1]) continue;
-        HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->elane[h - 1], hipStreamNonBlocking));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_e_join[h - 1], hipEventDisableTiming));
+        HIPCHK(ctx, hipStreamCreateWithFlags(ctx->elane[h - 1].put(), hipStreamNonBlocking));
+        HIPCHK(ctx, hipEventCreateWithFlags(ctx->ev_e_join[h - 1].put(), hipEventDisableTiming));
     }
-    if (n_lanes > 1 && !ctx->ev_e_fork) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_e_fork, hipEventDisableTiming));
+    if (n_lanes > 1 && !ctx->ev_e_fork) HIPCHK(ctx, hipEventCreateWithFlags(ctx->ev_e_fork.put(), hipEventDisableTiming));
     // the arguments of each lane's launches: `lat` keeps last / do_v from one launch of the lane to its next
     struct Half { SplitArgs pass, lat; Lane ln; int64_t rows; int M; };
     Half H[VLGP_E_LANES];

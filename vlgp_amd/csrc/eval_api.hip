@@ -202,14 +202,8 @@ extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, doubl
     if (!row_sums || !kl_terms) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_elbo needs row_sums and kl_terms");
     const int64_t rows = p.us->rows;
     const ElboLayout o = elbo_layout(rows, ctx->N, p.tasks, (rows + 255) / 256, row_ell != nullptr);
-    if (o.need > ctx->elbo_len) {  // the block is the context's and only grows: a fit under track_elbo calls once per iteration
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_elbo) HIPCHK(ctx, hipFree(ctx->d_elbo));
-        ctx->d_elbo = nullptr;
-        ctx->elbo_len = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_elbo, sizeof(double) * (size_t)(o.need + o.need / 4)));
-        ctx->elbo_len = o.need + o.need / 4;
-    }
+    // the block is the context's and only grows: a fit under track_elbo calls once per iteration
+    HIPCHK(ctx, ctx->d_elbo.ensure(o.need, o.need + o.need / 4, ctx->stream));
     double* d = ctx->d_elbo;
     int* d_flag = reinterpret_cast<int*>(d + o.flag);
     CHK(launch_elbo(ctx, *p.us, vb, p.rp, d + o.part, d + o.sums, row_ell ? d + o.rows : nullptr, d + o.terms, d_flag));

@@ -1101,12 +1101,7 @@ static int hstep_prepare_units(vlgp_ctx* ctx, UnitSet& us, int T, bool want_wlm,
     const int L = ctx->L, M = us.M;
     if (want_wlm && (!ctx->hwlm_valid || ctx->hmom_us != &us)) {
         const int64_t n = us.rows * L;
-        if (ctx->hwlm_len < n) {
-            if (ctx->d_hwlm) HIPCHK(ctx, hipFree(ctx->d_hwlm));
-            ctx->d_hwlm = nullptr; ctx->hwlm_len = 0;
-            HIPCHK(ctx, hipMalloc(&ctx->d_hwlm, sizeof(double) * (size_t)n));
-            ctx->hwlm_len = n;
-        }
+        HIPCHK(ctx, ctx->d_hwlm.ensure(n, n));
         hipLaunchKernelGGL(hstep_w_latent_major, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, L,
                            us.rows, us.w, ctx->d_hwlm);
         HIPCHK(ctx, hipGetLastError());
@@ -1115,14 +1110,11 @@ static int hstep_prepare_units(vlgp_ctx* ctx, UnitSet& us, int T, bool want_wlm,
     if (!want_mom) return VLGP_OK;
     const int HT = T <= 50 ? 50 : 64;
     constexpr int NCH = 64;
-    if (!ctx->d_hmom || ctx->hmom_len < (int64_t)L * HT * HT) {
-        if (ctx->d_hmom) HIPCHK(ctx, hipFree(ctx->d_hmom));
-        if (ctx->d_hmpart) HIPCHK(ctx, hipFree(ctx->d_hmpart));
-        ctx->d_hmom = nullptr; ctx->d_hmpart = nullptr;
-        HIPCHK(ctx, hipMalloc(&ctx->d_hmom, sizeof(double) * L * HT * HT));
-        HIPCHK(ctx, hipMalloc(&ctx->d_hmpart, sizeof(double) * (size_t)L * NCH * HT * HT));
-        ctx->hmom_len = (int64_t)L * HT * HT;
+    const int64_t n_mom = (int64_t)L * HT * HT;
+    if (ctx->d_hmom.len < n_mom || ctx->d_hmpart.len < n_mom * NCH) {  // (the two grow together)
         ctx->hmom_us = nullptr;
+        HIPCHK(ctx, ctx->d_hmom.ensure(n_mom, n_mom));
+        HIPCHK(ctx, ctx->d_hmpart.ensure(n_mom * NCH, n_mom * NCH));
     }
     if (ctx->hmom_us != &us || ctx->hmom_T != T) {
         if (HT == 50)
@@ -1204,11 +1196,11 @@ static int launch_hstep_impl(vlgp_ctx* ctx, UnitSet& us, int window, double dt, 
         double* hres = hp + 4 * n_eval + 8;
         {
             if (!ctx->d_hsync) {
-                HIPCHK(ctx, hipMalloc(&ctx->d_hsync, 32 * sizeof(unsigned)));
+                HIPCHK(ctx, ctx->d_hsync.alloc(32));
                 HIPCHK(ctx, hipMemsetAsync(ctx->d_hsync, 0, 32 * sizeof(unsigned), ctx->stream));
-                HIPCHK(ctx, hipHostMalloc(&ctx->h_hres, 64 * sizeof(double), hipHostMallocMapped));
+                HIPCHK(ctx, ctx->h_hres.alloc(64, hipHostMallocMapped));
                 memset(ctx->h_hres, 0, 64 * sizeof(double));
-                HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_hres), ctx->h_hres, 0));
+                CHK(device_view(ctx, ctx->d_hres, ctx->h_hres));
             }
             // second moments of mu: once per vlgp_hstep_begin bracket (or already there: vlgp_hstep_prepare), else per call
             if (!ctx->hmom_bracket) ctx->hmom_us = nullptr;

@@ -379,10 +379,10 @@ prior_compact_kernel(int T, int R, const double* G, const int* rl, double* out) 
 static int ensure_mailbox(vlgp_ctx* ctx) {
     if (ctx->h_prior_mb) return VLGP_OK;
     const size_t bytes = sizeof(int) * VLGP_PRIOR_SLOTS * VLGP_MAX_L + 64;
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_prior_mb), bytes, hipHostMallocMapped));
+    HIPCHK(ctx, ctx->h_prior_mb.alloc(bytes / sizeof(int), hipHostMallocMapped));
     memset(ctx->h_prior_mb, 0, bytes);
-    HIPCHK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_prior_mb_host), ctx->h_prior_mb, 0));
-    HIPCHK(ctx, hipMalloc(&ctx->d_prior_mb, sizeof(int) * VLGP_PRIOR_SLOTS * VLGP_MAX_L + 64));
+    CHK(device_view(ctx, ctx->d_prior_mb_host, ctx->h_prior_mb));
+    HIPCHK(ctx, ctx->d_prior_mb.alloc(bytes / sizeof(int)));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_prior_mb, 0, sizeof(int) * VLGP_PRIOR_SLOTS * VLGP_MAX_L + 64, ctx->stream));
     return VLGP_OK;
 }
@@ -493,14 +493,14 @@ int launch_compact_prior(vlgp_ctx* ctx, Prior& pr) {
     const int L = ctx->L, R = ctx->R, T = pr.T;
     CHK(vlgp_ensure_work(ctx, L + 8));
     CHK(vlgp_ensure_pinned(ctx, L + 8));
-    int* d_rank = reinterpret_cast<int*>(ctx->d_work);
+    int* d_rank = reinterpret_cast<int*>(ctx->d_work.get());
     hipLaunchKernelGGL(prior_rank_kernel, dim3(L), dim3(256), 0, ctx->stream, T, R, pr.d_full, d_rank);
     HIPCHK(ctx, hipGetLastError());
     const int gx = (int)((((int64_t)T * R) + 255) / 256);
     hipLaunchKernelGGL(prior_compact_kernel, dim3(gx > 64 ? 64 : gx, L), dim3(256), 0, ctx->stream, T, R, pr.d_full,
                        d_rank, pr.d_compact);
     HIPCHK(ctx, hipGetLastError());
-    int* h_rank = reinterpret_cast<int*>(ctx->h_pinned);
+    int* h_rank = reinterpret_cast<int*>(ctx->h_pinned.get());
     HIPCHK(ctx, hipMemcpyAsync(h_rank, d_rank, sizeof(int) * L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     pr.rl.assign(h_rank, h_rank + L);
