@@ -36,9 +36,9 @@ def V():
     return vlgp_amd
 
 
-def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, in_range=False):
+def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, in_range=False, rank=50):
     """Units with a given posterior (mu, v, w random and positive where they must be), parameters and the device-built
-    prior factors of `omega`.  in_range: mu = G c, as an E-step leaves it."""
+    prior factors of `omega` with `rank` columns.  in_range: mu = G c, as an E-step leaves it."""
     import vlgp_amd as V
     from vlgp_amd import synth
 
@@ -57,7 +57,7 @@ def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, in_range
     noise = np.where(gauss, 0.5 + rng.random(N), 1.0)
     omega = np.asarray(omega, dtype=float)
     sigma = np.ones(L)
-    with V.Engine(N, L, P, 50, gauss) as eng:
+    with V.Engine(N, L, P, rank, gauss) as eng:
         eng.build_prior(sorted(set(lengths)), omega, sigma)
         chol = {T: eng.get_prior(T) for T in sorted(set(lengths))}
     units = []
@@ -70,12 +70,13 @@ def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, in_range
         units.append({"y": t["y"], "x": lagged(t["y"], history) if history else None, "mu": mu,
                       "v": 0.05 * rng.random((T, L)) if vb else np.zeros((T, L)), "w": rng.uniform(0.05, 2.0, (T, L))})
     params = {"ydim": N, "zdim": L, "xdim": P, "a": a, "b": b, "noise": noise, "omega": omega, "sigma": sigma,
-              "rank": 50, "likelihood": np.where(gauss, "gaussian", "poisson"), "cholesky": chol}
+              "rank": rank, "likelihood": np.where(gauss, "gaussian", "poisson"), "cholesky": chol}
     return units, params, gauss
 
 
-def _device(V, units, params, gauss, vb, want_rows=True):
-    with V.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"], gauss) as eng:
+def _device(V, units, params, gauss, vb, want_rows=True, rank=None):
+    """vlgp_elbo on an engine of `rank` columns (default: the problem's own, params["rank"])."""
+    with V.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"] if rank is None else rank, gauss) as eng:
         eng.set_params(params["a"], params["b"], params["noise"])
         eng.upload(SET, units)
         for T, G in params["cholesky"].items():
@@ -125,14 +126,24 @@ CASES = {
     "c5_shape": ([100, 150, 200, 250, 100, 150, 200, 250], 40, 10, np.linspace(2e-2, 1e-3, 10), 10, 2, True, False),
     "twelve_latents": ([50] * 6, 14, 12, np.linspace(2e-2, 1e-3, 12), 0, 0, True, False),
     "map": ([50, 80, 50], 14, 3, [2e-2, 5e-3, 1e-3], 3, 0, False, True),
+    "rank_64_61_and_1": ([70, 130], 12, 3, [0.5, 1.5, 3.0], 2, 0, True, False),
 }
+# Engines of 64 columns: the rough omega of the case fills all 64, and every column from the listed rank on is zeroed (as
+# tests/joint_shapes.py cuts its factors): elbo_kl's two r x r matrices with every lane live, a rank that is no multiple
+# of 8, and rank 1; mu off the range of G and vb = True, so that all four terms are at work.
+CUT_RANKS = {"rank_64_61_and_1": [64, 61, 1]}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_device_terms_equal_the_numpy_statement(V, name):
     lengths, N, L, omega, n_gauss, history, vb, in_range = CASES[name]
     units, params, gauss = _problem(lengths, N, L, omega, seed=11, n_gauss=n_gauss, history=history, vb=vb,
-                                    in_range=in_range)
+                                    in_range=in_range, rank=64 if name in CUT_RANKS else 50)
+    for l, r in enumerate(CUT_RANKS.get(name, ())):
+        assert not in_range and vb
+        for G in params["cholesky"].values():
+            assert np.all(np.any(G[l] != 0.0, axis=0))  # (all 64 columns filled before the cut)
+            G[l][:, r:] = 0.0
     st = EN.statement(units, params["a"], params["b"], params["noise"], gauss, params["cholesky"], vb=vb)
     if name.startswith("ranks"):
         r = st["ranks"][0]
@@ -141,7 +152,10 @@ def test_device_terms_equal_the_numpy_statement(V, name):
         assert st["ranks"].max() == 50
     if in_range:
         assert np.max(st["terms"][:, :, 3] / st["mu_sq"]) < 1e-20
-    _compare(name, _device(V, units, params, gauss, vb), st, vb=vb)
+    dev = _device(V, units, params, gauss, vb)
+    if name in CUT_RANKS:
+        assert np.array_equal(dev[4], [CUT_RANKS[name]] * len(units)) and np.all(st["terms"][:, :, 3] > 1e-3 * st["mu_sq"])
+    _compare(name, dev, st, vb=vb)
 
 
 def _c1_session(V, track=False, iters=2, **kw):

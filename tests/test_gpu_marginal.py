@@ -29,9 +29,10 @@ def V():
     return vlgp_amd
 
 
-def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, clamp_channel=None):
+def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, clamp_channel=None, rank=R):
     """Units with a given posterior (mu, v, w random and positive where they must be), parameters and the oracle's prior
-    factors of `omega`, injected from the host.  clamp_channel: a channel whose linear predictor lies above the clamp."""
+    factors of `omega` with `rank` columns, injected from the host.  clamp_channel: a channel whose linear predictor lies
+    above the clamp."""
     from vlgp_amd import synth
 
     rng = np.random.default_rng(seed)
@@ -50,7 +51,7 @@ def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, clamp_ch
         b[1:] = -0.05 * rng.random((history, N))
     noise = np.where(gauss, 0.5 + rng.random(N), 1.0)
     omega = np.asarray(omega, dtype=float)
-    prior = O.build_prior(sorted(set(lengths)), omega, np.ones(L), R)
+    prior = O.build_prior(sorted(set(lengths)), omega, np.ones(L), rank)
     units = []
     for t in trials:
         T = t["y"].shape[0]
@@ -58,12 +59,13 @@ def _problem(lengths, N, L, omega, seed, n_gauss=0, history=0, vb=True, clamp_ch
                       "mu": 0.3 * rng.standard_normal((T, L)),
                       "v": 0.05 * rng.random((T, L)) if vb else np.zeros((T, L)), "w": rng.uniform(0.05, 2.0, (T, L))})
     params = {"ydim": N, "zdim": L, "xdim": P, "a": a, "b": b, "noise": noise, "omega": omega, "sigma": np.ones(L),
-              "rank": R, "likelihood": np.where(gauss, "gaussian", "poisson"), "cholesky": prior}
+              "rank": rank, "likelihood": np.where(gauss, "gaussian", "poisson"), "cholesky": prior}
     return units, params, gauss
 
 
-def _engine(V, units, params, gauss):
-    eng = V.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"], gauss)
+def _engine(V, units, params, gauss, rank=None):
+    """An engine of `rank` columns (default: the problem's own, params["rank"]) holding the units, parameters and factors."""
+    eng = V.Engine(params["ydim"], params["zdim"], params["xdim"], params["rank"] if rank is None else rank, gauss)
     eng.set_params(params["a"], params["b"], params["noise"])
     eng.upload(SET, units)
     for T, G in params["cholesky"].items():
@@ -76,8 +78,8 @@ def _device(V, units, params, gauss, eps, vb=True):
         return eng.marginal(SET, eps, vb=vb, want_parts=True)
 
 
-def _eps(units, L, K, seed=1):
-    return np.random.default_rng(seed).standard_normal((len(units), L, R, K))
+def _eps(units, L, K, seed=1, rank=R):
+    return np.random.default_rng(seed).standard_normal((len(units), L, rank, K))
 
 
 def _compare(name, dev, st):
@@ -107,14 +109,23 @@ CASES = {
     "long_rank50": ([1000, 1000, 1000], 10, 2, [1e-3, 2e-3], 0, 0, True, None, 3),
     "above_the_clamp": ([50, 65], 8, 2, [2e-2, 1e-3], 0, 0, True, 3, 5),
     "map": ([50, 80, 50], 14, 3, [2e-2, 5e-3, 1e-3], 3, 0, False, None, 5),
+    "rank_64_61_and_1": ([70, 130], 10, 3, [0.5, 1.5, 3.0], 2, 0, True, None, 5),
 }
+# Engines of 64 columns: the rough omega of the case fills all 64, and every column from the listed rank on is zeroed (as
+# tests/joint_shapes.py cuts its factors): marginal_task with every lane live, a rank that is no multiple of 8, and rank 1.
+CUT_RANKS = {"rank_64_61_and_1": [64, 61, 1]}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_device_weights_equal_the_numpy_statement(V, name):
     lengths, N, L, omega, n_gauss, history, vb, clamp, K = CASES[name]
+    rank = 64 if name in CUT_RANKS else R
     units, params, gauss = _problem(lengths, N, L, omega, seed=11, n_gauss=n_gauss, history=history, vb=vb,
-                                    clamp_channel=clamp)
+                                    clamp_channel=clamp, rank=rank)
+    for l, r in enumerate(CUT_RANKS.get(name, ())):
+        for G in params["cholesky"].values():
+            assert np.all(np.any(G[l] != 0.0, axis=0))  # (all 64 columns filled before the cut)
+            G[l][:, r:] = 0.0
     ranks = np.array([[FN.rank(params["cholesky"][T][l]) for l in range(L)] for T in sorted(set(lengths))])
     if name.startswith("ranks"):
         r = ranks[0]
@@ -123,9 +134,14 @@ def test_device_weights_equal_the_numpy_statement(V, name):
         assert ranks.max() == 50
     if clamp is not None:
         assert np.all(units[0]["mu"] @ params["a"][:, clamp] + params["b"][0, clamp] > 10.0)
-    eps = _eps(units, L, K)
+    eps = _eps(units, L, K, rank=rank)
     st = MN.statement(units, params["a"], params["b"], params["noise"], gauss, params["cholesky"], eps, vb=vb)
-    _compare(name, _device(V, units, params, gauss, eps, vb=vb), st)
+    with _engine(V, units, params, gauss) as eng:
+        dev = eng.marginal(SET, eps, vb=vb, want_parts=True)
+        dev_ranks = eng.unit_ranks(SET)
+    if name in CUT_RANKS:
+        assert np.array_equal(ranks, [CUT_RANKS[name]] * 2) and np.array_equal(dev_ranks, [CUT_RANKS[name]] * len(units))
+    _compare(name, dev, st)
 
 
 @pytest.fixture(scope="module")
