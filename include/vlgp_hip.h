@@ -405,6 +405,26 @@ int vlgp_mstep_begin(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, double
                      double learning_rate, double da_bound, double db_bound);
 int vlgp_mstep_end(vlgp_ctx* ctx, int* n_failed, double* device_ms);
 
+/* core.mstep under a full Gaussian posterior per row: the M-step of an EM whose E-step is the joint
+ * Laplace posterior (vlgp_joint_posterior).  mu (rows, L) and cov (rows, L (L + 1) / 2), pair (l, l'), l' <= l, at
+ * l (l + 1) / 2 + l' as vlgp_joint_posterior packs it, are host arrays over the rows of the set; they are uploaded once
+ * and stay on the device for all n_iter Newton iterations.  The set's own mu and v are not read.  With q_tn = C_t a_n
+ * and s2_tn = a_n . q_tn:
+ *   eta = mu a + x b,   r = exp(min(eta + s2 / 2, 10)),   noise = var(y - eta) at the parameters entering the last iteration;
+ *   Poisson channel:   grad_a = mu'y_n - sum_t r_tn (mu_t + q_tn),   nhess_a = sum_t r_tn [(mu_t + q_tn)(mu_t + q_tn)' + C_t],
+ *                      grad_b, nhess_b, eps, learning_rate, da_bound, db_bound, da, db as vlgp_mstep;
+ *   Gaussian channel:  vlgp_mstep's alternating least squares with mu'mu + sum_t C_t for mu'mu + diag(sum_t v_t).
+ * A cov without off-diagonal entries gives vlgp_mstep on a set whose v is its diagonal, to rounding.
+ * Takes plain sets and cuts; replicated and masked sets: VLGP_ERR_STATE.  L > 10, P > 8,
+ * VLGP_MSTEP_GENERIC set or a communicator of more than one rank: VLGP_ERR_STATE with the reason.  A null mu or cov or
+ * n_iter < 1: VLGP_ERR_ARG naming the argument.  A non-finite value in mu or cov (the rows of a unit whose Newton
+ * iteration failed) is found by a first pass on the device: VLGP_ERR_ARG naming the first such row.  After any of these
+ * no parameter has changed.  Waits for a pending M-step and norms pass and returns when the parameters are written;
+ * *n_failed (may be NULL) counts the channels whose system was not positive definite.  Fixed-order sums, no atomics on
+ * doubles: the same bits on every run. */
+int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
+                   double eps, double learning_rate, double da_bound, double db_bound, int* n_failed);
+
 /* ---- H-step ----------------------------------------------------------- */
 /* The objective scipy's L-BFGS-B minimises in gp.optimze1d (vlgp/gp.py:100-123):
  * construct_posterior_cov (gp.py:126-147) + elbo (gp.py:12-43), mask [0,1,0].

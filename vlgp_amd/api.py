@@ -15,7 +15,7 @@ from . import engine as E
 from .preprocess import fill_params, fill_trials, get_config, get_params, initialize
 from .util import _per_trial_entries, segment_starts
 
-__all__ = ["fit", "transform", "forecast", "FitSession", "bind_priors"]
+__all__ = ["fit", "transform", "forecast", "refit_joint", "FitSession", "bind_priors"]
 
 logger = logging.getLogger(__name__)
 
@@ -401,6 +401,96 @@ def transform(trials, params, config, device=0):
         E.infer(dev, params, config)
         dev.pull()
     return trials
+
+
+def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, newton_tol=1e-10, device=0, verbose=True,
+                comm=None):
+    """Laplace EM: refit ``a``, ``b`` and ``noise`` under the joint Laplace posterior of every whole trial.
+
+    ``trials, params, config`` as ``fit`` or ``transform`` return them.  ``omega``, ``sigma`` and the prior factors are
+    those of ``params`` and are not re-estimated; no loading constraint is applied, the fixed prior sets the scale.  With
+    ``E_k`` the sum over trials of the Laplace evidence under ``params_k``:
+
+    1. ``post_k`` = the joint posterior of every trial under ``params_k`` (``Engine.joint_posterior``, ``newton_iter``
+       factorisations at most, decrement ``newton_tol``), started from the caller's ``mu, w`` every time;
+    2. ``runtime["joint"]``: ``"laplace"`` gets ``E_k``, ``"n_newton"`` the largest count of the iteration,
+       ``"converged"`` whether every trial did;
+    3. if ``k >= 1`` and ``E_k - E_{k-1} <= tol |E_k|``: stop with ``(params_k, post_k)`` if ``E_k >= E_{k-1}``, else with
+       ``(params_{k-1}, post_{k-1})``;
+    4. if ``k == max_iter``: stop with ``(params_k, post_k)``;
+    5. else ``params_{k+1}`` = ``Engine.mstep_cov`` of ``post_k`` with ``config``'s M-step settings.
+
+    So the returned posterior is the posterior of the returned parameters.  For all-Gaussian channels the E-step is exact
+    and this is GPFA's EM in the low-rank prior.  A trial whose ``H`` cannot be factored raises ``VlgpError`` before an
+    M-step sees its rows.  Trials carrying ``missing``, a ``comm`` and trials without ``mu`` or ``w`` raise ``ValueError``.
+
+    Returns a new ``{"trials", "params", "config"}``; the caller's dicts are not modified.  Every trial copy has ``mu``
+    (the mode), ``v`` (the diagonal of ``cov``), ``cov`` (T, L, L) and ``w`` from ``update_w`` at that ``mu`` under the
+    returned parameters; ``params`` has the new ``a, b, noise, da, db``; ``config["runtime"]["joint"]`` the trace."""
+    if comm is not None:
+        raise ValueError("refit_joint runs on one rank: vlgp_mstep_cov takes no communicator (comm must be None)")
+    for i, tr in enumerate(trials):
+        if tr.get("missing") is not None:
+            raise ValueError("refit_joint: trial %d carries 'missing': the covariance M-step takes no masked set" % i)
+        if tr.get("mu") is None or tr.get("w") is None:
+            raise ValueError("refit_joint: trial %d has no 'mu' / 'w': pass trials as fit or transform return them" % i)
+    echo = _echo if verbose else (lambda msg: None)
+    L = int(params["zdim"])
+    lengths = [int(tr["y"].shape[0]) for tr in trials]
+    bounds = np.concatenate([[0], np.cumsum(lengths)])
+    units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "w": tr["w"],
+              "v": tr["v"] if tr.get("v") is not None else np.zeros((T, L))} for tr, T in zip(trials, lengths)]
+    trace = {"laplace": [], "n_newton": [], "converged": []}
+    m_args = (int(config["Mniter"]), config["use_hessian"], config["eps"], config["learning_rate"], config["da_bound"],
+              config["db_bound"])
+    out_params = dict(params)
+    with E.Engine.for_params(params, device) as eng:
+        eng.set_params(params["a"], params["b"], params["noise"])
+        eng.upload(SET_TRIALS, units)
+        bind_priors(eng, trials, out_params)  # (its own dict: the caller's params["cholesky"] stays as it is)
+        cur = (np.array(params["a"], dtype=float), np.array(params["b"], dtype=float), np.array(params["noise"], dtype=float),
+               None, None)
+        prev = None  # (parameters, posterior, evidence) of the iteration before
+        k = 0
+        while True:
+            post = eng.joint_posterior(SET_TRIALS, max_iter=newton_iter, tol=newton_tol)
+            if post["n_failed"]:
+                raise E.VlgpError("refit_joint: H of %d trial(s) could not be factored at iteration %d"
+                                  % (post["n_failed"], k))
+            ev = float(np.sum(post["laplace"]))
+            trace["laplace"].append(ev)
+            trace["n_newton"].append(int(np.max(post["n_newton"])))
+            trace["converged"].append(bool(np.all(post["converged"])))
+            echo("refit_joint %d: laplace %.6f, Newton %d%s" % (k, ev, trace["n_newton"][-1],
+                                                              "" if trace["converged"][-1] else " (not converged)"))
+            if prev is not None and ev - prev[2] <= tol * abs(ev):
+                if not ev >= prev[2]:
+                    cur, post = prev[0], prev[1]
+                    eng.set_params(*cur[:3])
+                break
+            if k == max_iter:
+                break
+            prev = (cur, post, ev)
+            bad = eng.mstep_cov(SET_TRIALS, post["mu"], post["cov"], *m_args)
+            if bad:
+                logger.error("%d Newton systems were singular (gradient step taken)", bad)
+            cur = eng.get_params()
+            k += 1
+        # w of the mode under the returned parameters, which the engine holds
+        v = np.ascontiguousarray(np.diagonal(post["cov"], axis1=1, axis2=2))
+        eng.upload(SET_TRIALS, [dict(u, mu=post["mu"][s:e], v=v[s:e]) for u, s, e in zip(units, bounds[:-1], bounds[1:])])
+        eng.update_w(SET_TRIALS)
+        w = eng.download(SET_TRIALS, ("w",))["w"]
+    out_trials = []
+    for tr, s, e in zip(trials, bounds[:-1], bounds[1:]):
+        out_trials.append(dict(tr, mu=post["mu"][s:e].copy(), v=v[s:e].copy(), cov=post["cov"][s:e].copy(), w=w[s:e].copy()))
+    a, b, noise, da, db = cur
+    out_params.update(a=a, b=b, noise=noise)
+    if da is not None:
+        out_params.update(da=da, db=db)
+    out_config = dict(config)
+    out_config["runtime"] = dict(config.get("runtime") or {}, joint=trace)
+    return {"trials": out_trials, "params": out_params, "config": out_config}
 
 
 def _full_factors(eng, lengths, params):

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <new>
 
+#include "call_block.h"
 #include "ctx.h"
 
 static thread_local std::string g_create_err;
@@ -134,6 +135,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_marginal, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_joint_laplace, NOT_REPLICATED, nullptr)                                                                    \
     X(vlgp_joint_posterior, NOT_REPLICATED | SET_MASKED_FIT, nullptr)                                                 \
+    X(vlgp_mstep_cov, NOT_REPLICATED, nullptr)                                                                        \
     X(vlgp_stash_mu, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_set_overlaps, NOT_REPLICATED, nullptr) /* (and equal-length units that are no tiling cut: see there) */    \
     X(vlgp_unshare_mu, NOT_REPLICATED, nullptr)                                                                       \
@@ -1052,6 +1054,48 @@ extern "C" int vlgp_mstep(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, d
     if (n_iter < 1) return VLGP_OK;  // core.py:131-133
     CHK(vlgp_mstep_begin(ctx, set, n_iter, use_hessian, eps, lr, da_bound, db_bound));
     return vlgp_mstep_end(ctx, n_failed, nullptr);
+}
+
+// core.mstep under a full covariance per row (mstep_cov.hip).  Opens as an entry point that writes
+// parameters; every refusal comes before the first launch that writes one: the admission, the limits and arguments
+// (mstep_cov_refusal, call_block.h), then a pass over the uploaded moments for a non-finite value.
+extern "C" int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
+                              double eps, double lr, double da_bound, double db_bound, int* n_failed) {
+    NEED_CTX(ctx);
+    if (n_failed) *n_failed = 0;
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_mstep_cov));
+    const MstepCovRefusal r = mstep_cov_refusal(ctx->L, ctx->P, ctx->sw.mstep_generic, ctx->world, mu, cov, n_iter);
+    if (r.status) return vlgp_fail(ctx, r.status, "%s", r.text);
+    if (!(da_bound > 0) || !(db_bound > 0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "da_bound/db_bound must be positive");
+    const int64_t rows = us->rows;
+    const int L = ctx->L;
+    const MstepCovLayout o = mstep_cov_layout(rows, L);
+    hipStream_t st = ctx->mstream;
+    HIPCHK(ctx, ctx->d_mcov.ensure(o.need, o.need + o.need / 4 + 1024, st));
+    // the M-step lane starts after everything already queued on the main stream
+    HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+    HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_fork, 0));
+    double* B = ctx->d_mcov;
+    unsigned long long first = (unsigned long long)rows;
+    unsigned long long* d_first = reinterpret_cast<unsigned long long*>(B + o.first);
+    HIPCHK(ctx, hipMemcpyAsync(d_first, &first, sizeof(first), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(B + o.mu, mu, sizeof(double) * (size_t)(rows * L), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(B + o.cov, cov, sizeof(double) * (size_t)(o.need - o.cov), hipMemcpyHostToDevice, st));
+    CHK(launch_mcov_first_bad_row(ctx, rows, B + o.mu, B + o.cov, d_first, st));
+    HIPCHK(ctx, hipMemcpyAsync(&first, d_first, sizeof(first), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (first < (unsigned long long)rows)
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_mstep_cov: mu or cov of row %lld is not finite (the rows of a unit whose "
+                         "Newton iteration failed?)", (long long)first);
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_fail_m, 0, sizeof(int), st));
+    ctx->msnap_valid = false;
+    CHK(launch_mstep_cov(ctx, *us, B + o.mu, B + o.cov, n_iter, use_hessian, eps, lr, da_bound, db_bound));
+    int nf = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&nf, ctx->d_fail_m, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (n_failed) *n_failed = nf;
+    return VLGP_OK;
 }
 
 extern "C" int vlgp_hstep_objective(vlgp_ctx* ctx, int set, int window, double dt, int n_eval, const int* latent,

@@ -98,8 +98,31 @@ inline JointPosteriorLayout joint_posterior_layout(int64_t work, int64_t rows, i
     return {b.doubles(work), b.doubles(8 * M), b.doubles(rows * (L * (L + 1) / 2)), b.need()};
 }
 
+// vlgp_mstep_cov: the first row with a non-finite moment (one 64-bit integer) | mu (rows, L) | cov (rows, L (L + 1) / 2),
+// the handle's own buffer (vlgp_ctx::d_mcov), on the device for all Newton iterations of the call
+struct MstepCovLayout { int64_t first, mu, cov, need; };
+inline MstepCovLayout mstep_cov_layout(int64_t rows, int64_t L) {
+    BlockLayout b;
+    return {b.i64(1), b.doubles(rows * L), b.doubles(rows * (L * (L + 1) / 2)), b.need()};
+}
+// ... and what the call refuses before anything reaches the device: status 0 (VLGP_OK), -1 (VLGP_ERR_ARG, the text names
+// the argument) or -3 (VLGP_ERR_STATE, the text says why) -- the limits of the compiled kernels first, then the arguments
+struct MstepCovRefusal { int status; const char* text; };
+inline MstepCovRefusal mstep_cov_refusal(int L, int P, bool generic_switch, int world, const void* mu, const void* cov,
+                                         int n_iter) {
+    if (L > 10) return {-3, "vlgp_mstep_cov: more than 10 latents (L > 10): the loop-based M-step kernels take no covariance"};
+    if (P > 8) return {-3, "vlgp_mstep_cov: more than 8 regressors (P > 8): the loop-based M-step kernels take no covariance"};
+    if (generic_switch) return {-3, "vlgp_mstep_cov: VLGP_MSTEP_GENERIC is set: the loop-based M-step kernels take no covariance"};
+    if (world > 1) return {-3, "vlgp_mstep_cov: more than one rank"};
+    if (!mu) return {-1, "vlgp_mstep_cov needs mu"};
+    if (!cov) return {-1, "vlgp_mstep_cov needs cov"};
+    if (n_iter < 1) return {-1, "vlgp_mstep_cov: n_iter must be at least 1"};
+    return {0, nullptr};
+}
+
 #ifdef __HIPCC__
 #include "ctx.h"
+static_assert(VLGP_ERR_ARG == -1 && VLGP_ERR_STATE == -3, "mstep_cov_refusal spells the status codes out");
 
 // The call's own device block.  Leaving the call, by whichever return, waits for what the call queued on the stream and
 // frees the block: early CHK / HIPCHK returns are safe.

@@ -200,6 +200,7 @@ struct vlgp_ctx {
     // rounds on the main stream (they touch disjoint data: a, b vs omega)
     DevStream mstream;
     GrowBuf<double> d_work_m;
+    GrowBuf<double> d_mcov;       // vlgp_mstep_cov: first bad row | mu | cov of the call (mstep_cov_layout, call_block.h)
     DevPtr<int> d_fail_m;
     DevEvent ev_fork, ev_m_start, ev_m_done;
     bool m_pending = false;
@@ -383,6 +384,14 @@ static_assert(EP_LEN == VLGP_ESTEP_PLAN_LEN, "vlgp_debug_estep_plan: the report'
 int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double eps, double lr,
                  double da_bound, double db_bound);
 int mstep_plan_report(vlgp_ctx* ctx, int64_t rows, int out[12]);  // vlgp_debug_mstep_plan: what launch_mstep would launch
+// the M-step under a supplied posterior (vlgp_mstep_cov; mstep_cov.hip): d_mu (rows, L) and d_cov (rows, L (L + 1) / 2),
+// pair (l, l'), l' <= l, at l (l + 1) / 2 + l', take the place of the set's mu, v.  One rank, L <= 10, P <= 8, the
+// compiled kernels: the caller has checked.  launch_mcov_first_bad_row: *d_first = the first row of (mu | cov) with a
+// non-finite value, untouched when there is none.
+int launch_mstep_cov(vlgp_ctx* ctx, UnitSet& us, const double* d_mu, const double* d_cov, int n_iter, int use_hessian,
+                     double eps, double lr, double da_bound, double db_bound);
+int launch_mcov_first_bad_row(vlgp_ctx* ctx, int64_t rows, const double* d_mu, const double* d_cov, unsigned long long* d_first,
+                              hipStream_t st);
 int launch_hstep(vlgp_ctx* ctx, UnitSet& us, int window, double dt, int n_eval, const int* latent,
                  const double* logp, double* ll, double* dll);
 // factor the listed priors (bit-exact ichol_gauss), ranks and compact copies included; returns with pr.rl set

@@ -1144,6 +1144,26 @@ int launch_moments(vlgp_ctx* ctx, UnitSet& us) {
     return latent_moments(ctx, us, d_partial, ctx->d_work, LANE_MAIN);
 }
 
+// the fixed-order sum of the partials and the per-channel solves in one launch (single rank): which instantiation of
+// mstep_sum_solve_kernel, ONE place for launch_mstep and launch_mstep_cov (mstep_cov.hip)
+static void launch_sum_solve(vlgp_ctx* ctx, hipStream_t st, const double* d_part, int G, int64_t n, double* d_stats,
+                             unsigned* d_ticket, const SolveArgs& S) {
+    const dim3 sg((unsigned)((n + MS_OUT - 1) / MS_OUT));
+    const int fixed = solve_fixed(S.L, S.P);
+    const bool anyg = solve_anyg(ctx, fixed);
+#define MS_SUM_SOLVE(F)                                                                                                  \
+    do {                                                                                                                  \
+        if (anyg) hipLaunchKernelGGL((mstep_sum_solve_kernel<F, true>), sg, dim3(512), 0, st, d_part, G, n, d_stats, d_ticket, S);  \
+        else hipLaunchKernelGGL((mstep_sum_solve_kernel<F, false>), sg, dim3(512), 0, st, d_part, G, n, d_stats, d_ticket, S);      \
+    } while (0)
+    if (fixed == 3) MS_SUM_SOLVE(3);
+    else if (fixed == 5) MS_SUM_SOLVE(5);
+    else if (fixed == 8) MS_SUM_SOLVE(8);
+    else if (fixed == 10) MS_SUM_SOLVE(10);
+#undef MS_SUM_SOLVE
+    else hipLaunchKernelGGL(mstep_sum_solve_kernel<0>, sg, dim3(512), 0, st, d_part, G, n, d_stats, d_ticket, S);
+}
+
 int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double eps, double lr,
                  double da_bound, double db_bound) {
     const int N = ctx->N, L = ctx->L, P = ctx->P;
@@ -1277,21 +1297,7 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
             vlgp_prof_end(ctx, VLGP_PROF_MSTEP, (double)us.rows, st);
             CHK(rc);
             if (ctx->world == 1) {  // no all-reduce between the sum and the solves: one launch for both
-                const int64_t n = (int64_t)Kn * N;
-                const dim3 sg((unsigned)((n + MS_OUT - 1) / MS_OUT));
-                const int fixed = solve_fixed(L, P);
-                const bool anyg = solve_anyg(ctx, fixed);
-#define MS_SUM_SOLVE(F)                                                                                                  \
-    do {                                                                                                                  \
-        if (anyg) hipLaunchKernelGGL((mstep_sum_solve_kernel<F, true>), sg, dim3(512), 0, st, d_part, g.G, n, d_stats, d_ticket, S);  \
-        else hipLaunchKernelGGL((mstep_sum_solve_kernel<F, false>), sg, dim3(512), 0, st, d_part, g.G, n, d_stats, d_ticket, S);      \
-    } while (0)
-                if (fixed == 3) MS_SUM_SOLVE(3);
-                else if (fixed == 5) MS_SUM_SOLVE(5);
-                else if (fixed == 8) MS_SUM_SOLVE(8);
-                else if (fixed == 10) MS_SUM_SOLVE(10);
-#undef MS_SUM_SOLVE
-                else hipLaunchKernelGGL(mstep_sum_solve_kernel<0>, sg, dim3(512), 0, st, d_part, g.G, n, d_stats, d_ticket, S);
+                launch_sum_solve(ctx, st, d_part, g.G, (int64_t)Kn * N, d_stats, d_ticket, S);
                 HIPCHK(ctx, hipGetLastError());
                 continue;
             }
@@ -1320,3 +1326,6 @@ int launch_mstep(vlgp_ctx* ctx, UnitSet& us, int n_iter, int use_hessian, double
     HIPCHK(ctx, hipGraphLaunch(exec, st));
     return VLGP_OK;
 }
+
+// the M-step under a full covariance per row (vlgp_mstep_cov): this translation unit's reduce and solve kernels, one more pass
+#include "mstep_cov.hip"

@@ -580,6 +580,26 @@ class Engine:
                                      C.byref(n) if count else None))
         return n.value
 
+    def mstep_cov(self, set_id, mu, cov, n_iter, use_hessian=True, eps=1e-8, learning_rate=1.0, da_bound=5.0,
+                  db_bound=5.0):
+        """``mstep`` under a full Gaussian posterior per row (vlgp_mstep_cov): ``mu`` (rows of the set, L) and ``cov``
+        (those rows, L, L) -- symmetric, checked -- or packed as ``joint_posterior`` unpacks it take the place of the
+        set's ``mu, v``, which are not read.  A ``cov`` without off-diagonal entries is ``mstep`` on a set whose ``v`` is
+        its diagonal.  Plain sets and cuts, one rank, ``L <= 10``, ``P <= 8``; a non-finite moment is an error that names
+        its row and changes no parameter.  Returns the number of channels whose system was not positive definite."""
+        if mu is None or cov is None:
+            raise ValueError("mu and cov go together: a posterior mean and covariance per row of the set")
+        cov = np.asarray(cov, dtype=float)
+        if cov.ndim == 3:  # (the lower triangle is what goes to the device: an asymmetric cov would be silently halved)
+            gap = np.abs(cov - cov.transpose(0, 2, 1))
+            if np.any(gap > 1e-9 * max(1.0, float(np.nanmax(np.abs(cov), initial=0.0)))):
+                raise ValueError("cov must be symmetric in its last two axes")
+        mu, cov = self._moments(set_id, mu, cov)
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_mstep_cov(self.h, int(set_id), dptr(mu), dptr(cov), int(n_iter), int(bool(use_hessian)),
+                                         float(eps), float(learning_rate), float(da_bound), float(db_bound), C.byref(n)))
+        return n.value
+
     def mstep_begin(self, set_id, n_iter, use_hessian=True, eps=1e-8, learning_rate=1.0, da_bound=5.0,
                     db_bound=5.0):
         """Enqueue the M-step on the engine's second stream and return at once."""
