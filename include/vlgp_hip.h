@@ -153,7 +153,9 @@ int vlgp_replicate_units(vlgp_ctx* ctx, int src, int dst, int n_rep, const int* 
  * set a, b, da, db are those of `src`, bit for bit, and noise is that of its two-pass form.  A channel with no observed
  * row keeps a, b, noise and is not counted in *n_failed.  The masked M-step is VLGP_ERR_STATE, the message naming the
  * reason, with a Gaussian channel on the handle, on the loop-based kernels (P > 8, VLGP_MSTEP_GENERIC), beyond 10
- * latents and with more than one rank.  vlgp_elbo, vlgp_forecast, vlgp_project_units, cuts, merges, stashes and
+ * latents and with more than one rank.  The Laplace EM takes it too: vlgp_joint_posterior (the Newton E-step never
+ * reads a missing entry) and vlgp_mstep_cov_masked (that M-step under the posterior's covariance per row; a set
+ * without a mask goes to vlgp_mstep_cov).  vlgp_elbo, vlgp_forecast, vlgp_project_units, cuts, merges, stashes and
  * overlaps refuse a masked fit set like every replicated set; a group-replica set and a masked set of several
  * replicas are refused by all of the above (the whole table: DESIGN.md 4.6). */
 int vlgp_replicate_masked(vlgp_ctx* ctx, int src, int dst, int n_rep, const uint64_t* held_out);
@@ -424,6 +426,20 @@ int vlgp_mstep_end(vlgp_ctx* ctx, int* n_failed, double* device_ms);
  * doubles: the same bits on every run. */
 int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
                    double eps, double learning_rate, double da_bound, double db_bound, int* n_failed);
+/* vlgp_mstep_cov of a masked fit set (vlgp_replicate_masked with one replica): every channel over the
+ * rows where it is observed -- mu'y, x'y, every gradient and Hessian sum above with sum_t running over the observed rows
+ * of channel n, and noise = the variance of y - eta over those rows.  mu, cov over the rows of the set (the source's
+ * rows), as vlgp_joint_posterior on that set returns them; the set's own mu, v are not read.  What y holds at a missing
+ * entry, NaN included, reaches no sum; with no bit set a, b, da, db are vlgp_mstep_cov's on the source set, bit for bit,
+ * and noise is that of its two-pass form (VLGP_NOISE_PASSES).  A channel with no observed row keeps a, b, noise, steps by
+ * 0 and is not counted in *n_failed, whatever eps is.
+ * Takes a masked fit set only: a set without a mask is VLGP_ERR_STATE naming vlgp_mstep_cov, group replicas and masked
+ * sets of several replicas are refused as replicated.  A Gaussian channel on the handle, L > 10, P > 8,
+ * VLGP_MSTEP_GENERIC set or more than one rank: VLGP_ERR_STATE with the reason.  A null mu or cov or n_iter < 1:
+ * VLGP_ERR_ARG naming the argument; a non-finite value in mu or cov: VLGP_ERR_ARG naming the first such row.  After any
+ * of these no parameter has changed.  Everything else as vlgp_mstep_cov. */
+int vlgp_mstep_cov_masked(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
+                          double eps, double learning_rate, double da_bound, double db_bound, int* n_failed);
 
 /* ---- H-step ----------------------------------------------------------- */
 /* The objective scipy's L-BFGS-B minimises in gp.optimze1d (vlgp/gp.py:100-123):

@@ -89,6 +89,8 @@ _SIGNATURES = {
     "vlgp_mstep_end": (C.c_int, [_h, _ip, _dp]),
     "vlgp_mstep_cov": (C.c_int, [_h, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                  C.c_double, _ip]),
+    "vlgp_mstep_cov_masked": (C.c_int, [_h, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, _ip]),
     "vlgp_hstep_objective": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, C.c_int, _ip, _dp, _dp, _dp]),
     "vlgp_sample_posterior": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _ip]),
     "vlgp_comm_host_exchange": (C.c_int, [_h]),

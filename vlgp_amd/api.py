@@ -404,7 +404,7 @@ def transform(trials, params, config, device=0):
 
 
 def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, newton_tol=1e-10, device=0, verbose=True,
-                comm=None):
+                comm=None, missing=None):
     """Laplace EM: refit ``a``, ``b`` and ``noise`` under the joint Laplace posterior of every whole trial.
 
     ``trials, params, config`` as ``fit`` or ``transform`` return them.  ``omega``, ``sigma`` and the prior factors are
@@ -422,24 +422,53 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
 
     So the returned posterior is the posterior of the returned parameters.  For all-Gaussian channels the E-step is exact
     and this is GPFA's EM in the low-rank prior.  A trial whose ``H`` cannot be factored raises ``VlgpError`` before an
-    M-step sees its rows.  Trials carrying ``missing``, a ``comm`` and trials without ``mu`` or ``w`` raise ``ValueError``.
+    M-step sees its rows.  A ``comm`` and trials without ``mu`` or ``w`` raise ``ValueError``.
+
+    ``missing``: a list per trial of (T, N) bool arrays, True where the observation is absent, as ``fit`` and
+    ``evaluation.impute`` take it; by default the trials' own ``missing`` arrays when every trial carries one, as the
+    trials of ``fit(..., missing=)`` do (some trials carrying one and some not is a ``ValueError``).  The same loop on a
+    masked fit set: the posterior does not see the missing entries, ``E_k`` is the evidence of the observed ones, the
+    M-step is ``Engine.mstep_cov_masked`` (every channel over its observed rows) and ``w`` sums over a row's observed
+    channels.  What ``y`` holds at a missing entry is never read.  Poisson channels only, and every channel needs an
+    observed entry: each a ``ValueError`` otherwise.  Every returned trial carries its ``missing`` array.
 
     Returns a new ``{"trials", "params", "config"}``; the caller's dicts are not modified.  Every trial copy has ``mu``
     (the mode), ``v`` (the diagonal of ``cov``), ``cov`` (T, L, L) and ``w`` from ``update_w`` at that ``mu`` under the
     returned parameters; ``params`` has the new ``a, b, noise, da, db``; ``config["runtime"]["joint"]`` the trace."""
     if comm is not None:
         raise ValueError("refit_joint runs on one rank: vlgp_mstep_cov takes no communicator (comm must be None)")
+    if missing is None:
+        carried = [tr.get("missing") is not None for tr in trials]
+        if any(carried) and not all(carried):
+            raise ValueError("refit_joint: trial %d carries 'missing' and trial %d does not: pass missing= for all of them"
+                             % (carried.index(True), carried.index(False)))
+        if any(carried):
+            missing = [tr["missing"] for tr in trials]
     for i, tr in enumerate(trials):
-        if tr.get("missing") is not None:
-            raise ValueError("refit_joint: trial %d carries 'missing': the covariance M-step takes no masked set" % i)
         if tr.get("mu") is None or tr.get("w") is None:
             raise ValueError("refit_joint: trial %d has no 'mu' / 'w': pass trials as fit or transform return them" % i)
+    if missing is not None:
+        if np.any(np.asarray(params["likelihood"]) == "gaussian"):
+            raise ValueError("refit_joint(missing=...) takes Poisson channels only: a Gaussian channel's update needs "
+                             "per-channel masked Gram matrices")
+        missing = [np.array(m, dtype=bool) for m in _per_trial_entries(missing, trials, "missing", bool)]
+        n_obs = sum((~m).sum(axis=0) for m in missing)
+        if np.any(n_obs == 0):
+            raise ValueError("refit_joint(missing=...): channel(s) %s have no observed entry" % np.flatnonzero(n_obs == 0).tolist())
     echo = _echo if verbose else (lambda msg: None)
     L = int(params["zdim"])
     lengths = [int(tr["y"].shape[0]) for tr in trials]
     bounds = np.concatenate([[0], np.cumsum(lengths)])
     units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "w": tr["w"],
               "v": tr["v"] if tr.get("v") is not None else np.zeros((T, L))} for tr, T in zip(trials, lengths)]
+    work = SET_TRIALS  # the set the loop runs on
+    if missing is not None:
+        # private copies of y with 0.0 in the holes: the by-row passes behind update_w leave an entry out by a zero
+        # coefficient, under which a NaN in the caller's y would survive.  The fill value reaches no result.
+        for u, m in zip(units, missing):
+            u["y"] = np.where(m, 0.0, u["y"]).astype(float)
+        mask_rows = np.concatenate(missing, axis=0)
+        work = SET_TRIALS_MASKED
     trace = {"laplace": [], "n_newton": [], "converged": []}
     m_args = (int(config["Mniter"]), config["use_hessian"], config["eps"], config["learning_rate"], config["da_bound"],
               config["db_bound"])
@@ -447,13 +476,16 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
     with E.Engine.for_params(params, device) as eng:
         eng.set_params(params["a"], params["b"], params["noise"])
         eng.upload(SET_TRIALS, units)
+        if missing is not None:  # the masked fit set: the same rows, one mask bit per entry, the source's mu, v, w
+            eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=mask_rows[None])
+        mstep = eng.mstep_cov if missing is None else eng.mstep_cov_masked
         bind_priors(eng, trials, out_params)  # (its own dict: the caller's params["cholesky"] stays as it is)
         cur = (np.array(params["a"], dtype=float), np.array(params["b"], dtype=float), np.array(params["noise"], dtype=float),
                None, None)
         prev = None  # (parameters, posterior, evidence) of the iteration before
         k = 0
         while True:
-            post = eng.joint_posterior(SET_TRIALS, max_iter=newton_iter, tol=newton_tol)
+            post = eng.joint_posterior(work, max_iter=newton_iter, tol=newton_tol)
             if post["n_failed"]:
                 raise E.VlgpError("refit_joint: H of %d trial(s) could not be factored at iteration %d"
                                   % (post["n_failed"], k))
@@ -471,19 +503,25 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
             if k == max_iter:
                 break
             prev = (cur, post, ev)
-            bad = eng.mstep_cov(SET_TRIALS, post["mu"], post["cov"], *m_args)
+            bad = mstep(work, post["mu"], post["cov"], *m_args)
             if bad:
                 logger.error("%d Newton systems were singular (gradient step taken)", bad)
             cur = eng.get_params()
             k += 1
         # w of the mode under the returned parameters, which the engine holds
         v = np.ascontiguousarray(np.diagonal(post["cov"], axis1=1, axis2=2))
+        if missing is not None:
+            eng.free_units(SET_TRIALS_MASKED)  # (its source takes no new contents while a replica aliases its rows)
         eng.upload(SET_TRIALS, [dict(u, mu=post["mu"][s:e], v=v[s:e]) for u, s, e in zip(units, bounds[:-1], bounds[1:])])
-        eng.update_w(SET_TRIALS)
-        w = eng.download(SET_TRIALS, ("w",))["w"]
+        if missing is not None:
+            eng.replicate(SET_TRIALS, SET_TRIALS_MASKED, held_out=mask_rows[None])
+        eng.update_w(work)
+        w = eng.download(work, ("w",))["w"]
     out_trials = []
-    for tr, s, e in zip(trials, bounds[:-1], bounds[1:]):
+    for i, (tr, s, e) in enumerate(zip(trials, bounds[:-1], bounds[1:])):
         out_trials.append(dict(tr, mu=post["mu"][s:e].copy(), v=v[s:e].copy(), cov=post["cov"][s:e].copy(), w=w[s:e].copy()))
+        if missing is not None:
+            out_trials[-1]["missing"] = missing[i]
     a, b, noise, da, db = cur
     out_params.update(a=a, b=b, noise=noise)
     if da is not None:

@@ -136,6 +136,8 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_joint_laplace, NOT_REPLICATED, nullptr)                                                                    \
     X(vlgp_joint_posterior, NOT_REPLICATED | SET_MASKED_FIT, nullptr)                                                 \
     X(vlgp_mstep_cov, NOT_REPLICATED, nullptr)                                                                        \
+    X(vlgp_mstep_cov_masked, SET_MASKED_FIT,                                                                          \
+      "vlgp_mstep_cov_masked takes a masked fit set (set %d has no mask: vlgp_mstep_cov takes it)")                   \
     X(vlgp_stash_mu, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_set_overlaps, NOT_REPLICATED, nullptr) /* (and equal-length units that are no tiling cut: see there) */    \
     X(vlgp_unshare_mu, NOT_REPLICATED, nullptr)                                                                       \
@@ -1059,14 +1061,9 @@ extern "C" int vlgp_mstep(vlgp_ctx* ctx, int set, int n_iter, int use_hessian, d
 // core.mstep under a full covariance per row (mstep_cov.hip).  Opens as an entry point that writes
 // parameters; every refusal comes before the first launch that writes one: the admission, the limits and arguments
 // (mstep_cov_refusal, call_block.h), then a pass over the uploaded moments for a non-finite value.
-extern "C" int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
-                              double eps, double lr, double da_bound, double db_bound, int* n_failed) {
-    NEED_CTX(ctx);
-    if (n_failed) *n_failed = 0;
-    UnitSet* us = nullptr;
-    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_mstep_cov));
-    const MstepCovRefusal r = mstep_cov_refusal(ctx->L, ctx->P, ctx->sw.mstep_generic, ctx->world, mu, cov, n_iter);
-    if (r.status) return vlgp_fail(ctx, r.status, "%s", r.text);
+// (the part vlgp_mstep_cov and vlgp_mstep_cov_masked share: the set is admitted and the arguments are checked)
+static int mstep_cov_run(vlgp_ctx* ctx, const char* who, UnitSet* us, const double* mu, const double* cov, int n_iter,
+                         int use_hessian, double eps, double lr, double da_bound, double db_bound, int* n_failed) {
     if (!(da_bound > 0) || !(db_bound > 0)) return vlgp_fail(ctx, VLGP_ERR_ARG, "da_bound/db_bound must be positive");
     const int64_t rows = us->rows;
     const int L = ctx->L;
@@ -1086,8 +1083,8 @@ extern "C" int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const do
     HIPCHK(ctx, hipMemcpyAsync(&first, d_first, sizeof(first), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (first < (unsigned long long)rows)
-        return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_mstep_cov: mu or cov of row %lld is not finite (the rows of a unit whose "
-                         "Newton iteration failed?)", (long long)first);
+        return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: mu or cov of row %lld is not finite (the rows of a unit whose "
+                         "Newton iteration failed?)", who, (long long)first);
     HIPCHK(ctx, hipMemsetAsync(ctx->d_fail_m, 0, sizeof(int), st));
     ctx->msnap_valid = false;
     CHK(launch_mstep_cov(ctx, *us, B + o.mu, B + o.cov, n_iter, use_hessian, eps, lr, da_bound, db_bound));
@@ -1096,6 +1093,29 @@ extern "C" int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const do
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (n_failed) *n_failed = nf;
     return VLGP_OK;
+}
+extern "C" int vlgp_mstep_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
+                              double eps, double lr, double da_bound, double db_bound, int* n_failed) {
+    NEED_CTX(ctx);
+    if (n_failed) *n_failed = 0;
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_mstep_cov));
+    const MstepCovRefusal r = mstep_cov_refusal(ctx->L, ctx->P, ctx->sw.mstep_generic, ctx->world, mu, cov, n_iter);
+    if (r.status) return vlgp_fail(ctx, r.status, "%s", r.text);
+    return mstep_cov_run(ctx, "vlgp_mstep_cov", us, mu, cov, n_iter, use_hessian, eps, lr, da_bound, db_bound, n_failed);
+}
+// ... of a masked fit set: every channel over its observed rows.  The same frame and the same order of
+// refusals, the Gaussian channel first among the limits (mstep_cov_masked_refusal).
+extern "C" int vlgp_mstep_cov_masked(vlgp_ctx* ctx, int set, const double* mu, const double* cov, int n_iter, int use_hessian,
+                                     double eps, double lr, double da_bound, double db_bound, int* n_failed) {
+    NEED_CTX(ctx);
+    if (n_failed) *n_failed = 0;
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_JOIN | OPEN_PARAMS | OPEN_DEVICE, &us, &admit_vlgp_mstep_cov_masked));
+    const MstepCovRefusal r = mstep_cov_masked_refusal(ctx->n_gauss, ctx->L, ctx->P, ctx->sw.mstep_generic, ctx->world, mu,
+                                                       cov, n_iter);
+    if (r.status) return vlgp_fail(ctx, r.status, "%s", r.text);
+    return mstep_cov_run(ctx, "vlgp_mstep_cov_masked", us, mu, cov, n_iter, use_hessian, eps, lr, da_bound, db_bound, n_failed);
 }
 
 extern "C" int vlgp_hstep_objective(vlgp_ctx* ctx, int set, int window, double dt, int n_eval, const int* latent,

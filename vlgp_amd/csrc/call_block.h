@@ -119,6 +119,21 @@ inline MstepCovRefusal mstep_cov_refusal(int L, int P, bool generic_switch, int 
     if (n_iter < 1) return {-1, "vlgp_mstep_cov: n_iter must be at least 1"};
     return {0, nullptr};
 }
+// vlgp_mstep_cov_masked (a masked fit set; the moments' block is mstep_cov_layout): the same order, after the one thing the
+// masked kernels cannot do at all -- a Gaussian channel's least squares would need a masked Gram matrix per channel
+inline MstepCovRefusal mstep_cov_masked_refusal(int n_gauss, int L, int P, bool generic_switch, int world, const void* mu,
+                                                const void* cov, int n_iter) {
+    if (n_gauss > 0) return {-3, "vlgp_mstep_cov_masked: the handle has Gaussian channels (their least-squares update needs "
+                                 "per-channel masked Gram matrices)"};
+    if (L > 10) return {-3, "vlgp_mstep_cov_masked: more than 10 latents (L > 10): the loop-based M-step kernels take no covariance"};
+    if (P > 8) return {-3, "vlgp_mstep_cov_masked: more than 8 regressors (P > 8): the loop-based M-step kernels take no covariance"};
+    if (generic_switch) return {-3, "vlgp_mstep_cov_masked: VLGP_MSTEP_GENERIC is set: the loop-based M-step kernels take no covariance"};
+    if (world > 1) return {-3, "vlgp_mstep_cov_masked: more than one rank"};
+    if (!mu) return {-1, "vlgp_mstep_cov_masked needs mu"};
+    if (!cov) return {-1, "vlgp_mstep_cov_masked needs cov"};
+    if (n_iter < 1) return {-1, "vlgp_mstep_cov_masked: n_iter must be at least 1"};
+    return {0, nullptr};
+}
 
 #ifdef __HIPCC__
 #include "ctx.h"

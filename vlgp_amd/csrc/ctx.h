@@ -387,7 +387,8 @@ int mstep_plan_report(vlgp_ctx* ctx, int64_t rows, int out[12]);  // vlgp_debug_
 // the M-step under a supplied posterior (vlgp_mstep_cov; mstep_cov.hip): d_mu (rows, L) and d_cov (rows, L (L + 1) / 2),
 // pair (l, l'), l' <= l, at l (l + 1) / 2 + l', take the place of the set's mu, v.  One rank, L <= 10, P <= 8, the
 // compiled kernels: the caller has checked.  launch_mcov_first_bad_row: *d_first = the first row of (mu | cov) with a
-// non-finite value, untouched when there is none.
+// non-finite value, untouched when there is none.  A masked fit set (vlgp_mstep_cov_masked; no Gaussian channel on the
+// handle: checked too) takes the masked PREP and noise passes and mstep_cov_accum_masked.
 int launch_mstep_cov(vlgp_ctx* ctx, UnitSet& us, const double* d_mu, const double* d_cov, int n_iter, int use_hessian,
                      double eps, double lr, double da_bound, double db_bound);
 int launch_mcov_first_bad_row(vlgp_ctx* ctx, int64_t rows, const double* d_mu, const double* d_cov, unsigned long long* d_first,

@@ -45,143 +45,21 @@ __device__ __forceinline__ int mcov_slot(int k, int L, int P) {
 
 // lane <-> channel, S row slices per workgroup, as mstep_accum; A.v is cov (rows, tri(L)), pair (l, l'), l' <= l, at
 // l (l + 1) / 2 + l' whatever L is: in a row padded to tri(LT) every pair keeps its place.
+//
+// MASKED (vlgp_mstep_cov_masked): a masked fit set, every channel over its observed rows.  The sums are
+// linear in the rate, so a missing entry puts 0 there by a select, as mstep_accum<..., K_NEWTON | K_MASKED, ...> does --
+// never a product with 0 -- and with no bit set the sums are the unmasked kernel's, bit for bit.  A.mask sits in the
+// slot of A.gauss (a masked handle has no Gaussian channel), A.nobs in the slot of A.mean.  One body
+// (mstep_cov_accum.inc) behind two kernel names: the unmasked kernel keeps its symbol and its code.
 template <int LT, int PT>
 __global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_cov_accum(MArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NA = nacc_cov<LT, PT>();
-    const int N = A.N, CT = A.CT, S = A.S, L = A.L, P = A.P;
-    const int TL = tri(L);
-    const int tid = threadIdx.x;
-    const int nl = tid % CT, s = tid / CT;
-    const int n = blockIdx.y * CT + nl;
-    const bool active = s < S && n < N;
-    constexpr int TLT = tri(LT);
-    constexpr int tile_d = MC_TILE * (LT + TLT);  // mu tile | cov tile, rows padded to the compiled size with zeros
-    double* red = smem;                       // aliases the tiles after the row loop: MS_GS x (S CT)
-    const int red_d = MS_GS * S * CT;
-    double* etab = smem + (tile_d > red_d ? tile_d : red_d);
-    fast_exp_tab_init(etab, tid);
-
-    double al[LT], bl[PT], acc[NA];
-#pragma unroll
-    for (int l = 0; l < LT; ++l) al[l] = (active && l < L) ? A.a[l * N + n] : 0.0;
-#pragma unroll
-    for (int j = 0; j < PT; ++j) bl[j] = (active && j < P) ? A.b[j * N + n] : 0.0;
-#pragma unroll
-    for (int k = 0; k < NA; ++k) acc[k] = 0.0;
-    const bool gch = active ? A.gauss[n] != 0 : false;
-
-    const int64_t c0 = (int64_t)blockIdx.x * A.rows_per_wg;
-    int64_t c1 = c0 + A.rows_per_wg;
-    if (c1 > A.rows) c1 = A.rows;
-    double* mu_t = smem;
-    double* c_t = smem + MC_TILE * LT;
-    // (the padding is written here, once per tile: the row loop reads LT and tri(LT) doubles a row without a predicate)
-    auto copy_tile = [&](int64_t t0) {
-        const int nr = (int)((c1 - t0) < MC_TILE ? (c1 - t0) : MC_TILE);
-        for (int i = tid; i < nr * LT; i += blockDim.x) {
-            const int r = i / LT, l = i - r * LT;
-            mu_t[i] = l < L ? A.mu[(t0 + r) * L + l] : 0.0;
-        }
-        for (int i = tid; i < nr * TLT; i += blockDim.x) {
-            const int r = i / TLT, k = i - r * TLT;
-            c_t[i] = k < TL ? A.v[(t0 + r) * TL + k] : 0.0;
-        }
-    };
-    if (c0 < c1) copy_tile(c0);
-    __syncthreads();
-    for (int64_t t0 = c0; t0 < c1; t0 += MC_TILE) {
-        const int nr = (int)((c1 - t0) < MC_TILE ? (c1 - t0) : MC_TILE);
-        const bool more = t0 + MC_TILE < c1;
-        if (active && !gch) {  // Gaussian channels need no rate statistics
-            for (int rr = s; rr < nr; rr += S) {
-                const int64_t row = t0 + rr;
-                double xv[PT];
-#pragma unroll
-                for (int j = 0; j < PT; ++j) xv[j] = (j < P) ? (A.x ? A.x[(row * P + j) * N + n] : 1.0) : 0.0;
-                const double* cr = c_t + rr * TLT;
-                double mt[LT], q[LT];
-#pragma unroll
-                for (int l = 0; l < LT; ++l) q[l] = 0.0;
-                // q = C a over the packed lower triangle: each pair once, both of its products
-#pragma unroll
-                for (int i = 0; i < LT; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) {
-                        const double c = cr[tri(i) + j];
-                        q[i] = fma(c, al[j], q[i]);
-                        if (j < i) q[j] = fma(c, al[i], q[j]);
-                    }
-                double eta = 0.0;
-#pragma unroll
-                for (int j = 0; j < PT; ++j) eta = fma(xv[j], bl[j], eta);
-                double s2 = 0.0;
-#pragma unroll
-                for (int l = 0; l < LT; ++l) {
-                    const double m = mu_t[rr * LT + l];
-                    eta = fma(m, al[l], eta);
-                    s2 = fma(al[l], q[l], s2);
-                    mt[l] = m + q[l];
-                }
-                const double rate = trunc_exp_tab64(fma(0.5, s2, eta), etab);
-                // the Hessian reads the row's C from LDS again: held in registers across the exponential, its tri(L)
-                // doubles spill at five latents and 128 registers
-                asm volatile("" ::: "memory");
-                int k = 0;
-#pragma unroll
-                for (int l = 0; l < LT; ++l) { acc[k] = fma(rate, mt[l], acc[k]); ++k; }
-#pragma unroll
-                for (int i = 0; i < LT; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) {
-                        const double c = cr[tri(i) + j];
-                        acc[k] = fma(rate, fma(mt[i], mt[j], c), acc[k]);
-                        ++k;
-                    }
-#pragma unroll
-                for (int j = 0; j < PT; ++j) { acc[k] = fma(xv[j], rate, acc[k]); ++k; }
-#pragma unroll
-                for (int i = 0; i < PT; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) { acc[k] = fma(xv[i] * xv[j], rate, acc[k]); ++k; }
-            }
-        }
-        if (more) {
-            __syncthreads();  // everybody is done with the tile
-            copy_tile(t0 + MC_TILE);
-        }
-        __syncthreads();
-    }
-    // slices -> one partial per workgroup, as mstep_accum
-    const int K = 2 * L + TL + P + tri(P);
-    const int SC = S * CT;
-#pragma unroll
-    for (int g0 = 0; g0 < NA; g0 += MS_GS) {
-        if (s < S) {
-#pragma unroll
-            for (int j = 0; j < MS_GS; ++j)
-                if (g0 + j < NA) red[j * SC + s * CT + nl] = active ? acc[g0 + j] : 0.0;
-        }
-        __syncthreads();
-        for (int o = tid; o < MS_GS * CT; o += blockDim.x) {
-            const int j = o / CT, c = o - j * CT;
-            int ke = -1;
-#pragma unroll
-            for (int jj = 0; jj < MS_GS; ++jj)
-                if (g0 + jj < NA && jj == j) ke = mcov_slot<LT, PT>(g0 + jj, L, P);
-            const int nn = blockIdx.y * CT + c;
-            if (ke >= 0 && nn < N) {
-                double t = 0.0;
-                for (int qs = 0; qs < S; ++qs) t += red[j * SC + qs * CT + c];
-                A.partial[((int64_t)blockIdx.x * K + ke) * N + nn] = t;
-            }
-        }
-        if (g0 + MS_GS < NA) __syncthreads();
-    }
-    for (int o = tid; o < L * CT; o += blockDim.x) {  // the r'v slots: zeros
-        const int l = o / CT, nn = blockIdx.y * CT + (o - l * CT);
-        if (nn < N) A.partial[((int64_t)blockIdx.x * K + L + TL + l) * N + nn] = 0.0;
-    }
+    constexpr bool MASKED = false;
+#include "mstep_cov_accum.inc"
+}
+template <int LT, int PT>
+__global__ void __launch_bounds__(512, (LT <= 5 ? 4 : (LT <= 8 ? 2 : 1))) mstep_cov_accum_masked(MArgs A) {
+    constexpr bool MASKED = true;
+#include "mstep_cov_accum.inc"
 }
 
 // first row of (mu | cov) that holds a non-finite value: *first = its index, left alone (rows) when all are finite.
@@ -249,6 +127,32 @@ static int launch_cov_accum(vlgp_ctx* ctx, const Geometry& g, const MArgs& A) {
     }
     return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_mstep_cov: more than 10 latents (L = %d)", A.L);
 }
+// the same matrix of the masked kernel (A.mask, A.nobs set): the unmasked launch's grid, workgroup and LDS
+template <int LT>
+static int launch_cov_masked_p(vlgp_ctx* ctx, const Geometry& g, const MArgs& A) {
+    const dim3 grid(g.G, g.tiles), blk(g.nthr);
+    const size_t lds = mcov_lds(g, LT);
+    hipStream_t st = ctx->mstream;
+    switch (accum_pt(A.P)) {
+        case 1: hipLaunchKernelGGL((mstep_cov_accum_masked<LT, 1>), grid, blk, lds, st, A); break;
+        case 2: hipLaunchKernelGGL((mstep_cov_accum_masked<LT, 2>), grid, blk, lds, st, A); break;
+        case 4: hipLaunchKernelGGL((mstep_cov_accum_masked<LT, 4>), grid, blk, lds, st, A); break;
+        case 8: hipLaunchKernelGGL((mstep_cov_accum_masked<LT, 8>), grid, blk, lds, st, A); break;
+        default: return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_mstep_cov_masked: more than 8 regressors (P = %d)", A.P);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return VLGP_OK;
+}
+static int launch_cov_masked(vlgp_ctx* ctx, const Geometry& g, const MArgs& A) {
+    switch (A.L <= 10 ? accum_lt(A.L) : 0) {
+        case 2: return launch_cov_masked_p<2>(ctx, g, A);
+        case 3: return launch_cov_masked_p<3>(ctx, g, A);
+        case 5: return launch_cov_masked_p<5>(ctx, g, A);
+        case 8: return launch_cov_masked_p<8>(ctx, g, A);
+        case 10: return launch_cov_masked_p<10>(ctx, g, A);
+    }
+    return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_mstep_cov_masked: more than 10 latents (L = %d)", A.L);
+}
 
 int launch_mcov_first_bad_row(vlgp_ctx* ctx, int64_t rows, const double* d_mu, const double* d_cov, unsigned long long* d_first,
                               hipStream_t st) {
@@ -262,9 +166,15 @@ int launch_mcov_first_bad_row(vlgp_ctx* ctx, int64_t rows, const double* d_mu, c
 
 // One rank, the compiled sizes (L <= 10, P <= 8), a set that is not replicated: the caller has checked.  Everything on
 // ctx->mstream with the M-step lane's workspace, launch by launch (no captured graph: the moments' block is the call's).
+// A masked fit set (vlgp_mstep_cov_masked; no Gaussian channel on the handle: checked as well) takes what the masked
+// launch_mstep takes -- K_PREP | K_MASKED, the noise by the two masked passes over each channel's own observed rows --
+// with mstep_cov_accum_masked as the Newton pass.
 int launch_mstep_cov(vlgp_ctx* ctx, UnitSet& us, const double* d_mu, const double* d_cov, int n_iter, int use_hessian,
                      double eps, double lr, double da_bound, double db_bound) {
     const int N = ctx->N, L = ctx->L, P = ctx->P;
+    const bool masked = us.is(SET_MASKED_FIT);
+    if (masked && (!us.rep.d_mask || !us.rep.d_nobs)) return vlgp_fail(ctx, VLGP_ERR_STATE, "vlgp_mstep_cov_masked: the set has no mask");
+    const int km = masked ? K_MASKED : 0;
     const Geometry g = plan(ctx, us.rows);
     const int Kp = nstat_rt(L, P, K_PREP), Kn = nstat_rt(L, P, K_NEWTON);
     const int Kl = tri(L) + 3 * L + 1;
@@ -287,6 +197,7 @@ int launch_mstep_cov(vlgp_ctx* ctx, UnitSet& us, const double* d_mu, const doubl
     A.y = us.y; A.x = us.x_ones ? nullptr : us.x; A.mu = d_mu;
     A.v = d_cov;  // (the PREP and noise passes stage rows x L doubles of it beside mu and read none of them)
     A.a = ctx->d_a; A.b = ctx->d_b; A.gauss = ctx->d_gauss; A.mean = d_mean; A.partial = d_part;
+    if (masked) A.mask = us.rep.d_mask;  // (in the slot of gauss: the Newton launch gets nobs in the slot of mean)
     auto reduce_to = [&](int K, double* dst) -> int {
         const int64_t n = (int64_t)K * N;
         hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n + 63) / 64)), dim3(512), 0, st, d_part, g.G, n, dst);
@@ -295,7 +206,7 @@ int launch_mstep_cov(vlgp_ctx* ctx, UnitSet& us, const double* d_mu, const doubl
     };
 
     // sweep-invariant moments: mu'y, x'y, x'mu, x'x; gram and column sums of mu; sum_t C_t for the Gaussian channels
-    CHK(launch_accum(ctx, K_PREP, g, A));
+    CHK(launch_accum(ctx, K_PREP | km, g, A));
     CHK(reduce_to(Kp, d_prep));
     {
         int G = (int)((us.rows + 255) / 256);
@@ -330,22 +241,30 @@ int launch_mstep_cov(vlgp_ctx* ctx, UnitSet& us, const double* d_mu, const doubl
     for (int it = 0; it < n_iter; ++it) {
         if (it == n_iter - 1) {
             // noise = var(y - eta) with the parameters entering the last iteration (core.py:177), as launch_mstep
-            if (!noise_by_passes(ctx)) {
+            if (!masked && !noise_by_passes(ctx)) {
                 hipLaunchKernelGGL(noise_stats_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, L, P, total_rows, d_prep, d_lat,
                                    ctx->d_a, ctx->d_b, ctx->d_noise);
                 HIPCHK(ctx, hipGetLastError());
             } else {
-                CHK(launch_accum(ctx, K_NOISE1, g, A));
+                CHK(launch_accum(ctx, K_NOISE1 | km, g, A));
                 CHK(reduce_to(1, d_s1));
-                hipLaunchKernelGGL(noise_mean_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, total_rows, d_s1, d_mean);
-                CHK(launch_accum(ctx, K_NOISE2, g, A));
+                if (masked) hipLaunchKernelGGL(noise_mean_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.rep.d_nobs, d_s1, d_mean);
+                else hipLaunchKernelGGL(noise_mean_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, total_rows, d_s1, d_mean);
+                CHK(launch_accum(ctx, K_NOISE2 | km, g, A));
                 CHK(reduce_to(1, d_s1));
-                hipLaunchKernelGGL(noise_final_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, total_rows, d_s1, ctx->d_noise);
+                if (masked) hipLaunchKernelGGL(noise_final_nobs_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, us.rep.d_nobs, d_s1, ctx->d_noise);
+                else hipLaunchKernelGGL(noise_final_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, total_rows, d_s1, ctx->d_noise);
                 HIPCHK(ctx, hipGetLastError());
             }
         }
         if (any_poisson) {
-            CHK(launch_cov_accum(ctx, g, A));
+            if (masked) {
+                MArgs An = A;
+                An.nobs = us.rep.d_nobs;  // (the Newton launch reads no mean)
+                CHK(launch_cov_masked(ctx, g, An));
+            } else {
+                CHK(launch_cov_accum(ctx, g, A));
+            }
             launch_sum_solve(ctx, st, d_part, g.G, (int64_t)Kn * N, d_stats, d_ticket, S);
             HIPCHK(ctx, hipGetLastError());
             continue;

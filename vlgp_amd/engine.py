@@ -587,6 +587,20 @@ class Engine:
         set's ``mu, v``, which are not read.  A ``cov`` without off-diagonal entries is ``mstep`` on a set whose ``v`` is
         its diagonal.  Plain sets and cuts, one rank, ``L <= 10``, ``P <= 8``; a non-finite moment is an error that names
         its row and changes no parameter.  Returns the number of channels whose system was not positive definite."""
+        return self._mstep_cov(self.lib.vlgp_mstep_cov, set_id, mu, cov, n_iter, use_hessian, eps, learning_rate, da_bound,
+                               db_bound)
+
+    def mstep_cov_masked(self, set_id, mu, cov, n_iter, use_hessian=True, eps=1e-8, learning_rate=1.0, da_bound=5.0,
+                         db_bound=5.0):
+        """``mstep_cov`` of a masked fit set (``replicate(src, dst, held_out=missing[None])``; vlgp_mstep_cov_masked): every
+        channel over the rows where it is observed, ``noise`` the variance over those rows; what ``y`` holds at a missing
+        entry is not read.  ``mu``, ``cov`` over the rows of the set, as ``joint_posterior`` of that set returns them.  A
+        channel without an observed row keeps ``a, b, noise``.  Poisson channels only; a set without a mask is an error
+        (``mstep_cov`` takes it).  Arguments, checks and return value as ``mstep_cov``."""
+        return self._mstep_cov(self.lib.vlgp_mstep_cov_masked, set_id, mu, cov, n_iter, use_hessian, eps, learning_rate,
+                               da_bound, db_bound)
+
+    def _mstep_cov(self, entry, set_id, mu, cov, n_iter, use_hessian, eps, learning_rate, da_bound, db_bound):
         if mu is None or cov is None:
             raise ValueError("mu and cov go together: a posterior mean and covariance per row of the set")
         cov = np.asarray(cov, dtype=float)
@@ -596,8 +610,8 @@ class Engine:
                 raise ValueError("cov must be symmetric in its last two axes")
         mu, cov = self._moments(set_id, mu, cov)
         n = C.c_int(0)
-        self._ck(self.lib.vlgp_mstep_cov(self.h, int(set_id), dptr(mu), dptr(cov), int(n_iter), int(bool(use_hessian)),
-                                         float(eps), float(learning_rate), float(da_bound), float(db_bound), C.byref(n)))
+        self._ck(entry(self.h, int(set_id), dptr(mu), dptr(cov), int(n_iter), int(bool(use_hessian)), float(eps),
+                       float(learning_rate), float(da_bound), float(db_bound), C.byref(n)))
         return n.value
 
     def mstep_begin(self, set_id, n_iter, use_hessian=True, eps=1e-8, learning_rate=1.0, da_bound=5.0,
