@@ -7,13 +7,16 @@ from heldout_numpy import rate_ll
 from oracle import vlgp_oracle as O
 
 
-def estep_masked(y, x, a, b, noise, gauss, G, observed, n_iter, dmu_bound=5.0, vb=True):
-    """``n_iter`` sweeps of estep_unit from mu = v = w = 0 with the likelihood terms of the entries where ``observed``
-    (T, N) is False removed: res and U are 0 there.  Returns (mu, v, w, dmu, n_failed)."""
+def estep_masked(y, x, a, b, noise, gauss, G, observed, n_iter, dmu_bound=5.0, vb=True, start=None):
+    """``n_iter`` sweeps of estep_unit from mu = v = w = 0 (or from ``start``, a (mu, v, w) triple that is left alone) with
+    the likelihood terms of the entries where ``observed`` (T, N) is False removed: res and U are 0 there.  Returns
+    (mu, v, w, dmu, n_failed)."""
     y = np.asarray(y, dtype=float)
     obs = np.asarray(observed, dtype=float)
     T, L = y.shape[0], a.shape[0]
     mu, v, w, dmu = (np.zeros((T, L)) for _ in range(4))
+    if start is not None:
+        mu, v, w = (np.array(s, dtype=float) for s in start)
     eye = np.eye(G.shape[-1])
     pois = ~gauss
     asq = a ** 2
