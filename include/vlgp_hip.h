@@ -275,6 +275,19 @@ int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double tol, int n_s
  * doubles: the same bits on every run. */
 int vlgp_joint_posterior(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats, double* mu,
                          double* cov, int* n_failed);
+/* vlgp_joint_posterior with the window moments of the hyperparameter step of the Laplace EM, formed from
+ * the factor of H while it is still on the device.  Everything vlgp_joint_posterior returns, this call returns bit for
+ * bit.  For a unit of T rows the windows of `window` rows start at s = k window, k = 0 ... T / window - 1, and, when window
+ * does not divide T, once more at s = T - window (it overlaps its neighbour); a unit shorter than the window has none.
+ *   S[l] = sum over units and windows of  m[s : s + window] m[s : s + window]' + G_l[s : s + window, :] (H^-1)_ll G_l[s : s + window, :]'
+ * with m = column l of mu: S (L, window, window), symmetric to the bit (the entries above the diagonal are copies of
+ * their mirror images), the units added in unit order; *n_windows: the number of windows of the set.  y is not read by
+ * the moments: a masked fit set is taken as vlgp_joint_posterior takes it.  A unit whose factorisation failed makes S NaN
+ * and is counted in *n_failed.  Limits: 2 <= window <= 64 (VLGP_ERR_ARG), no prior factor of the set with a rank above 64
+ * and at least one unit as long as the window (VLGP_ERR_STATE each); a null S or n_windows: VLGP_ERR_ARG; all of them
+ * before anything is written.  Waits, state and the sets taken as vlgp_joint_posterior. */
+int vlgp_joint_posterior_moments(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats, double* mu,
+                                 double* cov, int* n_failed, int window, double* S, int64_t* n_windows);
 /* Posterior-predictive log density of every observation under the set's current posterior: where vlgp_loglik scores an
  * entry with the plug-in density p(y | E_q[rate]), this integrates the likelihood over the posterior of its linear
  * predictor,

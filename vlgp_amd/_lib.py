@@ -132,6 +132,8 @@ _SIGNATURES = {
     "vlgp_calibration": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "vlgp_joint_laplace": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "vlgp_joint_posterior": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip]),
+    "vlgp_joint_posterior_moments": (C.c_int, [_h, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip, C.c_int, _dp,
+                                               _i64p]),
     "vlgp_predictive_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "vlgp_calibration_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
 }

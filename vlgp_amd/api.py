@@ -12,6 +12,7 @@ import logging
 import numpy as np
 
 from . import engine as E
+from . import gp
 from .preprocess import fill_params, fill_trials, get_config, get_params, initialize
 from .util import _per_trial_entries, segment_starts
 
@@ -404,12 +405,13 @@ def transform(trials, params, config, device=0):
 
 
 def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, newton_tol=1e-10, device=0, verbose=True,
-                comm=None, missing=None):
-    """Laplace EM: refit ``a``, ``b`` and ``noise`` under the joint Laplace posterior of every whole trial.
+                comm=None, missing=None, hstep=False):
+    """Laplace EM: refit ``a``, ``b`` and ``noise`` (with ``hstep=True`` also ``omega``) under the joint Laplace posterior
+    of every whole trial.
 
-    ``trials, params, config`` as ``fit`` or ``transform`` return them.  ``omega``, ``sigma`` and the prior factors are
-    those of ``params`` and are not re-estimated; no loading constraint is applied, the fixed prior sets the scale.  With
-    ``E_k`` the sum over trials of the Laplace evidence under ``params_k``:
+    ``trials, params, config`` as ``fit`` or ``transform`` return them.  By default ``omega``, ``sigma`` and the prior
+    factors are those of ``params`` and are not re-estimated; no loading constraint is applied, the fixed prior sets the
+    scale.  With ``E_k`` the sum over trials of the Laplace evidence under ``params_k``:
 
     1. ``post_k`` = the joint posterior of every trial under ``params_k`` (``Engine.joint_posterior``, ``newton_iter``
        factorisations at most, decrement ``newton_tol``), started from the caller's ``mu, w`` every time;
@@ -431,6 +433,15 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
     M-step is ``Engine.mstep_cov_masked`` (every channel over its observed rows) and ``w`` sums over a row's observed
     channels.  What ``y`` holds at a missing entry is never read.  Poisson channels only, and every channel needs an
     observed entry: each a ``ValueError`` otherwise.  Every returned trial carries its ``missing`` array.
+
+    ``hstep=True`` learns the GP timescales under the same posterior.  Step 1 also returns the window
+    moments of ``post_k`` (``Engine.joint_posterior(..., window=config["window"])``) and step 5 becomes: ``a, b, noise`` from
+    the covariance M-step of ``post_k``; ``omega`` from ``gp.optimize_joint`` on ``post_k``'s moments; the prior factors
+    rebuilt on the device for the new ``omega`` before the next E-step.  Where step 3 goes back to ``params_{k-1}`` the
+    previous ``omega`` and its factors come back with it.  ``runtime["joint"]["omega"]`` gets ``omega_k``, one (L,) array
+    per iteration; the returned ``params`` carries the returned ``omega`` and the ``cholesky`` that belongs to it.
+    ``sigma`` and ``gp_noise`` are not re-estimated.  Works with ``missing`` as well.  ``config["window"]`` outside
+    2 ... 64, ``params["rank"] > 64`` and no trial as long as the window are a ``ValueError`` each.
 
     Returns a new ``{"trials", "params", "config"}``; the caller's dicts are not modified.  Every trial copy has ``mu``
     (the mode), ``v`` (the diagonal of ``cov``), ``cov`` (T, L, L) and ``w`` from ``update_w`` at that ``mu`` under the
@@ -458,6 +469,15 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
     echo = _echo if verbose else (lambda msg: None)
     L = int(params["zdim"])
     lengths = [int(tr["y"].shape[0]) for tr in trials]
+    window = None
+    if hstep:  # the limits of the compiled window-moments kernel (vlgp_joint_posterior_moments), before an engine exists
+        window = int(config["window"])
+        if not 2 <= window <= 64:
+            raise ValueError("refit_joint(hstep=True): config['window'] = %d, need 2 <= window <= 64" % window)
+        if int(params["rank"]) > 64:
+            raise ValueError("refit_joint(hstep=True): params['rank'] = %d, at most 64 is supported" % int(params["rank"]))
+        if max(lengths, default=0) < window:
+            raise ValueError("refit_joint(hstep=True): no trial is as long as the window (%d)" % window)
     bounds = np.concatenate([[0], np.cumsum(lengths)])
     units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "w": tr["w"],
               "v": tr["v"] if tr.get("v") is not None else np.zeros((T, L))} for tr, T in zip(trials, lengths)]
@@ -482,10 +502,15 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
         bind_priors(eng, trials, out_params)  # (its own dict: the caller's params["cholesky"] stays as it is)
         cur = (np.array(params["a"], dtype=float), np.array(params["b"], dtype=float), np.array(params["noise"], dtype=float),
                None, None)
-        prev = None  # (parameters, posterior, evidence) of the iteration before
+        # with hstep: omega_k and the factors that belong to it, on the host ({T: (L, T, R)}) to go back to
+        hyper = (np.array(params["omega"], dtype=float), out_params["cholesky"]) if hstep else None
+        prior_lengths = sorted(set(lengths))
+        if hstep:
+            trace["omega"] = []
+        prev = None  # (parameters, posterior, evidence, omega and factors) of the iteration before
         k = 0
         while True:
-            post = eng.joint_posterior(work, max_iter=newton_iter, tol=newton_tol)
+            post = eng.joint_posterior(work, max_iter=newton_iter, tol=newton_tol, window=window)
             if post["n_failed"]:
                 raise E.VlgpError("refit_joint: H of %d trial(s) could not be factored at iteration %d"
                                   % (post["n_failed"], k))
@@ -493,20 +518,30 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
             trace["laplace"].append(ev)
             trace["n_newton"].append(int(np.max(post["n_newton"])))
             trace["converged"].append(bool(np.all(post["converged"])))
+            if hstep:
+                trace["omega"].append(hyper[0].copy())
             echo("refit_joint %d: laplace %.6f, Newton %d%s" % (k, ev, trace["n_newton"][-1],
                                                               "" if trace["converged"][-1] else " (not converged)"))
             if prev is not None and ev - prev[2] <= tol * abs(ev):
                 if not ev >= prev[2]:
                     cur, post = prev[0], prev[1]
                     eng.set_params(*cur[:3])
+                    if hstep:  # the previous omega and its factors, as they were
+                        hyper = prev[3]
+                        for T in prior_lengths:
+                            eng.set_prior(T, hyper[1][T])
                 break
             if k == max_iter:
                 break
-            prev = (cur, post, ev)
+            prev = (cur, post, ev, hyper)
             bad = mstep(work, post["mu"], post["cov"], *m_args)
             if bad:
                 logger.error("%d Newton systems were singular (gradient step taken)", bad)
             cur = eng.get_params()
+            if hstep:
+                omega, _ = gp.optimize_joint(post["window_moments"], post["n_windows"], dict(out_params, omega=hyper[0]), config)
+                eng.build_prior(prior_lengths, omega, params["sigma"])
+                hyper = (omega, {T: eng.get_prior(T) for T in prior_lengths})
             k += 1
         # w of the mode under the returned parameters, which the engine holds
         v = np.ascontiguousarray(np.diagonal(post["cov"], axis1=1, axis2=2))
@@ -526,6 +561,8 @@ def refit_joint(trials, params, config, max_iter=20, tol=1e-6, newton_iter=50, n
     out_params.update(a=a, b=b, noise=noise)
     if da is not None:
         out_params.update(da=da, db=db)
+    if hstep:
+        out_params.update(omega=hyper[0], cholesky=dict(hyper[1]))
     out_config = dict(config)
     out_config["runtime"] = dict(config.get("runtime") or {}, joint=trace)
     return {"trials": out_trials, "params": out_params, "config": out_config}

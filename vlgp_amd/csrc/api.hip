@@ -135,6 +135,7 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
     X(vlgp_marginal, NOT_REPLICATED, nullptr)                                                                         \
     X(vlgp_joint_laplace, NOT_REPLICATED, nullptr)                                                                    \
     X(vlgp_joint_posterior, NOT_REPLICATED | SET_MASKED_FIT, nullptr)                                                 \
+    X(vlgp_joint_posterior_moments, NOT_REPLICATED | SET_MASKED_FIT, nullptr)                                         \
     X(vlgp_mstep_cov, NOT_REPLICATED, nullptr)                                                                        \
     X(vlgp_mstep_cov_masked, SET_MASKED_FIT,                                                                          \
       "vlgp_mstep_cov_masked takes a masked fit set (set %d has no mask: vlgp_mstep_cov takes it)")                   \

@@ -98,6 +98,29 @@ inline JointPosteriorLayout joint_posterior_layout(int64_t work, int64_t rows, i
     return {b.doubles(work), b.doubles(8 * M), b.doubles(rows * (L * (L + 1) / 2)), b.need()};
 }
 
+// vlgp_joint_posterior_moments (window > 0): vlgp_joint_posterior's block, then the window moments' partials (M, L,
+// window, window) | their sum S (L, window, window); window = 0 is vlgp_joint_posterior's block itself
+struct JointMomentsLayout { JointPosteriorLayout p; int64_t part, S, need; };
+inline JointMomentsLayout joint_moments_layout(int64_t work, int64_t rows, int64_t L, int64_t M, int64_t window) {
+    const JointPosteriorLayout p = joint_posterior_layout(work, rows, L, M);
+    BlockLayout b;
+    b.at = p.need;
+    return {p, b.doubles(M * L * window * window), b.doubles(L * window * window), b.need()};
+}
+// ... and what the call refuses for its window, in this order, before anything reaches the device: the window against the
+// compiled tile, the largest effective rank of the set against it, and a set without a unit as long as the window
+struct JointMomentsRefusal { int status; const char* text; int arg; };  // (text: a format with one %d, for arg)
+inline JointMomentsRefusal joint_moments_refusal(int window, int rp, int64_t n_windows) {
+    if (window < 2 || window > 64) return {-1, "vlgp_joint_posterior_moments: window = %d, need 2 <= window <= 64", window};
+    if (rp > 64) return {-3, "vlgp_joint_posterior_moments: a prior factor has rank %d, at most 64 are supported", rp};
+    if (n_windows < 1) return {-3, "vlgp_joint_posterior_moments: no unit of the set is as long as the window (%d)", window};
+    return {0, nullptr, 0};
+}
+// the number of windows of a unit of T rows: T / window whole ones and one more, ending at the last row, when a rest is left
+inline int64_t joint_unit_windows(int64_t T, int64_t window) {
+    return T < window ? 0 : T / window + (T % window ? 1 : 0);
+}
+
 // vlgp_mstep_cov: the first row with a non-finite moment (one 64-bit integer) | mu (rows, L) | cov (rows, L (L + 1) / 2),
 // the handle's own buffer (vlgp_ctx::d_mcov), on the device for all Newton iterations of the call
 struct MstepCovLayout { int64_t first, mu, cov, need; };

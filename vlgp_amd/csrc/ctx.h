@@ -354,7 +354,7 @@ struct Admission { const char* what; unsigned kinds; const char* refusal; };
 int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admission* a);  // (a null: admit() is the caller's)
 int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a);
 extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_calibration, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
-    admit_vlgp_joint_laplace, admit_vlgp_joint_posterior, admit_vlgp_predictive_cov,
+    admit_vlgp_joint_laplace, admit_vlgp_joint_posterior, admit_vlgp_joint_posterior_moments, admit_vlgp_predictive_cov,
     admit_vlgp_calibration_cov;  // the scoring entry points' rows of the table (eval_api.hip)
 
 // profiling brackets (HIP events on ctx->stream)
@@ -483,3 +483,6 @@ int launch_joint_round(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_i
 int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, double* d_stats, double* d_mu, double* d_v,
                         double* d_cov);
 int launch_joint_draw(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int kc, const double* d_eps, double* d_beta, double* d_c);
+// the window moments of the hyperparameter step, after launch_joint_finish: d_part (M, L, window, window), d_S (L, window,
+// window) = the sum over the units of sum over a unit's windows of m m' + G_w (H^-1)_ll G_w'
+int launch_joint_window_moments(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int window, double* d_part, double* d_S);

@@ -1,5 +1,6 @@
 // The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_calibration and their _cov
-// siblings, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior.  Every one is put together the same way: open the set,
+// siblings, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior, vlgp_joint_posterior_moments.
+// Every one is put together the same way: open the set,
 // check the arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
 #include <algorithm>
 
@@ -396,22 +397,34 @@ extern "C" int vlgp_joint_laplace(vlgp_ctx* ctx, int set, int max_iter, double t
     });
 }
 
-// vlgp_joint_laplace's mode without draws, on a plain set or a masked set of one replica, with the covariance of every row
-extern "C" int vlgp_joint_posterior(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats, double* mu,
-                                    double* cov, int* n_failed) {
-    static const char* who = "vlgp_joint_posterior";
+// vlgp_joint_laplace's mode without draws, on a plain set or a masked set of one replica, with the covariance of every row;
+// window > 0 (vlgp_joint_posterior_moments): also the window moments S (L, window, window) and the number of windows, from
+// the factor while it is still in the call's block
+static int joint_posterior_call(vlgp_ctx* ctx, const char* who, const Admission& a, int set, int max_iter, double tol,
+                                double* beta, double* stats, double* mu, double* cov, int* n_failed, int window, double* S,
+                                int64_t* n_windows) {
     Posterior p;
-    CHK(open_posterior(ctx, set, admit_vlgp_joint_posterior, n_failed, &p));
+    CHK(open_posterior(ctx, set, a, n_failed, &p));
     UnitSet* us = p.us;
     int Dmax = 1;
     CHK(joint_args(ctx, who, max_iter, tol));
-    if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "vlgp_joint_posterior needs stats");
+    if (!stats) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs stats", who);
+    const bool moments = &a == &admit_vlgp_joint_posterior_moments;
+    if (moments) {
+        if (!S || !n_windows) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs S and n_windows", who);
+        int64_t nw = 0;
+        for (int m = 0; m < us->M && window > 0; ++m) nw += joint_unit_windows(us->off[m + 1] - us->off[m], window);
+        const JointMomentsRefusal no = joint_moments_refusal(window, p.rp, nw);
+        if (no.status) return vlgp_fail(ctx, no.status, no.text, no.arg);
+        *n_windows = nw;
+    }
     CHK(joint_dmax(ctx, who, *us, &Dmax));
     const int L = ctx->L, M = us->M;
     const int64_t rows = us->rows, npair = (int64_t)L * (L + 1) / 2;
-    const JointPosteriorLayout o = joint_posterior_layout(joint_work_doubles(ctx, *us, Dmax, nullptr), rows, L, M);
+    const JointMomentsLayout om = joint_moments_layout(joint_work_doubles(ctx, *us, Dmax, nullptr), rows, L, M, window);
+    const JointPosteriorLayout& o = om.p;
     CallBlock blk(ctx);
-    HIPCHK(ctx, blk.alloc(o.need));
+    HIPCHK(ctx, blk.alloc(om.need));
     JointWork W;
     W.who = who;
     W.base = blk.at(o.work);
@@ -420,11 +433,26 @@ extern "C" int vlgp_joint_posterior(vlgp_ctx* ctx, int set, int max_iter, double
     CHK(joint_newton(ctx, cp, p, W, max_iter, tol));
     const bool path = mu || cov;
     CHK(launch_joint_finish(ctx, *us, p.rp, W, blk.at(o.stats), path ? W.g : nullptr, nullptr, blk.opt(path, o.cov)));
+    if (moments) CHK(launch_joint_window_moments(ctx, *us, W, window, blk.at(om.part), blk.at(om.S)));
     cp.out(stats, blk.at(o.stats), sizeof(double) * 8 * (size_t)M);
     cp.out(beta, W.beta, sizeof(double) * (size_t)(p.tasks * ctx->R));
     cp.out(mu, W.g, sizeof(double) * (size_t)(rows * L));
     cp.out(cov, blk.at(o.cov), sizeof(double) * (size_t)(rows * npair));
+    if (moments) cp.out(S, blk.at(om.S), sizeof(double) * (size_t)L * window * window);
     CHK(cp.finish(who, "copy-out"));
     count_failed_units(stats, M, n_failed);
     return VLGP_OK;
+}
+
+extern "C" int vlgp_joint_posterior(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats, double* mu,
+                                    double* cov, int* n_failed) {
+    return joint_posterior_call(ctx, "vlgp_joint_posterior", admit_vlgp_joint_posterior, set, max_iter, tol, beta, stats, mu,
+                                cov, n_failed, 0, nullptr, nullptr);
+}
+
+extern "C" int vlgp_joint_posterior_moments(vlgp_ctx* ctx, int set, int max_iter, double tol, double* beta, double* stats,
+                                            double* mu, double* cov, int* n_failed, int window, double* S,
+                                            int64_t* n_windows) {
+    return joint_posterior_call(ctx, "vlgp_joint_posterior_moments", admit_vlgp_joint_posterior_moments, set, max_iter, tol,
+                                beta, stats, mu, cov, n_failed, window, S, n_windows);
 }

@@ -51,6 +51,13 @@
 //                  the pair (l, l) is joint_var's v bit for bit; mu as there.
 //   joint_stats    one workgroup per unit: the sums of the final row pass into stats.
 //   joint_draw     one wave per unit, lane k one sample: the back substitution against Lc' in a per-lane global vector.
+//   joint_window_moments      vlgp_joint_posterior_moments, after the finish: one workgroup of 256 per (unit, latent).  Wave 0
+//                  solves for (H^-1)_ll as joint_var does, into LDS; then for every window of W <= 64 rows of the unit the
+//                  rows of G_l go to LDS, Z = G_w (H^-1)_ll (W x r) is formed there, and Z G_w' + m_w m_w' is added to a
+//                  4 x 4 register tile per thread of the unit's W x W sum (joint_assemble's tiling), which is kept across
+//                  the windows.  Three tiles of 64 x 65 doubles and m_w: 100 352 bytes of LDS, above the 64 KB a kernel
+//                  gets by default, so the launcher raises the ceiling as joint_factor's does.  A failed unit writes NaN.
+//   joint_window_moments_sum  the (unit, latent) partials added over the units in unit order: S (L, W, W).
 // A pivot that is not positive and finite marks the unit failed: its stats[0 .. 4], mu, v and c are NaN.  Every sum has a
 // fixed order; the only atomic is the integer count of finished units.  Every index stays in bounds whatever the values.
 #include <algorithm>
@@ -65,6 +72,8 @@
 #define JT_MIN_STEP 0x1p-30            // a step shorter than this ends the unit
 #define JT_STATIC_LDS 1024             // room left for joint_factor's own __shared__ variables under the device's limit
 #define JT_ST 8                        // per-unit state: doubles {s, f, decrement, log det H}, ints below
+#define JW_N 64                        // joint_window_moments: the largest window and the largest rank
+#define JW_LS (JW_N + 1)               // LDS row stride of its three tiles
 enum { JI_DONE = 0, JI_NFACT, JI_CONV, JI_FAILED, JI_NEED };
 
 namespace {
@@ -685,6 +694,134 @@ __global__ void __launch_bounds__(64) joint_draw(JointOutArgs O) {
     if (live) ck[0] = (0.5 * e2 - 0.5 * b2) - 0.5 * A.sd[(int64_t)u * JT_ST + 3];
 }
 
+// ---- window moments of the hyperparameter step ----------------------------------------------------------------------
+// part (M, L, W, W): for (unit, latent) the sum over the unit's windows of m_w m_w' + G_w (H^-1)_ll G_w', G_w = G_l[s : s + W]
+// and m_w = x[s : s + W, l] of the final row pass; the starts are s = k W, k < T / W, and T - W when W does not divide T.
+// Only the 4 x 4 tiles at or below the diagonal are summed and every entry above it is the copy of its mirror image.
+__global__ void __launch_bounds__(256) joint_window_moments(JointOutArgs O, int W, double* part) {
+    extern __shared__ double lds[];  // S | the window of G_l | Z = G_w S (64 x JW_LS each) | m_w (64)
+    const JointArgs& A = O.J;
+    const int tid = threadIdx.x, task = blockIdx.x, L = A.P.L;
+    if (task >= A.P.M * L || W < 2 || W > JW_N) return;
+    const TaskView t = task_view(A.P, task);
+    const int r = unit_rank(A.P, t.p, t.l, A.R);
+    const int* si = A.si + (int64_t)t.u * JT_ST;
+    int D = 0, d0 = 0;
+    for (int l = 0; l < L; ++l) {
+        if (l == t.l) d0 = D;
+        D += unit_rank(A.P, t.p, l, A.R);
+    }
+    double* out = part + (int64_t)task * W * W;
+    if (si[JI_FAILED] || r < 1 || D > A.Dmax) {
+        const double nan = __builtin_nan("");
+        for (int e = tid; e < W * W; e += 256) out[e] = nan;
+        return;
+    }
+    double* S = lds;
+    double* Gw = S + JW_N * JW_LS;
+    double* Z = Gw + JW_N * JW_LS;
+    double* mw = Z + JW_N * JW_LS;
+    for (int e = tid; e < JW_N * JW_LS; e += 256) S[e] = 0.0;
+    __syncthreads();
+    if (tid < r && t.T >= W) {  // joint_var's two substitutions: lane j the column (l, j) of H^-1 from d0 down
+        const int ld = D + 1;
+        const double* __restrict__ buf = A.H + (int64_t)t.u * (A.Dmax + 1) * (A.Dmax + 1);
+        double* z = A.zw + (int64_t)task * A.Dmax * 64 + tid;  // entry I at z[I * 64]
+        for (int I = d0; I < D; ++I) {
+            double s = I == d0 + tid ? 1.0 : 0.0;
+            for (int Q = d0; Q < I; ++Q) s = fma(-buf[(int64_t)Q * ld + I], z[(int64_t)Q * 64], s);
+            z[(int64_t)I * 64] = s / buf[(int64_t)I * ld + I];
+        }
+        for (int I = D - 1; I >= d0; --I) {
+            const double* __restrict__ row = buf + (int64_t)I * ld;
+            double s = z[(int64_t)I * 64];
+            for (int Q = I + 1; Q < D; ++Q) s = fma(-row[Q], z[(int64_t)Q * 64], s);
+            z[(int64_t)I * 64] = s / row[I];
+        }
+        for (int i = 0; i < r; ++i) S[i * JW_LS + tid] = z[(int64_t)(d0 + i) * 64];
+    }
+    const int i0 = (tid >> 4) * 4, j0 = (tid & 15) * 4;
+    double acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+    const int nfull = t.T / W, nwin = t.T < W ? 0 : nfull + (t.T % W ? 1 : 0);
+    for (int k = 0; k < nwin; ++k) {
+        const int s0 = k < nfull ? k * W : t.T - W;
+        __syncthreads();  // (S is whole; the last window's tiles are read)
+        for (int e = tid; e < JW_N * JW_N; e += 256) {
+            const int tt = e >> 6, i = e & 63;
+            Gw[tt * JW_LS + i] = (tt < W && i < r) ? t.G[(int64_t)(s0 + tt) * r + i] : 0.0;
+        }
+        if (tid < JW_N) mw[tid] = tid < W ? A.x[(t.r0 + s0 + tid) * L + t.l] : 0.0;
+        __syncthreads();
+        if (i0 < W && j0 < r) {  // Z = G_w S
+            double zt[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) zt[i][j] = 0.0;
+            for (int q = 0; q < r; ++q) {
+                double a4[4], b4[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a4[i] = Gw[(i0 + i) * JW_LS + q];
+                    b4[i] = S[q * JW_LS + j0 + i];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) zt[i][j] = fma(a4[i], b4[j], zt[i][j]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) Z[(i0 + i) * JW_LS + j0 + j] = zt[i][j];
+        }
+        __syncthreads();
+        if (i0 < W && j0 <= i0) {  // += Z G_w' + m_w m_w'
+            for (int q = 0; q < r; ++q) {
+                double a4[4], b4[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a4[i] = Z[(i0 + i) * JW_LS + q];
+                    b4[i] = Gw[(j0 + i) * JW_LS + q];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = fma(a4[i], b4[j], acc[i][j]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = fma(mw[i0 + i], mw[j0 + j], acc[i][j]);
+        }
+    }
+    if (j0 <= i0)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int I = i0 + i, J = j0 + j;
+                if (I < W && J <= I) {
+                    out[I * W + J] = acc[i][j];
+                    out[J * W + I] = acc[i][j];
+                }
+            }
+}
+
+// S (L, W, W) = the partials of the units added in unit order
+__global__ void __launch_bounds__(256) joint_window_moments_sum(int M, int L, int W2, const double* part, double* S) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)L * W2) return;
+    const int l = (int)(e / W2), at = (int)(e % W2);
+    double s = 0.0;
+    for (int u = 0; u < M; ++u) s += part[((int64_t)u * L + l) * W2 + at];
+    S[e] = s;
+}
+
 JointArgs fill_joint(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int max_iter, double tol, int final) {
     JointArgs A;
     A.m = fill_row_model(ctx, vlgp_rows_owner(ctx, us), us, 0);  // (a masked set of one replica: the source's y, xb)
@@ -790,6 +927,23 @@ int launch_joint_finish(vlgp_ctx* ctx, UnitSet& us, int rp, const JointWork& W, 
         else hipLaunchKernelGGL(joint_var, grid, dim3(64), lds, ctx->stream, O);
         HIPCHK(ctx, hipGetLastError());
     }
+    return VLGP_OK;
+}
+
+// after launch_joint_finish (the factor and x of the final row pass are in W): d_part (M, L, window, window) per (unit,
+// latent), d_S (L, window, window) their sum over the units; 2 <= window <= 64 and rp <= 64: the caller has checked
+int launch_joint_window_moments(vlgp_ctx* ctx, UnitSet& us, const JointWork& W, int window, double* d_part, double* d_S) {
+    JointOutArgs O = {};
+    O.J = fill_joint(ctx, us, W, 1, 0.0, 1);
+    const size_t lds = sizeof(double) * (size_t)(3 * JW_N * JW_LS + JW_N);
+    if ((int64_t)lds > ctx->lds_max) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: the window moments need %zu bytes of LDS", W.who, lds);
+    CHK(vlgp_raise_lds(ctx, (const void*)joint_window_moments, (int)lds));
+    hipLaunchKernelGGL(joint_window_moments, dim3((unsigned)(us.M * ctx->L)), dim3(256), lds, ctx->stream, O, window, d_part);
+    HIPCHK(ctx, hipGetLastError());
+    const int64_t n = (int64_t)ctx->L * window * window;
+    hipLaunchKernelGGL(joint_window_moments_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, us.M, ctx->L,
+                       window * window, d_part, d_S);
+    HIPCHK(ctx, hipGetLastError());
     return VLGP_OK;
 }
 

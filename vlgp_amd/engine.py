@@ -476,23 +476,38 @@ class Engine:
             out.update(log_w=log_w, parts=parts)
         return out
 
-    def joint_posterior(self, set_id, max_iter=50, tol=1e-10):
+    def joint_posterior(self, set_id, max_iter=50, tol=1e-10, window=None):
         """``joint_laplace`` without draws and with the covariance of every row, on a plain set or on a set replicated
         with ``held_out`` of one replica, whose held-out entries the posterior does not see (vlgp_joint_posterior).
         Returns ``joint_laplace``'s dict without ``v``, ``log_w`` and ``parts``, plus ``cov`` (rows, L, L), symmetric:
         ``cov[t, l, l'] = G_l[t] (H^-1)_{l l'} G_l'[t]'``, whose diagonal is ``joint_laplace``'s ``v``.  A failed unit's
-        rows of ``mu`` and ``cov`` are NaN.  Changes no state."""
+        rows of ``mu`` and ``cov`` are NaN.  Changes no state.
+
+        ``window`` (2 ... 64; vlgp_joint_posterior_moments): the same call and the same results, plus
+        ``"window_moments"`` (L, window, window), the sum over every window of every unit of
+        ``m m' + G_l (H^-1)_ll G_l'`` on the window's rows (``gp.optimize_joint`` takes it; NaN when a unit failed), and
+        ``"n_windows"``."""
         units, rows, _ = self.sets[set_id]
         beta = np.empty((units, self.L, self.R))
         stats = np.empty((units, 8))
         mu, packed = np.empty((rows, self.L)), np.empty((rows, self.L * (self.L + 1) // 2))
         n = C.c_int(0)
-        self._ck(self.lib.vlgp_joint_posterior(self.h, int(set_id), int(max_iter), float(tol), dptr(beta), dptr(stats),
-                                               dptr(mu), dptr(packed), C.byref(n)))
-        return {"beta": beta, "stats": stats, "mu": mu, "cov": unpack_cov(packed, self.L), "n_failed": n.value,
-                "laplace": stats[:, 0].copy(), "ll": stats[:, 1].copy(), "beta_sq": stats[:, 2].copy(),
-                "logdet": stats[:, 3].copy(), "decrement": stats[:, 4].copy(), "n_newton": stats[:, 5].astype(np.int64),
-                "converged": stats[:, 6] > 0, "D": stats[:, 7].astype(np.int64)}
+        extra = {}
+        if window is None:
+            self._ck(self.lib.vlgp_joint_posterior(self.h, int(set_id), int(max_iter), float(tol), dptr(beta), dptr(stats),
+                                                   dptr(mu), dptr(packed), C.byref(n)))
+        else:
+            w = min(max(int(window), 0), 65)  # (only the size of the buffer: the library refuses what is out of range)
+            S, n_w = np.empty((self.L, w, w)), np.zeros(1, dtype=np.int64)
+            self._ck(self.lib.vlgp_joint_posterior_moments(self.h, int(set_id), int(max_iter), float(tol), dptr(beta),
+                                                           dptr(stats), dptr(mu), dptr(packed), C.byref(n), int(window),
+                                                           dptr(S), i64ptr(n_w)))
+            extra = {"window_moments": S, "n_windows": int(n_w[0])}
+        return dict({"beta": beta, "stats": stats, "mu": mu, "cov": unpack_cov(packed, self.L), "n_failed": n.value,
+                     "laplace": stats[:, 0].copy(), "ll": stats[:, 1].copy(), "beta_sq": stats[:, 2].copy(),
+                     "logdet": stats[:, 3].copy(), "decrement": stats[:, 4].copy(),
+                     "n_newton": stats[:, 5].astype(np.int64), "converged": stats[:, 6] > 0,
+                     "D": stats[:, 7].astype(np.int64)}, **extra)
 
     def unit_ranks(self, set_id):
         """(units, L) effective rank of the prior factor each (unit, latent) of the set is bound to."""

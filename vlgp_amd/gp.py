@@ -11,6 +11,11 @@ the module is not built.  Every objective evaluation -- the T x T
 factorisations per segment that make up all of the arithmetic -- runs on the
 GPU through ``Engine.hstep_objective``.  The L latents' optimisers run in lock
 step so that each round of evaluations is ONE kernel launch over all latents.
+
+``optimize_joint`` is the same optimisation under the joint Laplace posterior of
+``refit_joint(..., hstep=True)``: there the posterior is fixed,
+the data enter through one W x W moment matrix per latent that the device forms
+(``Engine.joint_posterior(..., window=W)``), and the objective runs on the host.
 """
 import logging
 import math
@@ -18,6 +23,7 @@ import os
 import threading
 
 import numpy as np
+from scipy.linalg import cho_solve
 from scipy.optimize import minimize
 
 logger = logging.getLogger(__name__)
@@ -395,3 +401,66 @@ def optimize(trials, params, config):
     params["sigma"] = sigma
     params["omega"] = omega
     make_cholesky(trials, params, config)
+
+
+def joint_window_objective(logps, S, n_windows, dt=1.0):
+    """The hyperparameter objective under a fixed Gaussian posterior, for row k of ``logps`` (k, 3) =
+    log(sigma^2, omega, gp_noise) and window moments ``S`` (k, W, W) over ``n_windows`` windows:
+
+        K = sigma^2 exp(-omega D2) + gp_noise I,  D2_ij = (dt (i - j))^2
+        ll = -1/2 tr(K^-1 S) - n_windows / 2 log|K|
+        d ll / d ln omega = 1/2 tr[(K^-1 S K^-1 - n_windows K^-1) dK],  dK = -omega D2 o sigma^2 exp(-omega D2)
+
+    Returns ``(ll (k), dll (k, 3))``, the gradient non-zero in ln omega only -- the reference's ``gp.elbo`` with
+    ``mask = [0, 1, 0]`` summed over the windows; ``(-inf, 0)`` where K does not factor, as there.  Host NumPy: one
+    Cholesky factorisation of W x W, W <= 64, per row."""
+    logps = np.asarray(logps, dtype=np.float64)
+    W = S.shape[-1]
+    t = np.arange(W) * dt
+    D2 = (t[:, None] - t[None, :]) ** 2
+    ll, dll = np.empty(len(logps)), np.zeros((len(logps), 3))
+    for k, logp in enumerate(logps):
+        sig2, om, eps = np.exp(logp)
+        K0 = sig2 * np.exp(-om * D2)
+        try:
+            Lc = np.linalg.cholesky(K0 + eps * np.eye(W))
+        except np.linalg.LinAlgError:
+            ll[k] = -np.inf
+            continue
+        Kinv = cho_solve((Lc, True), np.eye(W))
+        KS = cho_solve((Lc, True), S[k])
+        ll[k] = -0.5 * np.trace(KS) - n_windows * np.sum(np.log(np.diag(Lc)))
+        dll[k, 1] = 0.5 * np.sum((KS @ Kinv - n_windows * Kinv) * (-om * D2 * K0))
+    return ll, dll
+
+
+def optimize_joint(S, n_windows, params, config):
+    """The H-step of the Laplace EM (``refit_joint(..., hstep=True)``): ``gp.optimize``'s bounded L-BFGS-B runs on
+    log(sigma^2, omega, gp_noise) per latent, in lock step, on ``joint_window_objective`` of the window moments ``S`` (L, W,
+    W) of ``Engine.joint_posterior(..., window=W)`` and its ``n_windows``.  The posterior is fixed, so the moments hold all
+    the data the objective needs and every evaluation is L small factorisations on the host.
+
+    Returns ``(omega, ll)``: the new ``omega`` (L) -- a result close to one of ``config["omega_bound"]`` keeps the old
+    value, as in ``optimize`` -- and per latent the objective reached.  ``params`` is not modified; ``sigma`` and
+    ``gp_noise`` do not move (their gradient is masked, as the reference's)."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    L = int(params["zdim"])
+    if S.shape != (L, S.shape[-1], S.shape[-1]) or not np.all(np.isfinite(S)):
+        raise ValueError("optimize_joint: S must be a finite (L, W, W) array, got shape %r" % (S.shape,))
+    dt, gp_noise = params["dt"], params["gp_noise"]
+    sigma, omega = np.asarray(params["sigma"], dtype=float), np.array(params["omega"], dtype=float)
+    bounds = np.log(np.array([(1e-3, 1.0), tuple(config["omega_bound"]), (gp_noise / 2, gp_noise * 2)]))
+
+    def batch(latents, logps):  # (minimised: negate)
+        ll, dll = joint_window_objective(logps, S[list(latents)], n_windows, dt)
+        return -ll, -dll
+
+    x0s = [np.log(np.array([sigma[l] ** 2, omega[l], gp_noise])) for l in range(L)]
+    xs = lockstep_minimize(batch, x0s, bounds)
+    reached = joint_window_objective(np.stack(xs), S, n_windows, dt)[0]
+    ob = [float(b) for b in config["omega_bound"]]
+    for l in range(L):
+        om = float(np.exp(xs[l])[1])
+        if not any(abs(om - b) <= 1e-8 + 1e-5 * abs(b) for b in ob):  # (np.isclose's predicate, as in optimize)
+            omega[l] = om
+    return omega, reached
