@@ -368,6 +368,23 @@ int vlgp_calibration_cov(vlgp_ctx* ctx, int set, int n_nodes, const double* z, c
                          const double* cov, int n_bins, int n_levels, const double* levels, int max_count, double* cdf,
                          double* sums);
 
+/* Pair moments of the predictive distribution: do pairs of channels co-fluctuate more than the model
+ * says?  For every row t scored under row `mrow` of the posterior's set (the table of DESIGN.md 4.12), with the Gaussian
+ * posterior N(mu[mrow], C) of the latents -- C = diag(v[mrow]) (0 when vb == 0) for vlgp_pair_moments, the packed cov[mrow]
+ * of vlgp_predictive_cov for the sibling -- and c[n, m] = a_n' C a_m:
+ *   e_n = the rate of vlgp_predictive / vlgp_predictive_cov (Poisson trunc_exp(m_n + max(0, c[n, n]) / 2), Gaussian m_n)
+ *   s_n = e_n Poisson, 1 Gaussian;   f = expm1 when both channels are Poisson, else the identity
+ *   K[n, m] = s_n s_m f(c[n, m]);   K[n, n] += e_n Poisson, noise_n Gaussian;   d_n = y_tn - e_n
+ *   resid[n, m] = sum_t live_tn live_tm d_n d_m,   model[n, m] = sum_t live_tn live_tm K[n, m]
+ * resid, model: host arrays (N, N) for a plain set or a tiling cut, every entry live; (n_rep, N, N) for a set made by
+ * vlgp_replicate_masked, an entry live where its replica holds it out (what y holds elsewhere is never read).  Both are
+ * required and both come back symmetric to the bit.  Under a supplied posterior a row whose mu or cov holds a non-finite
+ * value is dead for every channel: it adds nothing.  Refused (VLGP_ERR_STATE): a copied cut, and group replicas
+ * ("replicate with held_out=: a pair needs both channels in one replica").  The calls only read: no set state changes.
+ * The rows are summed in a fixed order without atomics: the same bits on every run. */
+int vlgp_pair_moments(vlgp_ctx* ctx, int set, int vb, double* resid, double* model);
+int vlgp_pair_moments_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, double* resid, double* model);
+
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);
 /* Any pointer may be NULL.  da, db are the last M-step increments

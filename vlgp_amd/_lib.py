@@ -136,6 +136,8 @@ _SIGNATURES = {
                                                _i64p]),
     "vlgp_predictive_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "vlgp_calibration_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
+    "vlgp_pair_moments": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
+    "vlgp_pair_moments_cov": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

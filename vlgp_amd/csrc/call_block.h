@@ -51,6 +51,31 @@ inline MomentsLayout moments_layout(int64_t sibling_need, int64_t post_rows, int
     return {b.doubles(post_rows * L), b.doubles(post_rows * (L * (L + 1) / 2)), b.need()};
 }
 
+// vlgp_pair_moments and its _cov sibling (pairs.hip; the sibling's mu, cov go behind the block: moments_layout): partials
+// (n_rep, tile_pairs, n_chunks, 2, 64, 64) | resid | model (n_rep, N, N each), for `rows` rows per replica on n_cu compute
+// units.  tiles = ceil(N / 64) channel tiles, tile_pairs = tiles (tiles + 1) / 2 pairs I >= J.  A workgroup takes
+// chunk_rows rows of one (tile pair, replica): as many chunks as give every compute unit two workgroups, no more than
+// keep the partials (64 KiB per workgroup) within PAIR_PART_DOUBLES, and never fewer than PAIR_MIN_CHUNK rows each.
+#define PAIR_MIN_CHUNK 32
+#define PAIR_PART_DOUBLES (int64_t(1) << 22)  // 32 MiB
+struct PairLayout { int64_t part, resid, model, tiles, tile_pairs, chunk_rows, n_chunks, need; };
+inline PairLayout pair_layout(int64_t rows, int64_t N, int64_t n_rep, int64_t n_cu) {
+    const int64_t tiles = (N + 63) / 64, tile_pairs = tiles * (tiles + 1) / 2, groups = tile_pairs * n_rep;
+    const int64_t want = (2 * n_cu + groups - 1) / groups, cap = PAIR_PART_DOUBLES / (groups * 8192);
+    const int64_t most = want < cap ? want : (cap > 1 ? cap : 1);
+    const int64_t even = (rows + most - 1) / most, chunk_rows = even > PAIR_MIN_CHUNK ? even : PAIR_MIN_CHUNK;
+    const int64_t n_chunks = (rows + chunk_rows - 1) / chunk_rows;
+    BlockLayout b;
+    return {b.doubles(groups * n_chunks * 8192), b.doubles(n_rep * N * N), b.doubles(n_rep * N * N), tiles, tile_pairs,
+            chunk_rows, n_chunks, b.need()};
+}
+// the LDS of a pair_moments workgroup, in doubles: a of both tiles and u of tile J (L, 64 each) | the row's mu and its v or
+// packed cov | d, s of both tiles (128 each) | the diagonal's observation variances (64)
+inline int64_t pair_lds_doubles(int64_t L) {
+    const int64_t npair = L * (L + 1) / 2;
+    return 3 * L * 64 + L + (npair > L ? npair : L) + 128 + 128 + 64;
+}
+
 // partials (N, n_blk, 4) | sums (N, 4) | terms (tasks, 4) | row_ell (rows, when wanted) | flags (tasks)
 struct ElboLayout { int64_t part, sums, terms, rows, flag, need; };
 inline ElboLayout elbo_layout(int64_t rows, int64_t N, int64_t tasks, int64_t n_blk, bool want_rows) {

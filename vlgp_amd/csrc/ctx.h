@@ -355,7 +355,8 @@ int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admissio
 int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a);
 extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_calibration, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
     admit_vlgp_joint_laplace, admit_vlgp_joint_posterior, admit_vlgp_joint_posterior_moments, admit_vlgp_predictive_cov,
-    admit_vlgp_calibration_cov;  // the scoring entry points' rows of the table (eval_api.hip)
+    admit_vlgp_calibration_cov, admit_vlgp_pair_moments,
+    admit_vlgp_pair_moments_cov;  // the scoring entry points' rows of the table (eval_api.hip)
 
 // profiling brackets (HIP events on ctx->stream)
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st = nullptr);
@@ -439,6 +440,11 @@ int launch_predictive_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double*
 int launch_calibration_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double* d_nodes, const double* d_mu,
                            const double* d_cov, int n_bins, int n_levels, const double* d_levels, int max_count,
                            double* d_cdf, double* d_part, double* d_sums);
+// pair moments of a plain or masked set's predictive distribution (pairs.hip): d_resid, d_model (replicas, N, N) under the
+// set's own mu, v (d_cov null) or under d_mu, d_cov as the two above take them; d_part: the partials of pair_layout
+// (call_block.h) for the source's rows; who: the entry point, for the messages
+int launch_pair_moments(vlgp_ctx* ctx, const char* who, UnitSet& us, int vb, const double* d_mu, const double* d_cov,
+                        double* d_part, double* d_resid, double* d_model);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace

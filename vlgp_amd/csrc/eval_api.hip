@@ -1,5 +1,6 @@
 // The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_calibration and their _cov
-// siblings, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior, vlgp_joint_posterior_moments.
+// siblings, vlgp_pair_moments and its, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior,
+// vlgp_joint_posterior_moments.
 // Every one is put together the same way: open the set,
 // check the arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
 #include <algorithm>
@@ -159,6 +160,44 @@ extern "C" int vlgp_calibration_cov(vlgp_ctx* ctx, int set, int n_nodes, const d
                                     double* cdf, double* sums) {
     return calibration_call(ctx, "vlgp_calibration_cov", admit_vlgp_calibration_cov, set, 1, n_nodes, z, lwa, {true, mu, cov},
                             n_bins, n_levels, levels, max_count, cdf, sums);
+}
+
+// The pair moments of a plain or masked set (pairs.hip): two (replicas, N, N) matrices, nothing per entry.  Group replicas
+// keep one channel group per replica, so no replica holds both channels of a pair: they are told what to make instead.
+static int pair_call(vlgp_ctx* ctx, const char* who, const Admission& a, int set, int vb, const Moments& m, double* resid,
+                     double* model) {
+    UnitSet* us = nullptr;
+    CHK(open_set(ctx, set, OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &us, nullptr));
+    if (!resid || !model) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs resid and model", who);
+    CHK(need_moments(ctx, who, m));
+    if (us->is(SET_GROUPS))
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "%s: replicate with held_out=: a pair needs both channels in one replica", who);
+    CHK(admit(ctx, set, us, a));
+    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
+    if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
+    if (rows_of.rows < 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "%s on an empty set", who);
+    const int64_t n_rep = us->is(SET_BY_ROW) ? us->rep.n : 1, nn = n_rep * ctx->N * ctx->N;
+    const PairLayout o = pair_layout(rows_of.rows, ctx->N, n_rep, ctx->n_cu);
+    const MomentsLayout om = moments_layout(o.need, m.given ? us->rows : 0, ctx->L);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(om.need));
+    Copies cp(ctx);
+    if (m.given) copy_moments_in(cp, blk, om, m, us->rows, ctx->L);
+    CHK(cp.status(who, "copy-in"));
+    CHK(launch_pair_moments(ctx, who, *us, vb, blk.opt(m.given, om.mu), blk.opt(m.given, om.cov), blk.at(o.part),
+                            blk.at(o.resid), blk.at(o.model)));
+    cp.out(resid, blk.at(o.resid), sizeof(double) * (size_t)nn);
+    cp.out(model, blk.at(o.model), sizeof(double) * (size_t)nn);
+    return cp.finish(who, "copy-out");
+}
+
+extern "C" int vlgp_pair_moments(vlgp_ctx* ctx, int set, int vb, double* resid, double* model) {
+    return pair_call(ctx, "vlgp_pair_moments", admit_vlgp_pair_moments, set, vb, {false, nullptr, nullptr}, resid, model);
+}
+
+extern "C" int vlgp_pair_moments_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, double* resid,
+                                     double* model) {
+    return pair_call(ctx, "vlgp_pair_moments_cov", admit_vlgp_pair_moments_cov, set, 1, {true, mu, cov}, resid, model);
 }
 
 // ---- the scores of a posterior (elbo, forecast, marginal, joint Laplace) --------------------------------------------------

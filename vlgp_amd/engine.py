@@ -394,6 +394,23 @@ class Engine:
                                            dptr(sums)))
         return sums, cdf
 
+    def pair_moments(self, set_id, vb=True, mu=None, cov=None):
+        """Pair moments of a set's predictive distribution (vlgp_pair_moments): ``(resid, model)``, the sums over the rows
+        of the products of residuals ``(y - mean)_n (y - mean)_m`` and of the predictive covariance of the two channels
+        (``evaluation``'s docstring has the closed forms).  Both are (N, N) for a plain set and (n_rep, N, N) for a set
+        replicated with ``held_out=``, where replica ``k`` adds a row to the pair ``(n, m)`` when it holds both entries out;
+        both are symmetric to the bit.  ``mu``, ``cov``: as ``predictive`` takes them (vlgp_pair_moments_cov; ``vb`` is then
+        not read); a row whose ``mu`` or ``cov`` holds a non-finite value adds nothing.  Changes no state."""
+        mu, cov = self._moments(set_id, mu, cov)
+        rep = self.replicas.get(set_id)
+        shape = (self.N, self.N) if rep is None else (rep.n, self.N, self.N)
+        resid, model = np.empty(shape), np.empty(shape)
+        if mu is not None:
+            self._ck(self.lib.vlgp_pair_moments_cov(self.h, int(set_id), dptr(mu), dptr(cov), dptr(resid), dptr(model)))
+        else:
+            self._ck(self.lib.vlgp_pair_moments(self.h, int(set_id), int(bool(vb)), dptr(resid), dptr(model)))
+        return resid, model
+
     def elbo(self, set_id, vb=True, want_rows=False):
         """Terms of the variational lower bound of a plain set (vlgp_elbo): ``(row_sums, kl_terms, n_failed, row_ell)``
         -- row_sums (N, 4) per channel, kl_terms (units, L, 4) = log det H, tr H^-1, beta'beta, |mu - G beta|^2 per

@@ -186,9 +186,30 @@ the covariance of the latents of every bin, ``cov[t, l, l'] = G_l[t, :] (H^-1)_{
 mean-field ``s2 = (a_n^2) . v_t`` drops it.  One fold at a time: a masked replica of the test set, the E-step, the Newton
 iteration (from ``beta = 0``: the mode does not depend on the start), the score, free.
 
+Residual correlations (``residual_correlation``, ``Engine.pair_moments``, ``vlgp_pair_moments``,
+``vlgp_pair_moments_cov``).  Every score above is a statement about one (bin, channel) marginal; this
+one asks whether PAIRS of channels co-fluctuate more than the model says once the latents are accounted for -- the usual
+sign of too few latents.  For row ``t`` with the posterior ``N(mu_t, C_t)`` of its latents -- ``C_t = diag(v_t)`` (0 under
+MAP) for the mean-field posterior, the full ``cov[t]`` for the joint one -- and ``c[n, m] = a_n' C_t a_m``:
+
+- predictive mean ``e_n``: the ``rate`` above, ``trunc_exp(m_n + max(0, c[n, n]) / 2)`` Poisson and ``m_n`` Gaussian; scale
+  ``s_n``: ``e_n`` Poisson, 1 Gaussian; residual ``d_n = y[t, n] - e_n``.
+- predictive covariance ``K[n, m] = s_n s_m f(c[n, m])`` with ``f = expm1`` when both channels are Poisson (the
+  covariance of two lognormal rates) and the identity otherwise; on the diagonal the observation variance is added,
+  ``K[n, n] += e_n`` Poisson and ``noise[n]`` Gaussian.  ``K[n, n]`` is the variance of the Pearson term above.
+- ``resid[n, m] = sum_t live_tn live_tm d_n d_m`` and ``model[n, m] = sum_t live_tn live_tm K[n, m]``; ``count[n, m]`` is
+  the number of rows in the sums.  Every entry of a plain set is live; under ``how="channels"`` the entries of the fold,
+  scored under the posterior inferred without it.  A row of a trial whose joint posterior failed (non-finite ``mu`` or
+  ``cov``) is dead for every channel.
+- ``residual_corr = resid / sqrt(model_nn model_mm)``, ``model_corr = model / sqrt(model_nn model_mm)`` and
+  ``excess_corr``, their difference: 0 in expectation under the model, whatever the posterior's width.  ``se_null =
+  1 / sqrt(count)`` is a rough scale for it only: the rows of a trial are not independent.
+  ``dispersion[n] = resid_nn / model_nn`` is the ratio of the summed squared residual to the summed predictive variance
+  (``calibration``'s ``dispersion`` is the mean of the per-entry ratios: the two agree where the variance is constant).
+
 Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``, ``vlgp_marginal``,
-``vlgp_predictive``, ``vlgp_calibration``, ``vlgp_joint_laplace``, ``vlgp_joint_posterior`` and the ``_cov`` scores): the
-results are the same bits on every run.
+``vlgp_predictive``, ``vlgp_calibration``, ``vlgp_joint_laplace``, ``vlgp_joint_posterior``, ``vlgp_pair_moments`` and the
+``_cov`` scores): the results are the same bits on every run.
 """
 import contextlib
 import math
@@ -204,7 +225,7 @@ from .util import _per_trial_entries
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
            "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
            "entry_scores", "leave_entries_out", "impute", "marginal_loglik", "weights_summary", "hermite_nodes",
-           "joint_posterior", "calibration", "calibration_from_sums"]
+           "joint_posterior", "calibration", "calibration_from_sums", "residual_correlation"]
 
 SAMPLE_CHUNK = 64  # draws per device call: one lane per sample (csrc/marginal.hip)
 
@@ -921,6 +942,111 @@ def calibration(trials, params, config, how="in_sample", groups=None, folds=None
         for k in range(got.shape[0]):
             sums += got[k]
     out = calibration_from_sums(sums, n_bins, levels)
+    out["n_failed"] = int(n_failed)
+    out.update(extra)
+    return out
+
+
+def _pair_summary(resid, model, count):
+    """Residual correlations from the pair moments (pure host code).  ``resid``, ``model`` (N, N): ``Engine.pair_moments``'
+    sums; ``count`` (N, N): the rows in each sum, 0 or NaN for a pair that was never scored.
+
+    Returns a dict: ``resid``, ``model``, ``count`` with NaN at the pairs never scored; ``residual_corr``, ``model_corr``,
+    ``excess_corr`` and ``se_null`` (N, N) and ``dispersion`` (N) by the module docstring, NaN where the pair or one of its
+    two variances was not scored; over the scored pairs ``n > m`` with a finite ``excess_corr``: ``n_pairs``, and
+    ``rms_excess``, ``mean_excess`` (NaN without a pair)."""
+    resid, model, count = (np.array(x, dtype=float) for x in (resid, model, count))
+    if resid.ndim != 2 or resid.shape[0] != resid.shape[1] or model.shape != resid.shape or count.shape != resid.shape:
+        raise ValueError("resid, model and count must be (N, N), got %r, %r, %r" % (resid.shape, model.shape, count.shape))
+    scored = count > 0  # (False for NaN)
+    resid, model, count = (np.where(scored, x, np.nan) for x in (resid, model, count))
+    var = np.diagonal(model)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = np.sqrt(var[:, None] * var[None, :])
+        norm = np.where(norm > 0, norm, np.nan)
+        residual_corr, model_corr = resid / norm, model / norm
+        dispersion = np.diagonal(resid) / np.where(var > 0, var, np.nan)
+        se_null = 1.0 / np.sqrt(count)
+    excess = residual_corr - model_corr
+    low = excess[np.tril_indices(len(var), -1)]
+    low = low[np.isfinite(low)]
+    return {"resid": resid, "model": model, "count": count, "residual_corr": residual_corr, "model_corr": model_corr,
+            "excess_corr": excess, "se_null": se_null, "dispersion": dispersion, "n_pairs": int(low.size),
+            "rms_excess": float(np.sqrt(np.mean(low * low))) if low.size else float("nan"),
+            "mean_excess": float(np.mean(low)) if low.size else float("nan")}
+
+
+def _pair_scorer():
+    """``Engine.pair_moments`` as ``_joint_fold`` takes a scorer: per replica ``resid | model | count`` stacked, (n_rep, 3, N,
+    N) -- ``count`` the rows of the posterior that are not dead -- and no per-entry output."""
+    def scorer(eng, set_id, vb, mu=None, cov=None):
+        resid, model = eng.pair_moments(set_id, vb=vb, mu=mu, cov=cov)
+        resid, model = resid.reshape((-1,) + resid.shape[-2:]), model.reshape((-1,) + model.shape[-2:])
+        rows = eng.sets[set_id][1] // resid.shape[0]
+        alive = np.full(resid.shape[0], rows)
+        if mu is not None:
+            ok = np.isfinite(mu).all(axis=1) & np.isfinite(cov.reshape(len(mu), -1)).all(axis=1)
+            alive = ok.reshape(resid.shape[0], rows).sum(axis=1)
+        count = np.broadcast_to(alive[:, None, None].astype(float), resid.shape)
+        return np.stack([resid, model, count], axis=1), None
+    scorer.width, scorer.predictive = 3, True
+    return scorer
+
+
+def residual_correlation(trials, params, config, how="in_sample", groups=None, n_folds=5, seed=0, posterior="mean_field",
+                         n_iter=None, device=0):
+    """Residual correlations between channels: do pairs co-fluctuate beyond what the model's predictive distribution says
+    (module docstring for the definitions)?
+
+    ``how="in_sample"``: the trials' own posterior ``mu, v``, every pair of channels over every row.  ``how="channels"``:
+    the honest version -- every fold of ``groups`` (default ``channel_folds(N, min(n_folds, N), seed)``) held out as a mask
+    that is constant along the rows, the latents inferred without it from a zero start (``n_iter`` E-step iterations,
+    default ``config["max_iter"]``), and the pairs WITHIN the fold scored; a pair across two folds is never scored.
+    ``posterior="joint"``: the same under the joint Laplace posterior with its full covariance per bin -- in sample the one
+    of the trials' own data started from their stored ``mu, w``, for ``"channels"`` one fold at a time as
+    ``leave_group_out`` runs it; the rows of a trial whose ``H`` could not be factored drop out of every sum and of
+    ``count``.  Trials that carry ``missing`` raise ``ValueError``.
+
+    Returns ``_pair_summary``' dict plus ``n_failed`` (failed E-step updates and failed trials; 0 in
+    sample under the mean-field posterior) and, under the joint posterior, ``converged`` and ``n_newton`` per (fold, trial)
+    or, in sample, per trial."""
+    if how not in ("in_sample", "channels"):
+        raise ValueError("how must be 'in_sample' or 'channels', got %r" % (how,))
+    joint = _check_posterior(posterior)
+    _no_missing(trials, "residual_correlation")
+    scorer = _pair_scorer()
+    N, L = int(params["ydim"]), int(params["zdim"])
+    rows = int(sum(int(tr["y"].shape[0]) for tr in trials))
+    n_failed, extra = 0, {}
+    if how == "channels":
+        groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
+        if joint:
+            got, _, n_failed, extra, _ = _joint_folds(trials, params, config, _group_masks(groups, rows, N), n_iter, device,
+                                                      scorer)
+        else:
+            vb = config["method"] == "VB"
+            n_it = int(config["max_iter"] if n_iter is None else n_iter)
+            got = []
+            with _resident(trials, params, _zero_start(trials, L), device) as eng:
+                cap = default_max_replicas(rows, L, mask_channels=N, gauss=bool(eng.gauss.any()))
+                for chunk in plan_chunks(list(_group_masks(groups, rows, N)), cap):
+                    s, _, bad, _ = _replica_chunk(eng, n_it, config["dmu_bound"], vb, scorer=scorer, held_out=np.stack(chunk))
+                    got.extend(s)
+                    n_failed += bad
+        total = np.full((3, N, N), np.nan)
+        for k, g in enumerate(groups):
+            total[np.ix_(range(3), g, g)] = got[k][np.ix_(range(3), g, g)]
+    elif joint:
+        with _posterior(trials, params, config, False, n_iter, device) as (eng, _):
+            post = eng.joint_posterior(SET_TEST)
+            total = scorer(eng, SET_TEST, True, mu=post["mu"], cov=post["cov"])[0][0]
+        n_failed, extra = post["n_failed"], {"converged": post["converged"], "n_newton": post["n_newton"]}
+    else:
+        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "v": tr.get("v", np.zeros((tr["y"].shape[0], L))),
+                  "w": None} for tr in trials]
+        with _resident(trials, params, units, device, priors=False) as eng:
+            total = scorer(eng, SET_TEST, config.get("method", "VB") == "VB")[0][0]
+    out = _pair_summary(*total)
     out["n_failed"] = int(n_failed)
     out.update(extra)
     return out
