@@ -385,6 +385,27 @@ int vlgp_calibration_cov(vlgp_ctx* ctx, int set, int n_nodes, const double* z, c
 int vlgp_pair_moments(vlgp_ctx* ctx, int set, int vb, double* resid, double* model);
 int vlgp_pair_moments_cov(vlgp_ctx* ctx, int set, const double* mu, const double* cov, double* resid, double* model);
 
+/* Lag moments of the predictive distribution: does a channel's residual at row t still predict its
+ * residual at row t + k once the latents are accounted for?  For every unit (a trial, or a window of a tiling cut) of the
+ * set, latent l and lags k = 0 ... max_lag, under the mean-field posterior of the set's own mu, v:
+ *   w_tl = sum over the entries n the posterior saw of a_ln^2 (rate_tn Poisson, 1 / noise_n Gaussian), vlgp_update_w's
+ *          formula recomputed from mu, v (the stored w is not read)
+ *   H_l = I + G_l' diag(w_.l) G_l = Lc Lc',  u_t = Lc^-1 G_l[t]',  c_l(t, s) = u_t . u_s,  q_n(t, s) = sum_l a_ln^2 c_l(t, s)
+ *   e, s, d = y - e as vlgp_pair_moments has them;  f = expm1 Poisson, the identity Gaussian
+ *   resid[k, n] = sum d_tn d_{t+k,n},  model[k, n] = sum s_tn s_{t+k,n} f(q_n(t, t + k)),  count[k, n] = the pairs summed,
+ *   over the t with t + k in the same unit and both entries live;  model[0, n] += e_tn Poisson, noise_n Gaussian.
+ * vb == 0: c == 0, so model[k >= 1] = 0.  resid, model, count: host arrays (max_lag + 1, N) for a plain set or a tiling
+ * cut, where every entry is seen and live; (n_rep, max_lag + 1, N) for a set made by vlgp_replicate_masked, where an entry
+ * is live where its replica holds it out and seen where it does not (what y holds at an entry that is not live is never
+ * read).  A (unit, latent) whose H has a pivot that is not positive and finite is counted in *n_failed (may be NULL), and
+ * its unit adds nothing to any sum.  Priors are bound as vlgp_elbo binds them.  0 <= max_lag <= 64, effective ranks
+ * <= 64; the workspace of c takes n_rep rows (max_lag + 1) L doubles of device memory: beyond 4 GiB the call is refused
+ * with the bytes it would need (VLGP_ERR_STATE).  Refused (VLGP_ERR_STATE): a copied cut, group replicas ("replicate
+ * with held_out="), more than one rank.  The call only reads: no set state changes.  Fixed-order sums without atomics:
+ * the same bits on every run. */
+int vlgp_lag_moments(vlgp_ctx* ctx, int set, int vb, int max_lag, double* resid, double* model, double* count,
+                     int* n_failed);
+
 /* ---- parameters ------------------------------------------------------- */
 int vlgp_set_params(vlgp_ctx* ctx, const double* a, const double* b, const double* noise);
 /* Any pointer may be NULL.  da, db are the last M-step increments

@@ -138,6 +138,7 @@ _SIGNATURES = {
     "vlgp_calibration_cov": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "vlgp_pair_moments": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
     "vlgp_pair_moments_cov": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp]),
+    "vlgp_lag_moments": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

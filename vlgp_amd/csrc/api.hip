@@ -124,6 +124,8 @@ UnitSet* vlgp_get_set(vlgp_ctx* ctx, int set, bool must_be_valid) {
       "vlgp_pair_moments on a copied cut: merge it and score the source set")                                         \
     X(vlgp_pair_moments_cov, SET_ANY & ~(SET_COPIED | SET_GROUPS),                                                    \
       "vlgp_pair_moments_cov on a copied cut: merge it and score the source set")                                     \
+    X(vlgp_lag_moments, SET_ANY & ~(SET_COPIED | SET_GROUPS),                                                         \
+      "vlgp_lag_moments on a copied cut: merge it and score the source set")                                          \
     X(vlgp_update_w, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_update_v, SET_FIT | SET_SOURCE, nullptr)                                                                   \
     X(vlgp_mstep_begin, SET_FIT | SET_SOURCE, nullptr)                                                                \

@@ -76,6 +76,47 @@ inline int64_t pair_lds_doubles(int64_t L) {
     return 3 * L * 64 + L + (npair > L ? npair : L) + 128 + 128 + 64;
 }
 
+// vlgp_lag_moments (lags.hip), for `rows` rows per replica, post_rows = n_rep rows rows of the posterior's set and its
+// `tasks` (unit, latent) pairs, lags 0 ... K, on n_cu compute units: w (post_rows, L) | c (post_rows, K + 1, L) | flags
+// (tasks) -- none of the three when vb == 0 -- | partials (n_rep, tiles, n_chunks, 3, K + 1, 64) | resid | model | count
+// (n_rep, K + 1, N each).  tiles = ceil(N / 64) channel tiles.  A wave takes chunk_rows rows of one (tile, replica): as
+// many chunks as give every compute unit eight waves, no more than keep the partials within LAG_PART_DOUBLES, and never
+// fewer than LAG_MIN_CHUNK rows each (a chunk also walks the K rows behind it).
+#define LAG_MAX 64
+#define LAG_GROUP 8  // lags a lane accumulates in registers per walk over its chunk
+#define LAG_MIN_CHUNK 128
+#define LAG_PART_DOUBLES (int64_t(1) << 22)  // 32 MiB
+#define LAG_C_DOUBLES (int64_t(1) << 29)     // 4 GiB: the most the c workspace may take of the call's block
+struct LagLayout { int64_t w, c, flag, part, resid, model, count, tiles, chunk_rows, n_chunks, c_doubles, need; };
+inline LagLayout lag_layout(int64_t rows, int64_t N, int64_t L, int64_t n_rep, int64_t tasks, int64_t K, bool vb,
+                            int64_t n_cu) {
+    const int64_t tiles = (N + 63) / 64, groups = tiles * n_rep, K1 = K + 1, post_rows = n_rep * rows;
+    const int64_t want = (8 * n_cu + groups - 1) / groups, cap = LAG_PART_DOUBLES / (groups * 3 * K1 * 64);
+    const int64_t most = want < cap ? want : (cap > 1 ? cap : 1);
+    const int64_t even = (rows + most - 1) / most, chunk_rows = even > LAG_MIN_CHUNK ? even : LAG_MIN_CHUNK;
+    const int64_t n_chunks = (rows + chunk_rows - 1) / chunk_rows, c_doubles = vb ? post_rows * K1 * L : 0;
+    BlockLayout b;
+    return {b.doubles(vb ? post_rows * L : 0), b.doubles(c_doubles), b.ints(vb ? tasks : 0),
+            b.doubles(groups * n_chunks * 3 * K1 * 64), b.doubles(n_rep * K1 * N), b.doubles(n_rep * K1 * N),
+            b.doubles(n_rep * K1 * N), tiles, chunk_rows, n_chunks, c_doubles, b.need()};
+}
+// ... and what the call refuses before anything reaches the device (status -1 VLGP_ERR_ARG, -3 VLGP_ERR_STATE): text is a
+// format with one %lld, for arg -- the c workspace is refused by its bytes, never chunked silently
+struct LagRefusal { int status; const char* text; long long arg; };
+inline LagRefusal lag_refusal(int world, int max_lag, int rp, int64_t c_doubles) {
+    if (world > 1) return {-3, "vlgp_lag_moments: more than one rank (%lld)", world};
+    if (max_lag < 0 || max_lag > LAG_MAX) return {-1, "vlgp_lag_moments: max_lag = %lld, need 0 <= max_lag <= 64", max_lag};
+    if (rp > 64) return {-3, "vlgp_lag_moments: a prior factor has rank %lld, at most 64 are supported", rp};
+    if (c_doubles > LAG_C_DOUBLES)
+        return {-3, "vlgp_lag_moments: the cross-time covariances need %lld bytes of workspace, at most 4294967296 are taken: "
+                    "score fewer rows, replicas or lags per call", (long long)(8 * c_doubles)};
+    return {0, nullptr, 0};
+}
+// the LDS of a lag_task wave, in doubles: H (rp, rs) | u of 64 + K rows (+ EW_CH = 8 of slack) | w (64) | 1 / diag Lc (rp)
+inline int64_t lag_task_lds_doubles(int64_t rp, int64_t rs, int64_t K) { return rp * rs + (64 + K) * rs + 8 + 64 + rp; }
+// ... and of a lag_moments wave, in bytes: a^2 (L, 64) | the ring of d and s (K + 1, 64 each) | of live (K + 1, 64 int)
+inline int64_t lag_moments_lds_bytes(int64_t L, int64_t K) { return 8 * (L * 64 + 2 * (K + 1) * 64) + 4 * (K + 1) * 64; }
+
 // partials (N, n_blk, 4) | sums (N, 4) | terms (tasks, 4) | row_ell (rows, when wanted) | flags (tasks)
 struct ElboLayout { int64_t part, sums, terms, rows, flag, need; };
 inline ElboLayout elbo_layout(int64_t rows, int64_t N, int64_t tasks, int64_t n_blk, bool want_rows) {

@@ -355,8 +355,8 @@ int open_set(vlgp_ctx* ctx, int set, unsigned how, UnitSet** out, const Admissio
 int admit(vlgp_ctx* ctx, int set, const UnitSet* us, const Admission& a);
 extern const Admission admit_vlgp_loglik, admit_vlgp_predictive, admit_vlgp_calibration, admit_vlgp_elbo, admit_vlgp_forecast, admit_vlgp_marginal,
     admit_vlgp_joint_laplace, admit_vlgp_joint_posterior, admit_vlgp_joint_posterior_moments, admit_vlgp_predictive_cov,
-    admit_vlgp_calibration_cov, admit_vlgp_pair_moments,
-    admit_vlgp_pair_moments_cov;  // the scoring entry points' rows of the table (eval_api.hip)
+    admit_vlgp_calibration_cov, admit_vlgp_pair_moments, admit_vlgp_pair_moments_cov,
+    admit_vlgp_lag_moments;  // the scoring entry points' rows of the table (eval_api.hip)
 
 // profiling brackets (HIP events on ctx->stream)
 void vlgp_prof_begin(vlgp_ctx* ctx, int kind, hipStream_t st = nullptr);
@@ -445,6 +445,12 @@ int launch_calibration_cov(vlgp_ctx* ctx, UnitSet& us, int n_nodes, const double
 // (call_block.h) for the source's rows; who: the entry point, for the messages
 int launch_pair_moments(vlgp_ctx* ctx, const char* who, UnitSet& us, int vb, const double* d_mu, const double* d_cov,
                         double* d_part, double* d_resid, double* d_model);
+// lag moments of a plain or masked set's predictive distribution (lags.hip): lags 0 ... K, rp the largest effective rank
+// among the set's priors (bound), o = lag_layout (call_block.h) of the call and the regions it names: d_w, d_c, d_flag (read
+// and written only when vb), d_part, and d_resid, d_model, d_count (replicas, K + 1, N)
+struct LagLayout;
+int launch_lag_moments(vlgp_ctx* ctx, UnitSet& us, int vb, int K, int rp, const LagLayout& o, double* d_w, double* d_c,
+                       int* d_flag, double* d_part, double* d_resid, double* d_model, double* d_count);
 int launch_scatter(vlgp_ctx* ctx, UnitSet& cut, UnitSet& dst, int window);
 // expected log-likelihood sums per channel and KL terms per (unit, latent) of a plain set (elbo.hip); rp: the largest
 // effective rank among the set's priors; d_part: (N, ceil(rows / 256), 4) doubles of workspace

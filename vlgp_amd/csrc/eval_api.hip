@@ -1,5 +1,5 @@
 // The read-only scores of a unit set (include/vlgp_hip.h): vlgp_loglik, vlgp_predictive, vlgp_calibration and their _cov
-// siblings, vlgp_pair_moments and its, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior,
+// siblings, vlgp_pair_moments and its, vlgp_lag_moments, vlgp_elbo, vlgp_forecast, vlgp_marginal, vlgp_joint_laplace, vlgp_joint_posterior,
 // vlgp_joint_posterior_moments.
 // Every one is put together the same way: open the set,
 // check the arguments, lay the call's device block out (call_block.h), copy in, launch, copy out.
@@ -206,14 +206,19 @@ extern "C" int vlgp_pair_moments_cov(vlgp_ctx* ctx, int set, const double* mu, c
 // latent) tasks, an int for the launches, and rp, the largest effective rank among the set's lengths: it sizes the LDS of
 // the (unit, latent) kernels.  *n_failed starts at 0.
 struct Posterior { UnitSet* us = nullptr; int64_t tasks = 0; int rp = 1; };
+static int posterior_ready(vlgp_ctx* ctx, const char* what, int* n_failed, Posterior* p);
 static int open_posterior(vlgp_ctx* ctx, int set, const Admission& a, int* n_failed, Posterior* p) {
     CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &p->us, &a));
+    return posterior_ready(ctx, a.what, n_failed, p);
+}
+// ... everything behind the admission (vlgp_lag_moments checks its arguments in between)
+static int posterior_ready(vlgp_ctx* ctx, const char* what, int* n_failed, Posterior* p) {
     const UnitSet& us = *p->us;
     UnitSet& rows_of = vlgp_rows_owner(ctx, *p->us);  // (the set itself, or the source of a masked set of one replica)
     if (!rows_of.x_ones) CHK(vlgp_refresh_xb(ctx, rows_of));
     CHK(vlgp_bind_priors(ctx, *p->us));
     p->tasks = (int64_t)us.M * ctx->L;
-    if (p->tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (unit, latent) pairs", a.what);
+    if (p->tasks > 0x7fffffffLL) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s: too many (unit, latent) pairs", what);
     int T_seen = -1;
     for (int m = 0; m < us.M; ++m) {
         const int T = (int)(us.off[m + 1] - us.off[m]);
@@ -252,6 +257,41 @@ extern "C" int vlgp_elbo(vlgp_ctx* ctx, int set, int vb, double* row_sums, doubl
     cp.out(kl_terms, d + o.terms, sizeof(double) * 4 * (size_t)p.tasks);
     cp.out(row_ell, d + o.rows, sizeof(double) * (size_t)rows);
     return count_flags(cp, "vlgp_elbo", d_flag, p.tasks, n_failed);
+}
+
+// The lag moments of a plain or masked set (lags.hip): three (replicas, max_lag + 1, N) tables.  The posterior's set is the
+// set itself: a masked set of several replicas has units, offsets and bound priors of its own (replica-major), so the
+// (unit, latent) tasks cover every replica.  Group replicas score one channel group per replica from pairs the replica
+// table lists: they are told what to make instead.
+extern "C" int vlgp_lag_moments(vlgp_ctx* ctx, int set, int vb, int max_lag, double* resid, double* model, double* count,
+                                int* n_failed) {
+    static const char* who = "vlgp_lag_moments";
+    Posterior p;
+    CHK(open_set(ctx, set, OPEN_COLLECT | OPEN_WAIT | OPEN_PARAMS | OPEN_DEVICE, &p.us, nullptr));
+    if (!resid || !model || !count) return vlgp_fail(ctx, VLGP_ERR_ARG, "%s needs resid, model and count", who);
+    LagRefusal no = lag_refusal(ctx->world, max_lag, 0, 0);
+    if (no.status) return vlgp_fail(ctx, no.status, no.text, no.arg);
+    UnitSet* us = p.us;
+    if (us->is(SET_GROUPS))
+        return vlgp_fail(ctx, VLGP_ERR_STATE, "%s: replicate with held_out=: the lags of a channel are scored by entry masks", who);
+    CHK(admit(ctx, set, us, admit_vlgp_lag_moments));
+    CHK(posterior_ready(ctx, who, n_failed, &p));
+    UnitSet& rows_of = vlgp_rows_owner(ctx, *us);
+    if (rows_of.rows < 1) return vlgp_fail(ctx, VLGP_ERR_STATE, "%s on an empty set", who);
+    const int64_t n_rep = us->is(SET_BY_ROW) ? us->rep.n : 1, n_out = n_rep * (max_lag + 1) * ctx->N;
+    const LagLayout o = lag_layout(rows_of.rows, ctx->N, ctx->L, n_rep, p.tasks, max_lag, vb != 0, ctx->n_cu);
+    no = lag_refusal(ctx->world, max_lag, vb ? p.rp : 0, o.c_doubles);
+    if (no.status) return vlgp_fail(ctx, no.status, no.text, no.arg);
+    CallBlock blk(ctx);
+    HIPCHK(ctx, blk.alloc(o.need));
+    Copies cp(ctx);
+    CHK(launch_lag_moments(ctx, *us, vb, max_lag, p.rp, o, blk.at(o.w), blk.at(o.c), blk.ints(o.flag), blk.at(o.part),
+                           blk.at(o.resid), blk.at(o.model), blk.at(o.count)));
+    cp.out(resid, blk.at(o.resid), sizeof(double) * (size_t)n_out);
+    cp.out(model, blk.at(o.model), sizeof(double) * (size_t)n_out);
+    cp.out(count, blk.at(o.count), sizeof(double) * (size_t)n_out);
+    if (!vb) return cp.finish(who, "copy-out");
+    return count_flags(cp, who, blk.ints(o.flag), p.tasks, n_failed);
 }
 
 extern "C" int vlgp_forecast(vlgp_ctx* ctx, int set, int vb, int n_lengths, const int* lengths, const int* n_ext,

@@ -411,6 +411,24 @@ class Engine:
             self._ck(self.lib.vlgp_pair_moments(self.h, int(set_id), int(bool(vb)), dptr(resid), dptr(model)))
         return resid, model
 
+    def lag_moments(self, set_id, max_lag, vb=True):
+        """Lag moments of a set's predictive distribution (vlgp_lag_moments): ``(resid, model, count, n_failed)``, per
+        lag ``k = 0 ... max_lag`` and channel the sums over the pairs of rows ``(t, t + k)`` of one unit of the products of
+        residuals, of the predictive covariance of the two counts (``evaluation``'s docstring has the closed forms) and
+        the number of pairs.  (max_lag + 1, N) each for a plain set, (n_rep, max_lag + 1, N) for a set replicated with
+        ``held_out=``, where replica ``k`` counts a pair when it holds both entries out.  ``n_failed``: the (unit, latent)
+        pairs whose ``H`` could not be factored; their units add nothing.  Needs bound priors.  Changes no state."""
+        max_lag = int(max_lag)
+        if max_lag < 0:  # (nothing to size the outputs by; the library refuses a lag past 64)
+            raise ValueError("max_lag = %d, need 0 <= max_lag <= 64" % max_lag)
+        rep = self.replicas.get(set_id)
+        shape = (max_lag + 1, self.N) if rep is None else (rep.n, max_lag + 1, self.N)
+        resid, model, count = np.empty(shape), np.empty(shape), np.empty(shape)
+        n = C.c_int(0)
+        self._ck(self.lib.vlgp_lag_moments(self.h, int(set_id), int(bool(vb)), max_lag, dptr(resid), dptr(model),
+                                           dptr(count), C.byref(n)))
+        return resid, model, count, n.value
+
     def elbo(self, set_id, vb=True, want_rows=False):
         """Terms of the variational lower bound of a plain set (vlgp_elbo): ``(row_sums, kl_terms, n_failed, row_ell)``
         -- row_sums (N, 4) per channel, kl_terms (units, L, 4) = log det H, tr H^-1, beta'beta, |mu - G beta|^2 per

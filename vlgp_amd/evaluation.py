@@ -207,6 +207,19 @@ MAP) for the mean-field posterior, the full ``cov[t]`` for the joint one -- and 
   ``dispersion[n] = resid_nn / model_nn`` is the ratio of the summed squared residual to the summed predictive variance
   (``calibration``'s ``dispersion`` is the mean of the per-entry ratios: the two agree where the variance is constant).
 
+Residual autocorrelation (``residual_autocorrelation``, ``Engine.lag_moments``, ``vlgp_lag_moments``).  The same question
+along time: does a channel's residual at row ``t`` still predict the one at row ``t + k`` of the same trial?  The posterior
+of latent ``l`` has the covariance ``S_l = G_l (I + G_l' W_l G_l)^-1 G_l'``; ``v`` is its diagonal, ``c_l(t, s)`` its entry
+``(t, s)``, with ``w`` recomputed from ``mu, v`` over the entries the posterior saw (every entry of a plain set, the ones a
+replica does not hold out).  With ``q_n(t, s) = sum_l a_ln^2 c_l(t, s)`` and ``e, s, d`` as above:
+
+- ``resid[k, n] = sum d_tn d_{t+k,n}``, ``model[k, n] = sum s_tn s_{t+k,n} f(q_n(t, t + k))`` (``f = expm1`` Poisson, the
+  identity Gaussian; at ``k = 0`` plus ``e_tn`` or ``noise[n]``), ``count[k, n]`` the pairs summed: the ``t`` with ``t + k``
+  in the same trial and both entries live.  Under MAP ``c = 0``.
+- ``residual_acf = resid / count / var`` with ``var[n] = model[0, n] / count[0, n]``, ``model_acf`` the same of ``model``,
+  ``excess_acf`` their difference, ``se_null = 1 / sqrt(count)``, ``dispersion = resid[0] / model[0]``; NaN where
+  ``count`` is 0 (a lag longer than every trial) or ``var`` is not positive.
+
 Every sum is a fixed-order device reduction (``vlgp_loglik``, ``vlgp_elbo``, ``vlgp_forecast``, ``vlgp_marginal``,
 ``vlgp_predictive``, ``vlgp_calibration``, ``vlgp_joint_laplace``, ``vlgp_joint_posterior``, ``vlgp_pair_moments`` and the
 ``_cov`` scores): the results are the same bits on every run.
@@ -225,7 +238,8 @@ from .util import _per_trial_entries
 __all__ = ["loglik", "leave_one_out", "leave_group_out", "channel_folds", "co_bits_per_spike", "plan_chunks",
            "bits_per_spike", "REPLICA_BUDGET_BYTES", "elbo", "elbo_from_terms", "forward_prediction", "entry_folds",
            "entry_scores", "leave_entries_out", "impute", "marginal_loglik", "weights_summary", "hermite_nodes",
-           "joint_posterior", "calibration", "calibration_from_sums", "residual_correlation"]
+           "joint_posterior", "calibration", "calibration_from_sums", "residual_correlation",
+           "residual_autocorrelation"]
 
 SAMPLE_CHUNK = 64  # draws per device call: one lane per sample (csrc/marginal.hip)
 
@@ -246,12 +260,13 @@ def plan_chunks(channels, max_replicas):
     return [channels[i:i + step] for i in range(0, len(channels), step)]
 
 
-def default_max_replicas(rows, n_latents, budget=REPLICA_BUDGET_BYTES, mask_channels=0, gauss=False):
+def default_max_replicas(rows, n_latents, budget=REPLICA_BUDGET_BYTES, mask_channels=0, gauss=False, extra_bytes=0):
     """Replicas of a ``rows``-row test set that fit ``budget`` bytes (at least one).  ``mask_channels``: the channel count
     of a replica with per-entry masks (``Engine.replicate(held_out=...)``), which adds one 64-bit word per row and 64
-    channels and, with a Gaussian channel (``gauss``), the per-row constant of ``w``: one double per (row, latent)."""
+    channels and, with a Gaussian channel (``gauss``), the per-row constant of ``w``: one double per (row, latent).
+    ``extra_bytes``: what the score of a replica takes beside it (``lag_moments``' workspace)."""
     rows, n_latents = max(int(rows), 1), max(int(n_latents), 1)
-    per = _DOUBLES_PER_ROW_LATENT * 8 * rows * n_latents
+    per = _DOUBLES_PER_ROW_LATENT * 8 * rows * n_latents + int(extra_bytes)
     if mask_channels:
         per += 8 * rows * ((int(mask_channels) + 63) // 64) + (8 * rows * n_latents if gauss else 0)
     return max(int(budget // per), 1)
@@ -1049,6 +1064,101 @@ def residual_correlation(trials, params, config, how="in_sample", groups=None, n
     out = _pair_summary(*total)
     out["n_failed"] = int(n_failed)
     out.update(extra)
+    return out
+
+
+def _lag_summary(resid, model, count):
+    """Residual autocorrelations from the lag moments (pure host code).  ``resid``, ``model``, ``count`` (K + 1, N):
+    ``Engine.lag_moments``' sums; a (lag, channel) with ``count`` 0 or NaN was never scored.
+
+    Returns a dict: ``resid``, ``model``, ``count`` with NaN where nothing was scored; ``residual_acf``, ``model_acf``,
+    ``excess_acf`` and ``se_null`` (K + 1, N) and ``dispersion`` (N) by the module docstring, NaN where ``count`` is 0 or
+    the channel's variance ``model[0] / count[0]`` is not positive; ``rms_excess`` (N) over the lags ``1 ... K`` with a
+    finite excess, ``rms_excess_all`` over those of every channel and ``n_scored``, their number."""
+    resid, model, count = (np.array(x, dtype=float) for x in (resid, model, count))
+    if resid.ndim != 2 or model.shape != resid.shape or count.shape != resid.shape:
+        raise ValueError("resid, model and count must be (K + 1, N), got %r, %r, %r" % (resid.shape, model.shape, count.shape))
+    scored = count > 0  # (False for NaN)
+    resid, model, count = (np.where(scored, x, np.nan) for x in (resid, model, count))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = model[0] / count[0]
+        var = np.where(var > 0, var, np.nan)
+        residual_acf, model_acf = resid / count / var, model / count / var
+        se_null = 1.0 / np.sqrt(count)
+        dispersion = resid[0] / np.where(model[0] > 0, model[0], np.nan)
+    excess = residual_acf - model_acf
+    sq = np.where(np.isfinite(excess[1:]), excess[1:], 0.0) ** 2
+    n_fin = np.isfinite(excess[1:]).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rms = np.where(n_fin > 0, np.sqrt(sq.sum(axis=0) / n_fin), np.nan)
+    n_all = int(n_fin.sum())
+    return {"resid": resid, "model": model, "count": count, "residual_acf": residual_acf, "model_acf": model_acf,
+            "excess_acf": excess, "se_null": se_null, "dispersion": dispersion, "rms_excess": rms,
+            "rms_excess_all": float(np.sqrt(sq.sum() / n_all)) if n_all else float("nan"), "n_scored": n_all}
+
+
+def _lag_scorer(max_lag):
+    """``Engine.lag_moments`` as ``_replica_chunk`` takes a scorer: per replica ``resid | model | count`` stacked, (n_rep, 3,
+    K + 1, N), and no per-entry output; ``n_failed`` adds up the (unit, latent) pairs without a factor."""
+    def scorer(eng, set_id, vb, mu=None, cov=None):
+        resid, model, count, bad = eng.lag_moments(set_id, max_lag, vb=vb)
+        scorer.n_failed += bad
+        return np.stack([x.reshape((-1,) + x.shape[-2:]) for x in (resid, model, count)], axis=1), None
+    scorer.width, scorer.predictive, scorer.n_failed = 3, True, 0
+    return scorer
+
+
+def _lag_replica_bytes(rows, L, max_lag):
+    """Device bytes one more replica adds to a ``lag_moments`` call: ``w`` and the cross-time covariances ``c``."""
+    return 8 * int(rows) * int(L) * (int(max_lag) + 2)
+
+
+def residual_autocorrelation(trials, params, config, max_lag=20, how="in_sample", groups=None, n_folds=5, seed=0,
+                             n_iter=None, device=0):
+    """Residual autocorrelation of every channel: does its residual at bin ``t`` still predict the one at ``t + k``,
+    ``k = 0 ... max_lag`` (at most 64), beyond what the predictive distribution says (module docstring)?  Excess at
+    lags 1-3 is what spike-history regressors (``history=``) absorb; slow positive excess over many lags says the GP
+    timescales ``omega`` are too smooth.  Pairs of bins never cross a trial.
+
+    ``how="in_sample"``: the trials' own ``mu, v``.  ``how="channels"``: every fold of ``groups`` (default
+    ``channel_folds(N, min(n_folds, N), seed)``) held out as a mask that is constant along the rows, the latents inferred
+    without it from a zero start (``n_iter`` E-step iterations, default ``config["max_iter"]``), each channel taken from
+    the replica that held it out.  The mean-field posterior only.  Trials that carry ``missing`` raise ``ValueError``.
+
+    Returns ``_lag_summary``'s dict plus ``n_failed``: failed E-step updates and (trial, latent) pairs whose ``H`` had no
+    factor (their trials are in no sum)."""
+    if how not in ("in_sample", "channels"):
+        raise ValueError("how must be 'in_sample' or 'channels', got %r" % (how,))
+    max_lag = int(max_lag)
+    if not 0 <= max_lag <= 64:
+        raise ValueError("max_lag = %d, need 0 <= max_lag <= 64" % max_lag)
+    _no_missing(trials, "residual_autocorrelation")
+    scorer = _lag_scorer(max_lag)
+    N, L = int(params["ydim"]), int(params["zdim"])
+    rows = int(sum(int(tr["y"].shape[0]) for tr in trials))
+    vb = config.get("method", "VB") == "VB"
+    n_failed = 0
+    if how == "channels":
+        groups = _check_groups(channel_folds(N, min(int(n_folds), N), seed) if groups is None else groups, N)
+        n_it = int(config["max_iter"] if n_iter is None else n_iter)
+        got = []
+        with _resident(trials, params, _zero_start(trials, L), device) as eng:
+            cap = default_max_replicas(rows, L, mask_channels=N, gauss=bool(eng.gauss.any()),
+                                       extra_bytes=_lag_replica_bytes(rows, L, max_lag))
+            for chunk in plan_chunks(list(_group_masks(groups, rows, N)), cap):
+                s, _, bad, _ = _replica_chunk(eng, n_it, config["dmu_bound"], vb, scorer=scorer, held_out=np.stack(chunk))
+                got.extend(s)
+                n_failed += bad
+        total = np.full((3, max_lag + 1, N), np.nan)
+        for k, g in enumerate(groups):
+            total[:, :, g] = got[k][:, :, g]
+    else:
+        units = [{"y": tr["y"], "x": tr.get("x"), "mu": tr["mu"], "v": tr.get("v", np.zeros((tr["y"].shape[0], L))),
+                  "w": None} for tr in trials]
+        with _resident(trials, params, units, device) as eng:
+            total = scorer(eng, SET_TEST, vb)[0][0]
+    out = _lag_summary(*total)
+    out["n_failed"] = int(n_failed) + scorer.n_failed
     return out
 
 
